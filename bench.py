@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- quartets counted per second on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints the headline line (`metric`, `value`, `unit`, `ms_per_step`, ...). Every
+leg, gate and secondary measurement described below (cpu_baseline, e2e and p2p legs, the OTHER mode's leg, collective alone /
+count-only, parity gates, scoring, config.secondary, roofline, issue probe) runs only with `--full`. `--dump-outputs DIR` writes
+what the last timed step computed to DIR/*.npy (dump_outputs).
 
 `--gpus N` with N > 1 (or `--via-launcher`) and no WORLD_SIZE in the environment: this process is only the PARENT. Before any
 GPU call it starts one fresh child `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
@@ -114,6 +119,13 @@ def parse_args():
     ap.add_argument("--secondary", type=int, default=-1,
                     help="after the timed region also measure 3 steps each of 512 taxa x 1500 trees with --collapse 0.2 / --dropout 0.1 / --mixed on the resident "
                          "table, and configs[1], one rank's share of configs[3], one shard of configs[4] (config.secondary); -1 = on for the default N = 1 line")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg, gate and secondary measurement beside the timed steps (cpu_baseline, CLI e2e, p2p and other-mode "
+                         "legs, collective alone / count-only, parity gates, scoring, upload-inclusive steps, secondary workloads, roofline, "
+                         "issue probe); without it a run sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (this rank's count table, or its reduced table / "
+                         "shard after a table collective) to DIR as .npy: a fixed, seeded sample of tuples (float64) and the per-cell sums")
     ap.add_argument("--cpu-child", default="", help=argparse.SUPPRESS)
     ap.add_argument("--gen-child", default="", help=argparse.SUPPRESS)
     return ap.parse_args()
@@ -577,6 +589,39 @@ def valu_frac(variant, m, units, count_ms):
     return units * ops32 / 32.0 / (count_ms * 1e-3) / 1e12 / VALU_PEAK_TLOPS, ops32
 
 
+DUMP_TUPLES = 1 << 20            # sampled tuples over all ranks: 24 MB of cells + 8 MB of indices (float64)
+DUMP_SEED = 1234567
+
+
+def dump_outputs(out_dir, words, n_tuples, bits, rank, world):
+    """--dump-outputs: one rank's result of the last timed step (`words`: int32 words of [tuple][3] u16 / u32 cells) as float64 .npy
+    files in out_dir (suffix _rank<r> when rank is not None):
+        count_table_sample.npy        [k, 3] cells of k tuples (every tuple when the rank holds at most DUMP_TUPLES / world of them)
+        count_table_sample_index.npy  [k] their tuple indices in this rank's table / shard (a fixed seeded sample, sorted)
+        count_table_cell_sums.npy     [3] each cell summed over ALL tuples of the rank
+    The sample depends only on (n_tuples, world): two builds given the same arguments dump the same tuples."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    k = DUMP_TUPLES // world
+    if n_tuples <= k:
+        idx = np.arange(n_tuples, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n_tuples, size=k, dtype=np.int64))
+    flat = words if bits == 32 else words.view(torch.int16)
+    assert flat.numel() >= 3 * n_tuples and (len(idx) == 0 or int(idx[-1]) < n_tuples)
+    cells = flat[: 3 * n_tuples].view(n_tuples, 3)
+    mask = 0xFFFFFFFF if bits == 32 else 0xFFFF
+    sample = (cells.index_select(0, torch.from_numpy(idx).to(words.device)).to(torch.int64) & mask).cpu().numpy()
+    sums = torch.zeros(3, dtype=torch.int64, device=words.device)
+    for lo in range(0, n_tuples, 1 << 26):
+        sums += (cells[lo: min(n_tuples, lo + (1 << 26))].to(torch.int64) & mask).sum(dim=0)
+    sfx = "" if rank is None else f"_rank{rank}"
+    np.save(os.path.join(out_dir, f"count_table_sample{sfx}.npy"), sample.astype(np.float64))
+    np.save(os.path.join(out_dir, f"count_table_sample_index{sfx}.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, f"count_table_cell_sums{sfx}.npy"), sums.cpu().numpy().astype(np.float64))
+
+
 
 
 def auto_mode(n, m_total, world, binary_full=True):
@@ -770,7 +815,7 @@ def main():
     # seeded inputs: seed = 1000 * config + tree-set id. Split configs: ONE set of m_total trees, rank
     # r takes trees [t_lo, t_hi); otherwise rank r counts its own set r (tree t of a set depends only on (seed, t)).
     seed_ref, seed_set = 1000 * cfg_no, 1000 * cfg_no + 1 + (0 if (split or par_mode == "table") else rank)
-    want_other_leg = multi and par_mode in ("tree", "table") and not (args.table_shards or cfg["shards"] > 1) and binary_full_trees and args.algo == "gather" \
+    want_other_leg = args.full and multi and par_mode in ("tree", "table") and not (args.table_shards or cfg["shards"] > 1) and binary_full_trees and args.algo == "gather" \
         and (args.other_leg == 1 or args.other_leg < 0)
     t_gen = time.perf_counter()
     batch_all = None
@@ -809,8 +854,8 @@ def main():
     gen_s = time.perf_counter() - t_gen
 
     # the secondary workloads' trees: generated beside the cpu_baseline leg, loaded after the timed region
-    want_secondary = args.secondary == 1 or (args.secondary < 0 and world == 1 and not custom and cfg_no == 2 and binary_full_trees
-                                             and args.algo == "gather" and shards == 1 and not args.nni and not multi)
+    want_secondary = args.full and (args.secondary == 1 or (args.secondary < 0 and world == 1 and not custom and cfg_no == 2 and binary_full_trees
+                                             and args.algo == "gather" and shards == 1 and not args.nni and not multi))
     sec_dir, sec_jobs = (None, [])
     if want_secondary and rank == 0:
         sec_dir, sec_jobs = start_secondary_generators(ref_nw, n, 1500, seed_set)
@@ -818,11 +863,11 @@ def main():
     # cpu_baseline leg first, in a child process, BEFORE this process touches the GPU (N = 1 only)
     cpu_baseline = None
     # (N = 1 only, as the measurement contract says: at N > 1 the other ranks would sit at the rendezvous for the two minutes it takes)
-    if not args.no_cpu_baseline and rank == 0 and (world == 1 or args.cpu_baseline_at_n):
+    if args.full and not args.no_cpu_baseline and rank == 0 and (world == 1 or args.cpu_baseline_at_n):
         cpu_baseline = run_cpu_baseline(ref_nw, sample_text, n, m, ranks.n_quartets(n), args.cpu_budget_s)
 
     cli_e2e = None
-    if not args.no_e2e and world == 1 and binary_full_trees and shards == 1 and args.algo == "gather":
+    if args.full and not args.no_e2e and world == 1 and binary_full_trees and shards == 1 and args.algo == "gather":
         cli_e2e = run_cli_e2e(ref_nw, sample_text)
         if "error" not in cli_e2e:      # the first process on a fresh box pays the driver's cold start (HIP runtime up after ~250 ms instead of ~80)
             time.sleep(3.0)             # (a process that starts right after another one released a 17-34 GB table waits in its own hipMalloc
@@ -835,7 +880,7 @@ def main():
     # a child process of rank 0 BEFORE rank 0 touches its GPU (the other ranks wait at the rendezvous with idle devices), so that
     # one N-GPU run measures the RCCL path (`value`) and the p2p path (`config.p2p_leg`) side by side.
     p2p_leg = None
-    want_p2p = args.p2p_leg == 1 or (args.p2p_leg < 0 and world > 1 and split)
+    want_p2p = args.full and (args.p2p_leg == 1 or (args.p2p_leg < 0 and world > 1 and split))
     if want_p2p and rank == 0 and binary_full_trees and shards == 1 and args.algo == "gather":
         p2p_leg = run_cli_e2e(ref_nw, sample_text, threads=0, extra=["--gpus", str(world), "--reduce", "p2p", "--trace"])
         if p2p_leg.get("counting_phase_ms"):
@@ -987,6 +1032,23 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
+    def step_result():
+        """What the last step handed this rank, as (int32 words of [tuple][3] u16 / u32 cells, tuples, cell bits): the table, or after
+        a table collective the reduced table / this rank's reduced shard (the two-cell wire formats unpacked to three cells)."""
+        if not collective:
+            return table, nq, count_bits
+        if reduce_mode == "scatter":
+            red, n_red = recv[last_buf[0]], distributed.scatter_owned(ctx.table_tuples, world, rank, layout_wire)[1]
+        else:
+            red, n_red = (wire if (wire16 or wire32x2) else tables)[last_buf[0]], nq
+        if wire_fmt in ("u16x2", "u32x2"):
+            bits_ = 16 if wire_fmt == "u16x2" else 32
+            cells = torch.zeros(distributed.table_words(max(n_red, 1), bits_), dtype=torch.int32, device=dev)
+            (ctx.unpack16x2 if bits_ == 16 else ctx.unpack32x2)(red, n_red, total_trees_reduced, cells)
+            ctx.sync()
+            return cells, n_red, bits_
+        return red, n_red, bits_wire
+
     # first step: lazy initialisation (code objects, RCCL communicator); second step: its duration sizes the run
     step()
     drain()
@@ -1036,9 +1098,13 @@ def main():
         elapsed = float(tt.item())
 
     drain()
+    if args.dump_outputs and steps > 0:
+        words, n_res, bits_res = step_result()
+        dump_outputs(args.dump_outputs, words, n_res, bits_res, rank if world > 1 else None, world)
+        del words
     # collective alone (N > 1): the same buffers, nothing else on the GPU, a few repetitions
     coll_alone_ms = None
-    if collective and steps > 0:
+    if args.full and collective and steps > 0:
         src = (wire if (wire16 or wire32x2) else tables)[last_buf[0]]
         fence()
         c0 = time.perf_counter()
@@ -1056,7 +1122,7 @@ def main():
     # the SAME ranks count the SAME shares without the table collective, inside this run: what the step costs when nothing is
     # exchanged (max over ranks). scaling_efficiency = value / (N x one rank's count-only rate) then reads from this line alone.
     count_only_ms = None
-    if collective and steps > 0:
+    if args.full and collective and steps > 0:
         fence()
         step(exchange=False)
         ctx.sync()
@@ -1078,7 +1144,7 @@ def main():
     # gate on the REDUCED table of the last step: every tuple sums to the total number of trees (binary, full trees)
     reduced_ok = None
     shard16 = None
-    if collective and steps > 0:
+    if args.full and collective and steps > 0:
         if reduce_mode == "scatter":
             own_lo, own_n = distributed.scatter_owned(ctx.table_tuples, world, rank, layout_wire)
             red, n_red = recv[last_buf[0]], own_n
@@ -1119,10 +1185,11 @@ def main():
     # (the roofline's `avg_launch_ms`). A sub-millisecond step is too short for one sample: there, and only there, the
     # average over a few extra event-bracketed steps is used and labelled `kernel_ms_source`.
     last_launches = ctx.last_count_launches() if steps > 0 else 0
-    kernel_ms_source = "last step of the timed region"
-    if last_step_ms and last_launches and one_ms >= 5:
+    panel_ms = count_ms = launches = kernel_ms_source = None
+    if args.full and last_step_ms and last_launches and one_ms >= 5:
+        kernel_ms_source = "last step of the timed region"
         panel_ms, count_ms, launches = float(last_step_ms[0]), float(last_step_ms[1]), int(last_launches)
-    else:
+    elif args.full:
         kern = []
         for _ in range(max(3, min(steps, 10))):
             step(timed=True)
@@ -1133,9 +1200,10 @@ def main():
         kernel_ms_source = f"mean of {len(kern)} extra event-bracketed steps after the timed region"
     variant = ctx.last_count_variant()
 
-    # ---- parity gates run with every measurement -------------------------------------------------------------
-    step()
-    ctx.sync()
+    # ---- parity gates run with every --full measurement --------------------------------------------------------
+    if args.full:
+        step()
+        ctx.sync()
     # ---- scoring (secondary metric of SURVEY 8(d)): ONE cold call (first use: reference tree, LCA matrix, plans,
     # accumulator allocation) and then warm calls; phases from qs_last_score_ms. It runs BEFORE the gates below: they
     # allocate and free tens of GB of scratch (a 17 GB table, a 34 GB clone), and the first hipMalloc after such a free
@@ -1143,7 +1211,7 @@ def main():
     score_cold_ms = score_ms = None
     score_phases_cold = score_phases = None
     score_mode = None
-    if not args.no_score:
+    if args.full and not args.no_score:
         def score_once():
             torch.cuda.synchronize(dev)
             s0 = time.perf_counter()
@@ -1186,7 +1254,7 @@ def main():
                           "table_pass_ms": round(t_ms, 3), "note": "pass 1 incl. the two samples" if one_read else "pass 1 + pass 2"}
 
     parity = None
-    if binary_full_trees:              # tuples sum to m only when every tree resolves every quartet
+    if args.full and binary_full_trees:    # tuples sum to m only when every tree resolves every quartet
         parity = True
         t16 = table.view(torch.int16)
         for c0_ in range(0, nq, 1 << 26):
@@ -1198,7 +1266,7 @@ def main():
     # independent byte-SWAR implementation of the same count produces, bit for bit, on the device
     impl_match = None
     free_b, _tot = torch.cuda.mem_get_info(dev)
-    if args.algo == "gather" and "bitslice" in variant and not args.no_impl_check and free_b > table.numel() * 4 + (4 << 30):
+    if args.full and args.algo == "gather" and "bitslice" in variant and not args.no_impl_check and free_b > table.numel() * 4 + (4 << 30):
         mine = table.clone()
         ctx.set_tuning(_lib.QS_TUNE_GATHER_IMPL, _lib.QS_IMPL_SWAR)
         step()
@@ -1213,7 +1281,7 @@ def main():
     # third gate, independent of every kernel: random quartets of this rank's table against the split-based brute
     # force (tests/bruteforce.py) on a short prefix of this rank's trees, counted into a scratch context
     lookup_ok = None
-    if rank == 0 and binary_full_trees:
+    if args.full and rank == 0 and binary_full_trees:
         import bruteforce
         k_trees = min(m, 48)
         rng = np.random.default_rng(12345)
@@ -1233,7 +1301,7 @@ def main():
     # ---- e2e leg 2: the same step with the host-array upload (qs_batch_upload: validation, pinned staging, H2D copy)
     # inside the timed region; the boundary hands over host arrays, so this is the PCIe-inclusive rate
     upload_step_ms = None
-    if not args.no_e2e and args.algo == "gather":
+    if args.full and not args.no_e2e and args.algo == "gather":
         def up_step():
             h2 = ctx.batch_upload(batch, with_nodes=False)
             ctx.count_batch(h2, step_algo)
@@ -1352,7 +1420,7 @@ def main():
     # how fast THIS device runs the count kernel's bare instruction slot (qs_issue_probe: 24 v_bitop3 + 4 v_bcnt in registers, 4
     # waves per SIMD): boxes of one pool differ by several per cent; the figure makes lines from different boxes comparable
     box_probe_ns = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             box_probe_ns = ctx.issue_probe(60000)
         except Exception:        # diagnostic only
@@ -1385,13 +1453,6 @@ def main():
     else:
         units_per_step = (m_total if split else m * world) * nq_all
     value = units_per_step * steps / elapsed
-    bytes_per_unit = 2 * (count_bits // 8)
-    units_per_launch = m * nq / launches
-    launch_ms = count_ms / launches
-    import re
-    mode, classes, ops32 = parse_variant(variant, m)
-    depth_bits = max((b_ for b_, _, _ in classes), default=None)
-    import re
     wl_name = (f"configs[{cfg_no}]" if not custom else "custom")
     workload_key = f"n{n}_m{m}_u{count_bits}_shard{d_lo}-{d_hi}_{'ladder' if args.shape == 'ladder' else 'nni' if args.nni else 'random'}" + ("" if binary_full_trees else f"_c{args.collapse}_d{args.dropout}" + ("_mixed" if args.mixed else ""))
     out = {
@@ -1472,52 +1533,58 @@ def main():
             if cli_e2e.get("counting_phase_ms"):
                 e2e["cli_counting_quartets_per_s"] = m * nq_all / (cli_e2e["counting_phase_ms"] * 1e-3)
         out["e2e"] = e2e
-    kname = (("count_bitslice3_fused_kernel" if "/fused:" in variant else "count_bitslice3_kernel") if "bitslice" in variant else "count_gather_kernel") if args.algo == "gather" else "count_scatter_kernel"
-    hbm_ratio = (units_per_launch * bytes_per_unit) / (launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-    table_bytes = ctx.table_bytes
-    panel_bytes = ((m + 31) // 32) * (n * (n - 1) // 2) * (max(depth_bits or 4, 4) * 4) if depth_bits else None
-    if ops32:
-        achieved = units_per_launch * ops32 / 32.0 / (launch_ms * 1e-3) / 1e12
-        # what the instruction mix itself allows (profiles/r03_valu_yardstick.txt): v_bcnt_u32_b32 issues at half rate, so
-        # the minimal chain of a class with B depth bits takes 2 x (ops - pops) + 4 x pops cycles, not 2 x ops
-        cyc_min = sum((2 * (ops_of(b_, mo_) - POPS[mo_]) + 4 * POPS[mo_]) * cnt_ for b_, cnt_, mo_ in classes) / float(sum(cnt_ for _, cnt_, _ in classes))
-        mix_ceiling = 2.0 * ops32 / cyc_min
-        roof = {"bound": "valu_issue", "achieved": achieved, "peak": VALU_PEAK_TLOPS, "unit": "Tlane-op/s", "frac": achieved / VALU_PEAK_TLOPS,
-                "issue_model": {"bcnt_half_rate": True, "min_cycles_per_unit32": cyc_min, "mix_ceiling_frac": mix_ceiling,
-                                "frac_of_mix_ceiling": achieved / VALU_PEAK_TLOPS / mix_ceiling, "source": "profiles/r03_valu_yardstick.txt"},
-                "algorithmic_ops_per_unit": ops32 / 32.0,
-                "algorithmic_ops_note": f"{ops32:.3f} wave-instr per (quartet, 32 trees), classes (B, trees, mode): {classes}"[:100]}
-    else:                                   # scatter / SWAR paths: priced against HBM with SURVEY 8(d)'s bytes
-        achieved = (units_per_launch * bytes_per_unit) / (launch_ms * 1e-3) / 1e9
-        roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS}
-    roof.update({"traffic": None, "kernel": kname, "units_per_launch": units_per_launch, "avg_launch_ms": launch_ms,
-                 "launches_per_step": launches, "hbm_algorithmic_ratio": hbm_ratio,
-                 "hbm_algorithmic_note": "SURVEY 8(d) RMW bytes / time / 8 TB/s: speed-up over a perfect scatter, not a fraction",
-                 "hbm_model_bytes_per_step": (table_bytes * (2 * launches - 1) + 2 * panel_bytes) if panel_bytes else None,
-                 "hbm_model_note": "gather minimum: table 1 write + (launches-1) RMW, panel written+read once",
-                 "issued": None})
-    pmc = pmc_for(workload_key, variant)
-    if pmc:
-        roof["traffic"] = pmc.get("hbm_bytes_per_launch")
-        if pmc.get("valu_insts_per_launch"):
-            per_simd = pmc["valu_insts_per_launch"] / 1024.0
-            roof["issued"] = {"valu_wave_insts_per_launch": pmc["valu_insts_per_launch"],
-                              "cycles_per_valu_inst_at_2.4GHz": launch_ms * 1e-3 * 2.4e9 / per_simd,
-                              "frac_of_2_cycle_issue": 2.0 * per_simd / (launch_ms * 1e-3 * 2.4e9),
-                              "minimal_share": units_per_launch * ops32 / 32.0 / 64.0 / pmc["valu_insts_per_launch"] if ops32 else None}
-        roof["pmc_source"] = {k_: pmc.get(k_) for k_ in ("file", "collected", "kernel_source_sha", "fetch_size_kb", "write_size_kb", "l2_hit")}
-        if roof["traffic"]:
-            # the axis BASELINE.json north_star names: achieved HBM GB/s of the dominant kernel against the 8 TB/s roofline. traffic = the
-            # PMC bytes of one launch (FETCH_SIZE x 2 + WRITE_SIZE, profiles/<pmc file>) / THIS run's event-timed launch duration;
-            # over_model = traffic / the bytes the gather formulation has to move (table once, panel written + read once)
-            gbps = roof["traffic"] / (launch_ms * 1e-3) / 1e9
-            model_b = roof.get("hbm_model_bytes_per_step")
-            roof["hbm"] = {"achieved_gbps": round(gbps, 1), "frac_of_8tbps": round(gbps / HBM_PEAK_GBS, 4),
-                           "over_model": round(roof["traffic"] * launches / model_b, 2) if model_b else None,
-                           "note": "fabric traffic of the count kernel (PMC, builder-collected, same kernel source); the kernel is VALU-bound"}
-    else:
-        roof["pmc_source"] = f"none under profiles/ for kernel source {kernel_source_sha()}"
-    out["roofline"] = roof
+    if args.full:                           # the roofline prices the kernel figures measured above
+        bytes_per_unit = 2 * (count_bits // 8)
+        units_per_launch = m * nq / launches
+        launch_ms = count_ms / launches
+        mode, classes, ops32 = parse_variant(variant, m)
+        depth_bits = max((b_ for b_, _, _ in classes), default=None)
+        kname = (("count_bitslice3_fused_kernel" if "/fused:" in variant else "count_bitslice3_kernel") if "bitslice" in variant else "count_gather_kernel") if args.algo == "gather" else "count_scatter_kernel"
+        hbm_ratio = (units_per_launch * bytes_per_unit) / (launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+        table_bytes = ctx.table_bytes
+        panel_bytes = ((m + 31) // 32) * (n * (n - 1) // 2) * (max(depth_bits or 4, 4) * 4) if depth_bits else None
+        if ops32:
+            achieved = units_per_launch * ops32 / 32.0 / (launch_ms * 1e-3) / 1e12
+            # what the instruction mix itself allows (profiles/r03_valu_yardstick.txt): v_bcnt_u32_b32 issues at half rate, so
+            # the minimal chain of a class with B depth bits takes 2 x (ops - pops) + 4 x pops cycles, not 2 x ops
+            cyc_min = sum((2 * (ops_of(b_, mo_) - POPS[mo_]) + 4 * POPS[mo_]) * cnt_ for b_, cnt_, mo_ in classes) / float(sum(cnt_ for _, cnt_, _ in classes))
+            mix_ceiling = 2.0 * ops32 / cyc_min
+            roof = {"bound": "valu_issue", "achieved": achieved, "peak": VALU_PEAK_TLOPS, "unit": "Tlane-op/s", "frac": achieved / VALU_PEAK_TLOPS,
+                    "issue_model": {"bcnt_half_rate": True, "min_cycles_per_unit32": cyc_min, "mix_ceiling_frac": mix_ceiling,
+                                    "frac_of_mix_ceiling": achieved / VALU_PEAK_TLOPS / mix_ceiling, "source": "profiles/r03_valu_yardstick.txt"},
+                    "algorithmic_ops_per_unit": ops32 / 32.0,
+                    "algorithmic_ops_note": f"{ops32:.3f} wave-instr per (quartet, 32 trees), classes (B, trees, mode): {classes}"[:100]}
+        else:                                   # scatter / SWAR paths: priced against HBM with SURVEY 8(d)'s bytes
+            achieved = (units_per_launch * bytes_per_unit) / (launch_ms * 1e-3) / 1e9
+            roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS}
+        roof.update({"traffic": None, "kernel": kname, "units_per_launch": units_per_launch, "avg_launch_ms": launch_ms,
+                     "launches_per_step": launches, "hbm_algorithmic_ratio": hbm_ratio,
+                     "hbm_algorithmic_note": "SURVEY 8(d) RMW bytes / time / 8 TB/s: speed-up over a perfect scatter, not a fraction",
+                     "hbm_model_bytes_per_step": (table_bytes * (2 * launches - 1) + 2 * panel_bytes) if panel_bytes else None,
+                     "hbm_model_note": "gather minimum: table 1 write + (launches-1) RMW, panel written+read once",
+                     "issued": None})
+        pmc = pmc_for(workload_key, variant)
+        if pmc:
+            roof["traffic"] = pmc.get("hbm_bytes_per_launch")
+            if pmc.get("valu_insts_per_launch"):
+                per_simd = pmc["valu_insts_per_launch"] / 1024.0
+                roof["issued"] = {"valu_wave_insts_per_launch": pmc["valu_insts_per_launch"],
+                                  "cycles_per_valu_inst_at_2.4GHz": launch_ms * 1e-3 * 2.4e9 / per_simd,
+                                  "frac_of_2_cycle_issue": 2.0 * per_simd / (launch_ms * 1e-3 * 2.4e9),
+                                  "minimal_share": units_per_launch * ops32 / 32.0 / 64.0 / pmc["valu_insts_per_launch"] if ops32 else None}
+            roof["pmc_source"] = {k_: pmc.get(k_) for k_ in ("file", "collected", "kernel_source_sha", "fetch_size_kb", "write_size_kb", "l2_hit")}
+            if roof["traffic"]:
+                # the axis BASELINE.json north_star names: achieved HBM GB/s of the dominant kernel against the 8 TB/s roofline. traffic = the
+                # PMC bytes of one launch (FETCH_SIZE x 2 + WRITE_SIZE, profiles/<pmc file>) / THIS run's event-timed launch duration;
+                # over_model = traffic / the bytes the gather formulation has to move (table once, panel written + read once)
+                gbps = roof["traffic"] / (launch_ms * 1e-3) / 1e9
+                model_b = roof.get("hbm_model_bytes_per_step")
+                roof["hbm"] = {"achieved_gbps": round(gbps, 1), "frac_of_8tbps": round(gbps / HBM_PEAK_GBS, 4),
+                               "over_model": round(roof["traffic"] * launches / model_b, 2) if model_b else None,
+                               "note": "fabric traffic of the count kernel (PMC, builder-collected, same kernel source); the kernel is VALU-bound"}
+        else:
+            roof["pmc_source"] = f"none under profiles/ for kernel source {kernel_source_sha()}"
+        out["roofline"] = roof
 
     if p2p_leg is not None:
         out["config"]["p2p_leg"] = p2p_leg

@@ -183,3 +183,37 @@ def test_secondary_workload_children_and_the_fraction_helper(tmp_path):
     frac, ops = bench.valu_frac("gather/mixed/binary_partial.bitslice_b4x2:1000+general_full.bitslice_b4x2:500/count_u32/fused:1", 1500, units, 60.0)
     assert abs(ops - (15 * 1000 + 18 * 500) / 1500) < 1e-12 and frac > 0
     assert bench.valu_frac("gather/partial/depth_u8/count_u32", 10, 10, 1.0) == (None, None)
+
+
+def test_dump_outputs_writes_a_fixed_sample_and_the_cell_sums(tmp_path, monkeypatch):
+    """--dump-outputs: the [tuple][3] u32 / u16 cells of a rank's table as float64 .npy files -- every tuple when they fit the budget,
+    else the same seeded, sorted sample of tuple indices in every run -- and each cell summed over all tuples."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_TUPLES", 1000)
+    rng = np.random.default_rng(5)
+    for bits, n, rank, world in ((32, 700, None, 1), (32, 5000, None, 1), (16, 5001, 1, 2)):
+        cells = rng.integers(0, 1 << bits, size=(n, 3), dtype=np.int64)
+        if bits == 32:
+            words = torch.from_numpy(cells.astype(np.uint32).view(np.int32).ravel().copy())
+        else:
+            u16 = np.zeros(2 * ((3 * n + 1) // 2), dtype=np.uint16)
+            u16[: 3 * n] = cells.ravel()
+            words = torch.from_numpy(u16.view(np.int32).copy())
+        out = tmp_path / f"u{bits}_{n}"
+        bench.dump_outputs(str(out), words, n, bits, rank, world)
+        sfx = "" if rank is None else f"_rank{rank}"
+        sample = np.load(out / f"count_table_sample{sfx}.npy")
+        index = np.load(out / f"count_table_sample_index{sfx}.npy")
+        sums = np.load(out / f"count_table_cell_sums{sfx}.npy")
+        assert sample.dtype == index.dtype == sums.dtype == np.float64
+        assert (sample == cells[index.astype(np.int64)]).all() and (sums == cells.sum(axis=0)).all()
+        if n <= 1000 // world:
+            assert (index == np.arange(n)).all()
+        else:
+            assert 0 < len(index) <= 1000 // world and (np.diff(index) > 0).all() and index[-1] < n
+            bench.dump_outputs(str(tmp_path / "again"), words, n, bits, rank, world)
+            assert (np.load(tmp_path / "again" / f"count_table_sample_index{sfx}.npy") == index).all()
+        assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20

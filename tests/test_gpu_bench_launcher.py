@@ -10,7 +10,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
-SMALL = ["--taxa", "224", "--trees", "6000", "--steps", "40", "--warmup", "5", "--no-cpu-baseline", "--no-e2e", "--no-score"]
+SMALL = ["--taxa", "224", "--trees", "6000", "--steps", "40", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-e2e", "--no-score"]
 
 
 def run_bench(extra):
@@ -55,7 +55,7 @@ def test_forced_collective_line_carries_its_own_scaling_figures_and_the_p2p_leg(
     os.environ["QS_BENCH_FORCE_DIST"] = "1"
     try:
         doc = run_bench(["--gpus", "1", "--config", "3", "--taxa", "160", "--trees", "6000", "--steps", "10", "--warmup", "2", "--p2p-leg", "1",
-                         "--no-cpu-baseline", "--no-e2e", "--no-score"])
+                         "--full", "--no-cpu-baseline", "--no-e2e", "--no-score"])
     finally:
         del os.environ["QS_BENCH_FORCE_DIST"]
     cfg = doc["config"]
@@ -79,7 +79,7 @@ def test_table_mode_through_the_launcher_and_the_other_mode_leg():
     try:
         doc = run_bench(["--gpus", "1", "--via-launcher", "--mode", "table"] + SMALL)
         tree = run_bench(["--gpus", "1", "--mode", "tree", "--taxa", "160", "--trees", "6000", "--steps", "10", "--warmup", "2",
-                          "--no-cpu-baseline", "--no-e2e", "--no-score"])
+                          "--full", "--no-cpu-baseline", "--no-e2e", "--no-score"])
     finally:
         del os.environ["QS_BENCH_FORCE_DIST"]
     cfg = doc["config"]
@@ -101,7 +101,7 @@ def test_two_ranks_share_the_gpu_over_gloo_both_modes():
     sharded scoring over SUM / MIN / all-gather. Tree-sharded: 3000 trees per rank, the reduce-scatter of the one-word-per-tuple wire
     format, every rank scores the shard it received. Each line carries the other mode as a leg; all tuple-sum gates hold on every rank."""
     os.environ["QS_BENCH_BACKEND"] = "gloo"
-    common = ["--gpus", "2", "--taxa", "160", "--trees", "6000", "--steps", "6", "--warmup", "1", "--p2p-leg", "0", "--no-cpu-baseline", "--no-e2e"]
+    common = ["--gpus", "2", "--taxa", "160", "--trees", "6000", "--steps", "6", "--warmup", "1", "--p2p-leg", "0", "--full", "--no-cpu-baseline", "--no-e2e"]
     try:
         table = run_bench(common + ["--mode", "table"])
         tree = run_bench(common + ["--mode", "tree"])
@@ -128,7 +128,7 @@ def test_four_ranks_share_the_gpu_table_mode_and_auto():
     """Four ranks on cuda:0 over gloo (QS_BENCH_BACKEND=gloo): the table-sharded mode with four cost-balanced shards (qs_shard_bounds), the
     tree-sharded leg with four chunks of the reduce-scatter, and `--mode auto`, which at this size (a 0.1 GB table) picks the tree cut."""
     os.environ["QS_BENCH_BACKEND"] = "gloo"
-    common = ["--gpus", "4", "--taxa", "160", "--trees", "4000", "--steps", "4", "--warmup", "1", "--p2p-leg", "0", "--no-cpu-baseline", "--no-e2e"]
+    common = ["--gpus", "4", "--taxa", "160", "--trees", "4000", "--steps", "4", "--warmup", "1", "--p2p-leg", "0", "--full", "--no-cpu-baseline", "--no-e2e"]
     try:
         table = run_bench(common + ["--mode", "table"])
         auto = run_bench(common + ["--no-score"])

@@ -25,7 +25,7 @@ for step in "$@"; do
             tail -3 "$out/pytest_$i.log" ;;
         bench)
             # shellcheck disable=SC2086
-            timeout -k 10 900 python3 bench.py $arg > "$out/bench_$i.json" 2> "$out/bench_$i.err" || { tail -20 "$out/bench_$i.err"; exit 1; }
+            timeout -k 10 900 python3 bench.py --full $arg > "$out/bench_$i.json" 2> "$out/bench_$i.err" || { tail -20 "$out/bench_$i.err"; exit 1; }
             tail -c 600 "$out/bench_$i.json"; echo ;;
         prof)
             # shellcheck disable=SC2086

@@ -5,7 +5,7 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-.}"
 O=gpurun_out/r05_multi; mkdir -p $O
-QS_BENCH_FORCE_DIST=1 python3 bench.py --config 3 --via-launcher --p2p-leg 1 --no-cpu-baseline > $O/bench_cfg3_forced_dist_via_launcher.json 2> $O/err.txt || { tail -20 $O/err.txt; exit 1; }
+QS_BENCH_FORCE_DIST=1 python3 bench.py --full --config 3 --via-launcher --p2p-leg 1 --no-cpu-baseline > $O/bench_cfg3_forced_dist_via_launcher.json 2> $O/err.txt || { tail -20 $O/err.txt; exit 1; }
 python3 - "$O/bench_cfg3_forced_dist_via_launcher.json" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); c=d["config"]

@@ -11,7 +11,7 @@ ARGS="--no-cpu-baseline --no-impl-check --no-e2e --prewarm-ms 0 --steps 1 --warm
 cd /tmp
 rocprofv3 -L > "$OUT/avail.txt" 2>&1
 have() { grep -qw "$1" "$OUT/avail.txt"; }
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- python3 "$ROOT/bench.py" $ARGS > "$OUT/stats.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- python3 "$ROOT/bench.py" --full $ARGS > "$OUT/stats.log" 2>&1
 for grp in "GRBM_GUI_ACTIVE SQ_WAVES SQ_BUSY_CYCLES" \
            "SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY" \
            "SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" \
@@ -30,7 +30,7 @@ for grp in "GRBM_GUI_ACTIVE SQ_WAVES SQ_BUSY_CYCLES" \
     for c in $grp; do if have $c; then use="$use $c"; else echo "not on this box: $c" >> "$OUT/missing.txt"; fi; done
     [ -z "$use" ] && continue
     name=$(echo $use | tr ' ' '_')
-    rocprofv3 --kernel-trace --output-format csv --pmc $use -d "$OUT/pmc_$name" -o run -- python3 "$ROOT/bench.py" $ARGS > "$OUT/pmc_$name.log" 2>&1 || echo "pmc group failed: $use" >> "$OUT/errors.txt"
+    rocprofv3 --kernel-trace --output-format csv --pmc $use -d "$OUT/pmc_$name" -o run -- python3 "$ROOT/bench.py" --full $ARGS > "$OUT/pmc_$name.log" 2>&1 || echo "pmc group failed: $use" >> "$OUT/errors.txt"
     echo "done: $use"
 done
 cd "$ROOT"

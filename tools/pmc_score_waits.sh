@@ -14,7 +14,7 @@ for grp in "GRBM_GUI_ACTIVE SQ_WAVES" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_A
     use=""; for c in $grp; do have $c && use="$use $c"; done
     [ -z "$use" ] && continue
     name=$(echo $use | tr ' ' '_')
-    rocprofv3 --kernel-trace --output-format csv --pmc $use -d "$OUT/pmc_$name" -o run -- python3 "$ROOT/bench.py" $ARGS > "$OUT/pmc_$name.log" 2>&1 || echo "pmc group failed: $use" >> "$OUT/errors.txt"
+    rocprofv3 --kernel-trace --output-format csv --pmc $use -d "$OUT/pmc_$name" -o run -- python3 "$ROOT/bench.py" --full $ARGS > "$OUT/pmc_$name.log" 2>&1 || echo "pmc group failed: $use" >> "$OUT/errors.txt"
 done
 cd "$ROOT"
 python3 - "$OUT" <<'PY' > "$OUT/score_counters.txt"

@@ -4,7 +4,7 @@
 #   bash tools/r06_fused_ab.sh <outdir>
 out=${1:-gpurun_out/r06_fused}
 mkdir -p "$out"
-common="--taxa 512 --trees 1500 --steps 10 --warmup 2 --no-cpu-baseline --no-e2e --no-score"
+common="--full --taxa 512 --trees 1500 --steps 10 --warmup 2 --no-cpu-baseline --no-e2e --no-score"
 for wl in "--mixed" "--collapse 0.2" "--collapse 0.2 --dropout 0.1" "--dropout 0.1"; do
   tag=$(echo "$wl" | tr -d ' -' | tr '.' 'p')
   for fuse in 1 0; do

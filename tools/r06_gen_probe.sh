@@ -2,7 +2,7 @@
 # A/B of compile-time variants of the general / partial instances against the product library: tools/r06_gen_probe.sh <outdir> <probe lib names...>
 out=${1:?outdir}; shift
 mkdir -p "$out"
-common="--taxa 512 --trees 1500 --steps 8 --warmup 2 --no-cpu-baseline --no-e2e --no-score --secondary 0"
+common="--full --taxa 512 --trees 1500 --steps 8 --warmup 2 --no-cpu-baseline --no-e2e --no-score --secondary 0"
 for wl in "--collapse 0.2" "--collapse 0.2 --dropout 0.1" "--dropout 0.1" "--mixed"; do
   tag=$(echo "$wl" | tr -d ' -' | tr '.' 'p')
   for lib in product "$@"; do

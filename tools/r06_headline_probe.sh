@@ -4,7 +4,7 @@ out=${1:?outdir}; shift
 mkdir -p "$out"
 for rep in 1 2; do for lib in product "$@"; do
   if [ $lib = product ]; then unset QS_PY_LIB; else export QS_PY_LIB=$PWD/quartetscores_amd/lib/libqs_probe_$lib.so; fi
-  python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-e2e --no-score --secondary 0 > "$out/bench_${lib}_$rep.json" 2> "$out/bench_${lib}_$rep.err" || echo "FAILED $lib"
+  python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-e2e --no-score --secondary 0 > "$out/bench_${lib}_$rep.json" 2> "$out/bench_${lib}_$rep.err" || echo "FAILED $lib"
   python - "$out/bench_${lib}_$rep.json" "$lib" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

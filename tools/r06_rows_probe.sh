@@ -4,7 +4,7 @@
 # rows -- twice the waves, each with half the counters -- could win; see profiles/r06_experiments.md 4.
 out=${1:-gpurun_out/r06_rows}
 mkdir -p "$out"
-common="--taxa 512 --trees 1500 --steps 6 --warmup 2 --no-cpu-baseline --no-e2e --no-score --no-impl-check --secondary 0"
+common="--full --taxa 512 --trees 1500 --steps 6 --warmup 2 --no-cpu-baseline --no-e2e --no-score --no-impl-check --secondary 0"
 for wl in "--collapse 0.2" "--collapse 0.2 --dropout 0.1"; do
   tag=$(echo "$wl" | tr -d ' -' | tr '.' 'p')
   for lib in product rows4_w3 rows4_w4; do

@@ -4,7 +4,7 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-.}"
 O=gpurun_out/tile_order_sweep; mkdir -p $O
-B="--no-cpu-baseline --no-e2e --no-score --no-impl-check --steps 8 --warmup 2 $*"
+B="--full --no-cpu-baseline --no-e2e --no-score --no-impl-check --steps 8 --warmup 2 $*"
 for v in "2 32" "1 32" "4 32" "2 16" "2 64" "4 64" "3 48" "2 32"; do
   set -- $v; val=$(( $1 | ($2 << 16) ))
   QS_PY_TUNING="4=$val" python3 bench.py $B > $O/chunk$1_cblock$2.json 2> $O/err.txt || { tail -5 $O/err.txt; exit 1; }
