@@ -14,7 +14,8 @@
  *                                 (QuartetCounterLookup.hpp:65-238), on pre-flattened trees
  *   qs_lookup                     QuartetCounterLookup::countQuartetOccurrences
  *                                 (QuartetCounterLookup.hpp:299-318)
- *   qs_table_*                    QuartetLookupTable<T> storage (quartet_lookup_table.hpp:19-228)
+ *   qs_table_*                    QuartetLookupTable<T> storage (quartet_lookup_table.hpp:19-228);
+ *                                 qs_table_remap replaces nothing (the reference recounts per reference tree)
  *   qs_score                      QuartetScoreComputer: processNodePair /
  *                                 computeQuartetScoresBifurcating / ...Multifurcating
  *                                 (QuartetScoreComputer.hpp:379-593) + getLQIC/QPIC/EQPICScores (:106-125)
@@ -246,6 +247,17 @@ int qs_table_upload(qs_ctx *ctx, const void *host_src, uint64_t bytes);
  * the reference has no cross-process reduction). 16-byte aligned pointers, at most 15 sources.
  * Asynchronous on the context's stream; the caller orders it after the peers' counting (events / synchronisation). */
 int qs_sum_words(qs_ctx *ctx, void *dst_device, const void *const *src_device, uint32_t n_src, uint64_t n_words);
+
+/* The table of `src` re-indexed into the lookup-id order of another reference tree over the same taxa, into `dst`'s table:
+ * src_id_of[i] (host, n_taxa entries, validated as a permutation of [0, n_taxa)) is the id in src's order of the taxon with id i
+ * in dst's order. The count table depends on the taxon set only; its id order is the reference tree's depth-first leaf order, which
+ * qs_score relies on -- so one count serves several reference trees: count with the first, remap into a second context, qs_score
+ * that context with the second tree. Whole-table contexts (d_lo = 0, d_hi = n_taxa) on the same device with the same n_taxa
+ * (else QS_ERR_UNSUPPORTED for a table shard, QS_ERR_ARG otherwise); both need a table (allocated or attached; else QS_ERR_STATE);
+ * cells 32 -> 32, 16 -> 16 or 16 -> 32 (narrowing: QS_ERR_ARG). Waits for src's stream, then runs asynchronously on dst's stream;
+ * dst's previous contents are overwritten, its trees-counted becomes src's. The reference recounts per run: this replaces
+ * nothing there (like qs_depth_clamp_plan). */
+int qs_table_remap(qs_ctx *dst, const qs_ctx *src, const uint16_t *src_id_of);
 
 /* Writes the u32 table as a u16 table (same [rank][3] layout, 2 bytes per cell, padded to a whole 32-bit word)
  * into caller-owned device memory: the wire format for the multi-GPU all-reduce while all totals stay below 2^16

@@ -425,6 +425,9 @@ public:
     std::vector<double> getLQICScores() { return LQICScores; }
     std::vector<double> getQPICScores() { return QPICScores; }
     std::vector<double> getEQPICScores() { return EQPICScores; }
+    // the context that holds the count table and the flattened reference tree (--also-ref remaps that table)
+    qs_ctx *context() const { return quartetCounterLookup->context(); }
+    const RefFlat &reference() const { return quartetCounterLookup->reference(); }
 
     // -q dump and its binary sidecar (print_raw_qic_scores / print_raw_qic_binary above)
     bool raw_rank_order = false;

@@ -10,11 +10,14 @@
 // where those differ observably: with a ROOTED reference tree the reference's table throws (quartet_lookup_table.hpp:79-85)
 // and the run ends with that error, here as there (QS_SCORE_SAVEMEM_LOOKUPS).
 // --save-table / --load-table write / read the raw count table (resume without recounting).
+// --also-ref REF OUT (repeatable) scores further reference trees over the same taxa from the same count table: the table is
+// re-indexed into REF's lookup-id order (qs_table_remap) instead of being counted again.
 #include "QuartetScoreComputer.hpp"
 #include "multi_gpu.hpp"
 #include "table_shards.hpp"
 
 #include <cerrno>
+#include <set>
 #include <cstdlib>
 #include <unistd.h>
 #include <chrono>
@@ -43,8 +46,15 @@ bool wrapped_by_tool() {
     return false;
 }
 
+// --also-ref: a further reference tree and the file its annotated tree goes to
+struct AlsoRef {
+    std::string ref, out;
+    Tree tree;
+};
+
 struct Args {
     std::string ref, eval, out, raw, raw_bin;
+    std::vector<AlsoRef> also;
     size_t threads = 0;
     bool verbose = false, savemem = false, raw_rank_order = false, fail_fast = false, clean_exit = false;
     int table_shards = -1;   // -1 = off (the whole table on the device); 0 = as many as the device's free memory asks for; K = K shards, one after the other (table_shards.hpp)
@@ -92,7 +102,10 @@ void usage(std::ostream &os) {
           "                  second time for the second scoring pass) | auto (host if it fits MemAvailable; default)\n"
           "   --save-table F write the count table to F after counting\n"
           "   --load-table F read the count table from F instead of counting (-e is still needed for m)\n"
-          "   --qic-binary F raw per-quartet QIC as a binary file (topology byte + double per quartet, in rank order)\n";
+          "   --qic-binary F raw per-quartet QIC as a binary file (topology byte + double per quartet, in rank order)\n"
+          "   --also-ref REF OUT  (repeatable) score the reference tree REF as well and write its annotated tree to OUT: the count\n"
+          "                  table of -r is re-indexed into REF's taxon order instead of counting again. REF must hold the same\n"
+          "                  taxa as -r; one GPU with the whole table (not with --gpus / --table-shards); works with --load-table\n";
 }
 
 // returns 0 ok, 1 error (message printed like the reference prints TCLAP::ArgException), 2 exit quietly
@@ -164,6 +177,16 @@ int parse(int argc, char **argv, Args &a) {
         else if (f == "--save-table") { if (!(v = need(i, "--save-table"))) return 1; a.dev.save_table = v; }
         else if (f == "--qic-binary") { if (!(v = need(i, "--qic-binary"))) return 1; a.raw_bin = v; }
         else if (f == "--load-table") { if (!(v = need(i, "--load-table"))) return 1; a.dev.load_table = v; }
+        else if (f == "--also-ref") {
+            if (i + 2 >= argc || argv[i + 2][0] == '-') {
+                std::cerr << "ERROR: Missing a value for this argument! for arg --also-ref (it takes two: REF OUT)" << std::endl;
+                return 1;
+            }
+            AlsoRef x;
+            x.ref = argv[++i];
+            x.out = argv[++i];
+            a.also.push_back(std::move(x));
+        }
         else if (f == "--version") { std::cout << argv[0] << "  version: 1.0.1 (" << qs_version() << ")" << std::endl; return 2; }
         else if (f == "-h" || f == "--help") { usage(std::cout); return 2; }
         else { std::cerr << "ERROR: Couldn't find match for argument for arg " << f << std::endl; return 1; }
@@ -174,6 +197,99 @@ int parse(int argc, char **argv, Args &a) {
     // fast exit: with a preloaded library or a profiler's environment the ordinary return is the default (--fast-exit overrides)
     if (!a.clean_exit && !fast_exit_forced && wrapped_by_tool()) a.clean_exit = true;
     return 0;
+}
+
+// annotated Newick: per edge "qp-ic:X;lq-ic:Y;eqp-ic:Z" via std::to_string, parts omitted when +inf;
+// the qp-ic guard tests the LQ value like the reference (quartet_newick_writer.hpp:164-187, quirk Q6)
+void write_annotated(const Tree &tree, const std::string &path, const std::vector<double> &lqic, const std::vector<double> &qpic,
+                     const std::vector<double> &eqpic) {
+    const double inf = std::numeric_limits<double>::infinity();
+    auto comment = [&](size_t v) -> std::string {
+        if (v == 0) return std::string();
+        const size_t e = v - 1;
+        std::string s;
+        auto add = [&](const std::string &part) { if (!s.empty()) s += ";"; s += part; };
+        if (!qpic.empty() && lqic[e] != inf) add("qp-ic:" + std::to_string(qpic[e]));
+        if (lqic[e] != inf) add("lq-ic:" + std::to_string(lqic[e]));
+        if (!eqpic.empty() && eqpic[e] != inf) add("eqp-ic:" + std::to_string(eqpic[e]));
+        return s;
+    };
+    std::ofstream out(path);
+    if (!out) throw std::runtime_error("cannot write " + path);
+    out << write_newick(tree, comment) << "\n";
+}
+
+uint32_t score_flags(const Args &a) {
+    return (a.dev.qp_exact64 ? QS_SCORE_QP_EXACT64 : QS_SCORE_QP_WRAP32) | (a.dev.root_as_edge ? QS_SCORE_ROOT_AS_EDGE : 0u) |
+           (a.savemem ? QS_SCORE_SAVEMEM_LOOKUPS : 0u);
+}
+
+// --also-ref: everything that needs no GPU, before the device is touched -- the files parse, every tree holds exactly the
+// taxa of -r, no OUT exists or repeats -o or another OUT, and qs_score_check passes for every tree with the run's flags
+void check_also_refs(Args &a) {
+    if (a.also.empty()) return;
+    if (a.gpus > 0 || a.table_shards >= 0)
+        throw std::runtime_error("--also-ref works on one GPU with the whole table: omit --gpus / --table-shards");
+    Tree primary;
+    {
+        const std::string text = slurp(a.ref);
+        NewickReader rr(text);
+        if (!rr.next(primary)) throw std::runtime_error("empty reference tree file");
+    }
+    const RefFlat rf = flatten_reference(primary);
+    const std::set<std::string> names(rf.names.begin(), rf.names.end());
+    std::set<std::string> outs{a.out};
+    for (AlsoRef &x : a.also) {
+        if (!outs.insert(x.out).second) throw std::runtime_error("--also-ref " + x.ref + ": the output file " + x.out + " is given twice");
+        if (std::ifstream(x.out).good()) throw std::runtime_error("--also-ref " + x.ref + ": the output file " + x.out + " already exists");
+        const std::string text = slurp(x.ref);
+        NewickReader rr(text);
+        if (!rr.next(x.tree)) throw std::runtime_error("--also-ref " + x.ref + ": empty reference tree file");
+        const RefFlat fx = flatten_reference(x.tree);
+        const std::set<std::string> other(fx.names.begin(), fx.names.end());
+        std::string missing, extra;
+        for (const std::string &s : names) if (!other.count(s)) missing += (missing.empty() ? "" : ", ") + s;
+        for (const std::string &s : other) if (!names.count(s)) extra += (extra.empty() ? "" : ", ") + s;
+        if (!missing.empty() || !extra.empty())
+            throw std::runtime_error("--also-ref " + x.ref + ": the taxa differ from those of the reference tree " + a.ref + " (missing: " +
+                                     (missing.empty() ? "none" : missing) + "; extra: " + (extra.empty() ? "none" : extra) + ")");
+        qs_ref_tree rt;
+        rt.n_nodes = (uint32_t)x.tree.node_count(); rt.n_taxa = (uint32_t)fx.names.size();
+        rt.parent = fx.parent.data(); rt.leaf_node = fx.leaf_node.data();
+        if (qs_score_check(nullptr, &rt, score_flags(a)) != QS_OK) throw std::runtime_error("--also-ref " + x.ref + ": " + qs_last_error(nullptr));
+    }
+}
+
+// --also-ref, after the primary tree's output is written: its table re-indexed into `table`'s context (allocated before the
+// counting), scored and written per further reference tree
+void score_also_refs(const Args &a, qs_ctx *src, const RefFlat &primary, qs_ctx *table) {
+    for (const AlsoRef &x : a.also) {
+        const auto begin = std::chrono::steady_clock::now();
+        std::cout << "Scoring the reference tree " << x.ref << " from the same count table.\n";
+        const RefFlat fx = flatten_reference(x.tree);
+        std::vector<uint16_t> src_id_of(fx.names.size());
+        for (size_t i = 0; i < fx.names.size(); ++i) src_id_of[i] = (uint16_t)primary.name_to_id.at(fx.names[i]);
+        if (qs_table_remap(table, src, src_id_of.data()) != QS_OK || qs_sync(table) != QS_OK) throw std::runtime_error(qs_last_error(table));
+        const auto remapped = std::chrono::steady_clock::now();
+        const auto remap_us = std::chrono::duration_cast<std::chrono::microseconds>(remapped - begin).count();
+        std::cout << "Remapped the count table in " << remap_us << " microseconds.\n";
+        if (a.dev.trace) std::fprintf(stderr, "[trace] qs_table_remap for %s: %.2f ms\n", x.ref.c_str(), remap_us / 1000.0);
+        qs_ref_tree rt;
+        rt.n_nodes = (uint32_t)x.tree.node_count(); rt.n_taxa = (uint32_t)fx.names.size();
+        rt.parent = fx.parent.data(); rt.leaf_node = fx.leaf_node.data();
+        std::vector<double> lq(rt.n_nodes), qp(rt.n_nodes), eqp(rt.n_nodes);
+        int bif = 0;
+        if (qs_score(table, &rt, score_flags(a), lq.data(), qp.data(), eqp.data(), &bif) != QS_OK) throw std::runtime_error(qs_last_error(table));
+        std::cout << (bif ? "The reference tree is bifurcating.\n" : "The reference tree is multifurcating.\n");
+        // edge e = edge above node e+1 (preorder), as QuartetScoreComputer hands them out
+        const std::vector<double> lqic(lq.begin() + 1, lq.end()), none;
+        const std::vector<double> qpic = bif ? std::vector<double>(qp.begin() + 1, qp.end()) : none;
+        const std::vector<double> eqpic = bif ? std::vector<double>(eqp.begin() + 1, eqp.end()) : none;
+        write_annotated(x.tree, x.out, lqic, qpic, eqpic);
+        std::cout << "Finished computing scores.\n";
+        std::cout << "It took: " << std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - begin).count()
+                  << " microseconds." << std::endl;
+    }
 }
 
 // --gpus N: trees split over N GPUs, one collective on the table, sharded scoring (multi_gpu.hpp)
@@ -233,6 +349,17 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
         }
     }
     if (a.gpus > 0) return run_multi(referenceTree, a, m, bits, lqic, qpic, eqpic);
+    // --also-ref: the second table is allocated before anything is counted, so that a table that fits once but not twice is
+    // reported now and not after the counting
+    qs_ctx *also_table = nullptr;
+    struct AlsoTable { qs_ctx *&c; bool keep; ~AlsoTable() { if (!keep) qs_destroy(c); } } also_guard{also_table, !a.clean_exit};
+    if (!a.also.empty()) {
+        if (ShardedTableQuartetScoreComputer::shards_needed(bytes, a.dev.device) > 1)
+            throw std::runtime_error("--also-ref needs the whole count table (" + std::to_string(bytes) + " bytes) on one GPU");
+        if (qs_create(&also_table, (uint32_t)n, bits, QS_FLAG_NONE, a.dev.device, nullptr, 0, 0) != QS_OK) throw std::runtime_error(qs_last_error(nullptr));
+        if (qs_table_alloc(also_table) != QS_OK) throw std::runtime_error(std::string("--also-ref: ") + qs_last_error(also_table));
+        trace_mark(a.dev, "main: --also-ref table allocated");
+    }
     // (without --clean-exit the computer is never destroyed: freeing a 17-34 GB table and the context is work the exiting process
     // leaves to the driver -- main ends with std::_Exit once the output is written)
     std::unique_ptr<QuartetScoreComputer<CINT>> holder(new QuartetScoreComputer<CINT>(referenceTree, a.eval, m, a.verbose, a.savemem, a.dev));
@@ -244,6 +371,10 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
     qsc.raw_rank_order = a.raw_rank_order;
     if (!a.raw.empty()) qsc.printRawQICScores(referenceTree, a.raw);
     if (!a.raw_bin.empty()) qsc.printRawQICBinary(referenceTree, a.raw_bin);
+    if (!a.also.empty()) {   // the primary tree's output first, exactly as without --also-ref
+        write_annotated(referenceTree, a.out, lqic, qpic, eqpic);
+        score_also_refs(a, qsc.context(), qsc.reference(), also_table);
+    }
     if (!a.clean_exit) (void)holder.release();
 }
 
@@ -259,6 +390,12 @@ int main(int argc, char *argv[]) {
     std::ifstream infile(a.out);
     if (infile.good()) {
         std::cout << "ERROR: The specified output file already exists.\n";
+        return 1;
+    }
+    try {
+        check_also_refs(a);
+    } catch (const std::exception &e) {
+        std::cerr << "ERROR: " << e.what() << std::endl;
         return 1;
     }
     a.dev.ingest_threads = (unsigned)a.threads;
@@ -308,22 +445,7 @@ int main(int argc, char *argv[]) {
         else if (m < (size_t(1) << 32)) run<uint32_t>(referenceTree, a, m, lqic, qpic, eqpic);
         else throw std::runtime_error("more than 2^32 evaluation trees are not supported");
 
-        // annotated Newick: per edge "qp-ic:X;lq-ic:Y;eqp-ic:Z" via std::to_string, parts omitted when +inf;
-        // the qp-ic guard tests the LQ value like the reference (quartet_newick_writer.hpp:164-187, quirk Q6)
-        const double inf = std::numeric_limits<double>::infinity();
-        auto comment = [&](size_t v) -> std::string {
-            if (v == 0) return std::string();
-            const size_t e = v - 1;
-            std::string s;
-            auto add = [&](const std::string &part) { if (!s.empty()) s += ";"; s += part; };
-            if (!qpic.empty() && lqic[e] != inf) add("qp-ic:" + std::to_string(qpic[e]));
-            if (lqic[e] != inf) add("lq-ic:" + std::to_string(lqic[e]));
-            if (!eqpic.empty() && eqpic[e] != inf) add("eqp-ic:" + std::to_string(eqpic[e]));
-            return s;
-        };
-        std::ofstream out(a.out);
-        if (!out) throw std::runtime_error("cannot write " + a.out);
-        out << write_newick(referenceTree, comment) << "\n";
+        if (a.also.empty()) write_annotated(referenceTree, a.out, lqic, qpic, eqpic);   // (with --also-ref: written by run())
     } catch (const std::exception &e) {
         std::cerr << "ERROR: " << e.what() << std::endl;
         if (a.savemem && std::string(e.what()).rfind("id = ", 0) == 0)

@@ -143,6 +143,7 @@ struct qs_ctx {
     uint32_t tune_score_dedupe = 1;              // QS_TUNE_SCORE_DEDUPE: the logging pass skips a quartet that repeats its node pair's last logged triple
     uint32_t tune_score_sample = 64u | 65536u;             // QS_TUNE_SCORE_SAMPLE: pre-pass of the single-read scoring (0 = none; S | by-round bit 16)
     uint64_t tune_score_log_cap = 0;             // QS_TUNE_SCORE_LOG_CAP: records the log may hold (0 = 8 M); tests force overflows
+    uint16_t *remap_ids = nullptr;               // qs_table_remap: src_id_of on the device (n entries)
 };
 
 static thread_local std::string g_create_err;   // per thread: qs_create of several contexts may run concurrently (multi_gpu.hpp)
@@ -551,6 +552,7 @@ extern "C" void qs_destroy(qs_ctx *c) {
     if (c->score_log) (void)hipFree(c->score_log);
     if (c->score_acc) (void)hipFree(c->score_acc);
     if (c->score_acc_host) (void)hipHostFree(c->score_acc_host);
+    if (c->remap_ids) (void)hipFree(c->remap_ids);
     delete c->ref_cache;
     delete c;
 }
@@ -770,6 +772,41 @@ extern "C" int qs_sum_words(qs_ctx *c, void *dst_device, const void *const *src_
     if (c->n_cu == 0) { int v = 0; QS_HIP(c, hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device)); c->n_cu = std::max(1, v); }
     QS_HIP(c, launch_sum_words(c->stream, dst_device, src_device, n_src, n_words, c->n_cu));
     return QS_OK;   // asynchronous on the context's stream
+}
+
+// The table of `src` in the lookup-id order of another reference tree over the same taxa (qs_remap.hip), so that one count
+// serves several reference trees. The reference recounts per run: this replaces nothing there.
+extern "C" int qs_table_remap(qs_ctx *dst, const qs_ctx *src, const uint16_t *src_id_of) {
+    if (dst) dst->log_valid = false;   // (the table changes: a logged pass 1 no longer describes it)
+    if (!dst) return QS_ERR_ARG;
+    if (!src || !src_id_of) return fail(dst, QS_ERR_ARG, "qs_table_remap: NULL argument");
+    if (dst == src) return fail(dst, QS_ERR_ARG, "qs_table_remap: source and destination are the same context");
+    if (dst->d_lo != 0 || dst->d_hi != dst->n || src->d_lo != 0 || src->d_hi != src->n)
+        return fail(dst, QS_ERR_UNSUPPORTED, "qs_table_remap: whole-table contexts only (no table shards)");
+    if (dst->n != src->n) return fail(dst, QS_ERR_ARG, "qs_table_remap: the contexts have different numbers of taxa");
+    if (dst->device != src->device) return fail(dst, QS_ERR_ARG, "qs_table_remap: the contexts are on different devices");
+    if (!dst->table || !src->table) return fail(dst, QS_ERR_STATE, std::string("qs_table_remap: the ") + (src->table ? "destination" : "source") + " has no table");
+    if (dst->table == src->table) return fail(dst, QS_ERR_ARG, "qs_table_remap: source and destination share their table");
+    if (dst->count_bits < src->count_bits) return fail(dst, QS_ERR_ARG, "qs_table_remap: 32-bit cells cannot be narrowed to 16 bits");
+    std::vector<uint8_t> seen(dst->n, 0);
+    for (uint32_t i = 0; i < dst->n; ++i) {
+        if (src_id_of[i] >= dst->n || seen[src_id_of[i]]) return fail(dst, QS_ERR_ARG, "qs_table_remap: src_id_of is not a permutation of [0, n_taxa)");
+        seen[src_id_of[i]] = 1;
+    }
+    QS_HIP(dst, hipSetDevice(dst->device));
+    if (!dst->remap_ids) QS_HIP(dst, hipMalloc(&dst->remap_ids, 4096 * sizeof(uint16_t)));
+    if (src->stream != dst->stream) {   // the source's counting (or upload) first
+        hipEvent_t ev = nullptr;
+        QS_HIP(dst, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        hipError_t e = hipEventRecord(ev, src->stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(dst->stream, ev, 0);
+        (void)hipEventDestroy(ev);
+        QS_HIP(dst, e);
+    }
+    QS_HIP(dst, hipMemcpyAsync(dst->remap_ids, src_id_of, dst->n * sizeof(uint16_t), hipMemcpyHostToDevice, dst->stream));
+    QS_HIP(dst, launch_table_remap(dst->stream, src->table, (int)src->count_bits, dst->table, (int)dst->count_bits, dst->remap_ids, dst->n, dst->n_tuples));
+    dst->trees_counted = src->trees_counted;   // sizes the log table and the 16-bit overflow guard of later counts
+    return QS_OK;   // asynchronous on dst's stream
 }
 
 // ---- issue probe: how fast does THIS device run the count kernel's instruction mix? ------------------------------------

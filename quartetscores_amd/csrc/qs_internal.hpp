@@ -5,7 +5,28 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "qs_common.hpp"
+
 namespace qs {
+
+// Ranks are walked in blocks of consecutive values: the block's first rank is un-ranked once (f64 sqrt / cbrt,
+// ~300 instructions), every other rank of the block from it: rank = C(d,4) + C(c,3) + (C(b,2) + a), so adding `off`
+// to the pair rank and carrying into c (and d) is enough; unrank2 is a float sqrt and two corrections.
+struct Ids4 { uint32_t a, b, c, d; };
+__device__ __forceinline__ Ids4 decode_near(const Ids4 &base, uint32_t off) {
+    Ids4 r;
+    uint32_t c = base.c, d = base.d;
+    uint64_t pr = binom2(base.b) + base.a + off;
+    for (;;) {
+        const uint64_t lim = binom2(c);
+        if (pr < lim) break;
+        pr -= lim;
+        if (++c == d) { ++d; c = 2; }
+    }
+    unrank2((uint32_t)pr, r.a, r.b);
+    r.c = c; r.d = d;
+    return r;
+}
 
 // Panel element type / kernel mode of one batch
 enum PanelBits { PANEL_U8 = 8, PANEL_U16 = 16 };
@@ -113,6 +134,9 @@ hipError_t launch_unpack32x2(hipStream_t s, const void *src, void *dst_u32, uint
 hipError_t launch_sum_words(hipStream_t s, void *dst, const void *const *src, uint32_t n_src, uint64_t n_words, int n_cu); // dst += sum of (peer) sources
 hipError_t launch_lookup(hipStream_t s, uint32_t n, uint32_t d_lo, uint32_t d_hi, uint64_t rank_lo, const void *table,
                          int count_bits, uint64_t nq, const uint16_t *abcd_dev, uint64_t *out_dev);
+// qs_remap.hip: dst (ids B) <- src (ids A); src_id_of_dev[i] = A-id of B-id i (a permutation of [0, n)); cell widths 32/32, 16/16 or 16 -> 32
+hipError_t launch_table_remap(hipStream_t s, const void *src, int src_bits, void *dst, int dst_bits, const uint16_t *src_id_of_dev,
+                              uint32_t n, uint64_t n_tuples);
 size_t gather_lds_bytes(uint32_t d_hi);
 uint32_t gather_tiles_for_c(uint32_t c); // workgroups of the gather kernel per (d-block, c)
 

@@ -31,24 +31,7 @@
 
 namespace qs {
 
-// Ranks are walked in blocks of consecutive values: the block's first rank is un-ranked once (f64 sqrt / cbrt,
-// ~300 instructions), every other rank of the block from it: rank = C(d,4) + C(c,3) + (C(b,2) + a), so adding `off`
-// to the pair rank and carrying into c (and d) is enough; unrank2 is a float sqrt and two corrections.
-struct Ids4 { uint32_t a, b, c, d; };
-__device__ __forceinline__ Ids4 decode_near(const Ids4 &base, uint32_t off) {
-    Ids4 r;
-    uint32_t c = base.c, d = base.d;
-    uint64_t pr = binom2(base.b) + base.a + off;
-    for (;;) {
-        const uint64_t lim = binom2(c);
-        if (pr < lim) break;
-        pr -= lim;
-        if (++c == d) { ++d; c = 2; }
-    }
-    unrank2((uint32_t)pr, r.a, r.b);
-    r.c = c; r.d = d;
-    return r;
-}
+// Ids4 / decode_near (qs_internal.hpp): a block's first rank is un-ranked once, the others are stepped to from it.
 
 struct QuartetRef {
     bool resolved;

@@ -142,6 +142,14 @@ class Context:
             raise ValueError("unpack16x2: buffer too small")
         self._chk(self.L.qs_unpack16x2(self.h, C.c_void_p(src.data_ptr()), n_tuples, total_trees, C.c_void_p(dst.data_ptr())))
 
+    def table_remap(self, src: "Context", src_id_of):
+        """qs_table_remap: this context's table := `src`'s table in another lookup-id order. src_id_of[i] = id in src's order
+        of the taxon whose id here is i (flatten.taxon_permutation(ref_here, ref_src)). Asynchronous on this context's stream."""
+        perm = np.ascontiguousarray(src_id_of, dtype=np.uint16)
+        if perm.shape != (self.n,):
+            raise ValueError(f"table_remap: src_id_of needs {self.n} entries, got {perm.shape}")
+        self._chk(self.L.qs_table_remap(self.h, src.h, perm.ctypes.data_as(C.c_void_p)))
+
     def table_clear(self):
         self._chk(self.L.qs_table_clear(self.h))
 

@@ -58,6 +58,18 @@ def flatten_reference(text_or_node) -> RefTree:
     return RefTree(root, nodes, parent, leaf_node, names, {nm: i for i, nm in enumerate(names)})
 
 
+def taxon_permutation(ref_dst: RefTree, ref_src: RefTree) -> np.ndarray:
+    """uint16[n]: entry i = lookup id under ref_src of the taxon whose lookup id under ref_dst is i -- the src_id_of of
+    qs_table_remap, which turns a table counted with ref_src into the table ref_dst would have counted. Raises ValueError
+    naming the missing and the extra taxa when the two trees do not hold the same taxa."""
+    missing = sorted(set(ref_src.names) - set(ref_dst.names))
+    extra = sorted(set(ref_dst.names) - set(ref_src.names))
+    if missing or extra:
+        raise ValueError("the reference trees hold different taxa: missing " + (", ".join(missing) or "none") +
+                         "; extra " + (", ".join(extra) or "none"))
+    return np.array([ref_src.name_to_id[nm] for nm in ref_dst.names], dtype=np.uint16)
+
+
 @dataclass
 class TreeBatch:
     n_trees: int
