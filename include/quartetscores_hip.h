@@ -16,6 +16,7 @@
  *                                 (QuartetCounterLookup.hpp:299-318)
  *   qs_table_*                    QuartetLookupTable<T> storage (quartet_lookup_table.hpp:19-228);
  *                                 qs_table_remap replaces nothing (the reference recounts per reference tree)
+ *   qs_tree_agreement             replaces nothing in the reference (it reports no per-tree agreement)
  *   qs_score                      QuartetScoreComputer: processNodePair /
  *                                 computeQuartetScoresBifurcating / ...Multifurcating
  *                                 (QuartetScoreComputer.hpp:379-593) + getLQIC/QPIC/EQPICScores (:106-125)
@@ -314,6 +315,21 @@ uint64_t qs_trees_counted(const qs_ctx *ctx);
 /* countQuartetOccurrences for nq quartets: abcd[4*i..] are lookup ids (any order, distinct),
  * out3[3*i..] = (#ab|cd, #ac|bd, #ad|bc). Quartets outside this context's shard give 0,0,0. */
 int qs_lookup(qs_ctx *ctx, uint64_t nq, const uint16_t *abcd, uint64_t *out3);
+
+/* Per-tree quartet agreement with the reference tree, for every tree of an uploaded batch: tree t with taxon set P_t is compared
+ * with the reference restricted to P_t over the C(|P_t|,4) quartets of P_t, and dst_device[4*t .. 4*t+3] (caller-owned device
+ * memory, 8-byte aligned, 4 * n_trees words) receives the exact counts
+ *   concordant (resolved in both trees, same topology), discordant (resolved in both, different topologies),
+ *   resolved_eval (resolved in t), resolved_ref (resolved in the reference restricted to P_t).
+ * eval_only = resolved_eval - concordant - discordant, ref_only = resolved_ref - concordant - discordant, unresolved = the rest.
+ * Trees with fewer than 4 taxa give zeros; multifurcating and rooted trees on both sides (quartet topologies do not depend on the
+ * root, so QS_SCORE_ROOT_AS_EDGE and quirk Q5 play no part). O(#inner nodes of t x #inner nodes of the reference) per tree, no
+ * quartet is enumerated. Needs no count table and changes neither the table nor trees-counted. The reference's
+ * link intervals are derived with the checks qs_score makes and uploaded once per context and reference tree.
+ * Errors: QS_ERR_STATE = the batch was uploaded without node_off / rng_off / ranges; QS_ERR_ARG = the reference's n_taxa differs
+ * from the context's or its ids are not in depth-first order; QS_ERR_UNSUPPORTED = a table-shard context (use a whole-table one).
+ * Asynchronous on the context's stream, ordered behind the batch's upload. */
+int qs_tree_agreement(qs_ctx *ctx, const qs_ref_tree *ref, const qs_device_batch *b, uint64_t *dst_device);
 
 /* ---- scoring (QuartetScoreComputer) ----------------------------------------------------- */
 

@@ -21,6 +21,7 @@
 #include <limits>
 #include <memory>
 #include <sstream>
+#include <functional>
 #include <future>
 #include <thread>
 #include <stdexcept>
@@ -76,6 +77,10 @@ struct DeviceOptions {
     bool comm_overlap = false;   // --gpus N, rccl: count while ncclCommInitAll runs (false: the first launch waits for the communicators)
     std::string load_table, save_table; // count-table persistence
     bool trace = false;          // --trace: time stamps of the counting pipeline on stderr
+    std::string per_tree;        // --per-tree FILE: batches carry their node ranges (qs_tree_agreement reads them)
+    // called behind every batch's qs_count_batch (first tree of the batch, the flattened batch) and behind the final qs_sync
+    std::function<void(qs_ctx *, const qs_device_batch *, size_t, const BatchFlat &)> after_count;
+    std::function<void(qs_ctx *)> after_sync;
 };
 
 // --trace: "[trace] +12.3 ms  what" relative to the first call (process start for practical purposes)
@@ -167,7 +172,9 @@ private:
     static unsigned threads_of(const DeviceOptions &opt) {
         return opt.ingest_threads ? opt.ingest_threads : std::max(1u, std::thread::hardware_concurrency());
     }
-    static bool wants_ranges(const DeviceOptions &opt) { return (opt.algo & 0xFFu) == QS_ALGO_SCATTER; } // the gather kernels do not read them
+    static bool wants_ranges(const DeviceOptions &opt) { // the gather kernels do not read them; the per-tree agreement does
+        return (opt.algo & 0xFFu) == QS_ALGO_SCATTER || !opt.per_tree.empty();
+    }
     // batch boundaries: [0, first_batch_trees), then steps of batch_trees
     static size_t batch_end(size_t i0, size_t n, const DeviceOptions &opt) {
         const size_t first = std::max<size_t>(1, std::min(opt.first_batch_trees ? opt.first_batch_trees : opt.batch_trees, opt.batch_trees));
@@ -217,6 +224,7 @@ private:
                 if (qs_batch_upload(ctx_, &hb, &db) != QS_OK) fail();
                 in_flight.push_back(db);
                 if (qs_count_batch(ctx_, db, opt.algo) != QS_OK) fail(); // asynchronous
+                if (opt.after_count) opt.after_count(ctx_, db, i0, b);
                 trace_mark(opt, "host: batch uploaded, count enqueued");
                 while ((float)i1 > progress * onePercent && progress <= 100) { // QCL:230-233
                     std::cout << "Counting quartets... " << progress << "%" << std::endl;
@@ -232,6 +240,7 @@ private:
                 trace_mark(opt, "host: scoring set-up done behind the enqueued counts");
             }
             if (qs_sync(ctx_) != QS_OK) fail();
+            if (opt.after_sync) opt.after_sync(ctx_);
             trace_mark(opt, "host: all counts done (device synchronised)");
         } catch (...) {
             if (ahead.valid()) { try { (void)ahead.get(); } catch (...) {} }   // (the worker still reads the evaluation file)

@@ -54,6 +54,7 @@ struct AlsoRef {
 
 struct Args {
     std::string ref, eval, out, raw, raw_bin;
+    std::string per_tree;   // --per-tree FILE: quartet agreement of every evaluation tree with -r (TSV)
     std::vector<AlsoRef> also;
     size_t threads = 0;
     bool verbose = false, savemem = false, raw_rank_order = false, fail_fast = false, clean_exit = false;
@@ -105,7 +106,11 @@ void usage(std::ostream &os) {
           "   --qic-binary F raw per-quartet QIC as a binary file (topology byte + double per quartet, in rank order)\n"
           "   --also-ref REF OUT  (repeatable) score the reference tree REF as well and write its annotated tree to OUT: the count\n"
           "                  table of -r is re-indexed into REF's taxon order instead of counting again. REF must hold the same\n"
-          "                  taxa as -r; one GPU with the whole table (not with --gpus / --table-shards); works with --load-table\n";
+          "                  taxa as -r; one GPU with the whole table (not with --gpus / --table-shards); works with --load-table\n"
+          "   --per-tree F   write the quartet agreement of every evaluation tree with the -r tree to F (TSV, one line per tree in\n"
+          "                  -e order after a header: tree taxa quartets concordant discordant eval_only ref_only unresolved\n"
+          "                  concordance); computed on the device behind the counting; one GPU that counts (not with --gpus /\n"
+          "                  --table-shards / --load-table)\n";
 }
 
 // returns 0 ok, 1 error (message printed like the reference prints TCLAP::ArgException), 2 exit quietly
@@ -176,6 +181,7 @@ int parse(int argc, char **argv, Args &a) {
         else if (f == "--qic-rank-order") a.raw_rank_order = true;
         else if (f == "--save-table") { if (!(v = need(i, "--save-table"))) return 1; a.dev.save_table = v; }
         else if (f == "--qic-binary") { if (!(v = need(i, "--qic-binary"))) return 1; a.raw_bin = v; }
+        else if (f == "--per-tree") { if (!(v = need(i, "--per-tree"))) return 1; a.per_tree = v; }
         else if (f == "--load-table") { if (!(v = need(i, "--load-table"))) return 1; a.dev.load_table = v; }
         else if (f == "--also-ref") {
             if (i + 2 >= argc || argv[i + 2][0] == '-') {
@@ -259,6 +265,62 @@ void check_also_refs(Args &a) {
         if (qs_score_check(nullptr, &rt, score_flags(a)) != QS_OK) throw std::runtime_error("--also-ref " + x.ref + ": " + qs_last_error(nullptr));
     }
 }
+
+// --per-tree: refused before the device is touched where no trees are counted on one GPU, and where FILE exists or is another output
+void check_per_tree(const Args &a) {
+    if (a.per_tree.empty()) return;
+    if (a.gpus > 0 || a.table_shards >= 0 || !a.dev.load_table.empty())
+        throw std::runtime_error("--per-tree needs the evaluation trees counted on one GPU: omit --gpus / --table-shards / --load-table");
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table};
+    for (const AlsoRef &x : a.also) others.insert(x.out);
+    if (others.count(a.per_tree)) throw std::runtime_error("--per-tree: " + a.per_tree + " is also another output file");
+    if (std::ifstream(a.per_tree).good()) throw std::runtime_error("--per-tree: the output file " + a.per_tree + " already exists");
+}
+
+// --per-tree: qs_tree_agreement behind every batch's count into one device buffer of 4 x m words, downloaded once after the last
+// qs_sync; taxa per tree from the flattened batches
+struct PerTree {
+    size_t m = 0;
+    int device = 0;
+    uint64_t *dev = nullptr;
+    std::vector<uint64_t> counts;
+    std::vector<uint32_t> taxa;
+    ~PerTree() { if (dev) (void)hipFree(dev); }
+    void hook(DeviceOptions &opt, const RefFlat &ref) {
+        taxa.assign(m, 0);
+        opt.after_count = [this, &ref](qs_ctx *ctx, const qs_device_batch *db, size_t i0, const BatchFlat &b) {
+            if (!dev) {
+                if (hipSetDevice(device) != hipSuccess || hipMalloc((void **)&dev, std::max<size_t>(1, 4 * m) * 8) != hipSuccess)
+                    throw std::runtime_error("--per-tree: Insufficient memory!");
+            }
+            for (uint32_t t = 0; t < b.n_trees; ++t) taxa[i0 + t] = b.leaf_off[t + 1] - b.leaf_off[t];
+            qs_ref_tree rt;
+            rt.n_nodes = (uint32_t)ref.parent.size(); rt.n_taxa = (uint32_t)ref.names.size();
+            rt.parent = ref.parent.data(); rt.leaf_node = ref.leaf_node.data();
+            if (qs_tree_agreement(ctx, &rt, db, dev + 4 * i0) != QS_OK) throw std::runtime_error(qs_last_error(ctx));
+        };
+        opt.after_sync = [this](qs_ctx *) {
+            counts.assign(4 * m, 0);
+            if (m && hipMemcpy(counts.data(), dev, 4 * m * 8, hipMemcpyDeviceToHost) != hipSuccess)
+                throw std::runtime_error("--per-tree: download failed");
+        };
+    }
+    void write(const std::string &path) const {
+        std::ofstream f(path);
+        if (!f) throw std::runtime_error("cannot write " + path);
+        f << "tree\ttaxa\tquartets\tconcordant\tdiscordant\teval_only\tref_only\tunresolved\tconcordance\n";
+        char conc[64];
+        for (size_t t = 0; t < m; ++t) {
+            const uint64_t n = taxa[t], c = counts[4 * t], d = counts[4 * t + 1], re = counts[4 * t + 2], rr = counts[4 * t + 3];
+            const uint64_t q = n < 4 ? 0 : n * (n - 1) * (n - 2) * (n - 3) / 24;
+            const uint64_t eo = re - c - d, ro = rr - c - d;
+            if (c + d) std::snprintf(conc, sizeof conc, "%.6f", (double)c / (double)(c + d));
+            else std::snprintf(conc, sizeof conc, "nan");
+            f << t << '\t' << n << '\t' << q << '\t' << c << '\t' << d << '\t' << eo << '\t' << ro << '\t' << (q - c - d - eo - ro) << '\t' << conc << '\n';
+        }
+        if (!f) throw std::runtime_error("cannot write " + path);
+    }
+};
 
 // --also-ref, after the primary tree's output is written: its table re-indexed into `table`'s context (allocated before the
 // counting), scored and written per further reference tree
@@ -362,7 +424,16 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
     }
     // (without --clean-exit the computer is never destroyed: freeing a 17-34 GB table and the context is work the exiting process
     // leaves to the driver -- main ends with std::_Exit once the output is written)
-    std::unique_ptr<QuartetScoreComputer<CINT>> holder(new QuartetScoreComputer<CINT>(referenceTree, a.eval, m, a.verbose, a.savemem, a.dev));
+    PerTree per_tree;
+    DeviceOptions dev = a.dev;
+    const RefFlat per_tree_ref = a.per_tree.empty() ? RefFlat() : flatten_reference(referenceTree);
+    if (!a.per_tree.empty()) {
+        per_tree.m = m;
+        per_tree.device = a.dev.device;
+        dev.per_tree = a.per_tree;
+        per_tree.hook(dev, per_tree_ref);
+    }
+    std::unique_ptr<QuartetScoreComputer<CINT>> holder(new QuartetScoreComputer<CINT>(referenceTree, a.eval, m, a.verbose, a.savemem, dev));
     QuartetScoreComputer<CINT> &qsc = *holder;
     lqic = qsc.getLQICScores();
     qpic = qsc.getQPICScores();
@@ -371,6 +442,7 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
     qsc.raw_rank_order = a.raw_rank_order;
     if (!a.raw.empty()) qsc.printRawQICScores(referenceTree, a.raw);
     if (!a.raw_bin.empty()) qsc.printRawQICBinary(referenceTree, a.raw_bin);
+    if (!a.per_tree.empty()) per_tree.write(a.per_tree);
     if (!a.also.empty()) {   // the primary tree's output first, exactly as without --also-ref
         write_annotated(referenceTree, a.out, lqic, qpic, eqpic);
         score_also_refs(a, qsc.context(), qsc.reference(), also_table);
@@ -394,6 +466,7 @@ int main(int argc, char *argv[]) {
     }
     try {
         check_also_refs(a);
+        check_per_tree(a);
     } catch (const std::exception &e) {
         std::cerr << "ERROR: " << e.what() << std::endl;
         return 1;

@@ -45,6 +45,8 @@ struct RefHost {
     uint64_t root_items = 0;
 };
 
+static int build_ref_shape(qs_ctx *c, const qs_ref_tree *ref, RefHost &R);
+
 struct qs_ctx {
     uint32_t n = 0, count_bits = 32, flags = 0;
     int device = 0;
@@ -144,6 +146,13 @@ struct qs_ctx {
     uint32_t tune_score_sample = 64u | 65536u;             // QS_TUNE_SCORE_SAMPLE: pre-pass of the single-read scoring (0 = none; S | by-round bit 16)
     uint64_t tune_score_log_cap = 0;             // QS_TUNE_SCORE_LOG_CAP: records the log may hold (0 = 8 M); tests force overflows
     uint16_t *remap_ids = nullptr;               // qs_table_remap: src_id_of on the device (n entries)
+    // qs_tree_agreement: the reference tree's inner nodes (>= 3 links) as id boundaries on the device, and the tree they came from
+    std::vector<int32_t> agree_parent;
+    std::vector<uint32_t> agree_leaf_node;
+    uint32_t *agree_off = nullptr;
+    uint16_t *agree_bnd = nullptr;
+    uint8_t *agree_par = nullptr;
+    uint32_t agree_n_u = 0;
 };
 
 static thread_local std::string g_create_err;   // per thread: qs_create of several contexts may run concurrently (multi_gpu.hpp)
@@ -553,6 +562,9 @@ extern "C" void qs_destroy(qs_ctx *c) {
     if (c->score_acc) (void)hipFree(c->score_acc);
     if (c->score_acc_host) (void)hipHostFree(c->score_acc_host);
     if (c->remap_ids) (void)hipFree(c->remap_ids);
+    if (c->agree_off) (void)hipFree(c->agree_off);
+    if (c->agree_bnd) (void)hipFree(c->agree_bnd);
+    if (c->agree_par) (void)hipFree(c->agree_par);
     delete c->ref_cache;
     delete c;
 }
@@ -807,6 +819,69 @@ extern "C" int qs_table_remap(qs_ctx *dst, const qs_ctx *src, const uint16_t *sr
     QS_HIP(dst, launch_table_remap(dst->stream, src->table, (int)src->count_bits, dst->table, (int)dst->count_bits, dst->remap_ids, dst->n, dst->n_tuples));
     dst->trees_counted = src->trees_counted;   // sizes the log table and the 16-bit overflow guard of later counts
     return QS_OK;   // asynchronous on dst's stream
+}
+
+// Per-tree quartet agreement of a batch with the reference tree (qs_agree.hip). The reference's links come from its depth-first id
+// order: the children of an inner node split its id interval, ordered by their first id, and its parent link holds the other ids.
+// The reference has no per-tree output: this replaces nothing there.
+static int agree_ref_upload(qs_ctx *c, const qs_ref_tree *ref) {
+    if (!ref || !ref->parent || !ref->leaf_node) return fail(c, QS_ERR_ARG, "qs_tree_agreement: NULL reference arrays");
+    if (ref->n_taxa != c->n) return fail(c, QS_ERR_ARG, "qs_tree_agreement: the reference tree's n_taxa differs from the context");
+    const uint32_t N = ref->n_nodes, n = ref->n_taxa;
+    if (c->agree_off && c->agree_parent.size() == N && c->agree_leaf_node.size() == n &&
+        memcmp(c->agree_parent.data(), ref->parent, (size_t)N * 4) == 0 && memcmp(c->agree_leaf_node.data(), ref->leaf_node, (size_t)n * 4) == 0)
+        return QS_OK;
+    RefHost R;
+    if (int rc = build_ref_shape(c, ref, R)) return rc;
+    // children of every node in id order
+    std::vector<std::vector<uint32_t>> kids(N);
+    for (uint32_t v = 0; v < N; ++v)
+        if (R.parent[v] >= 0 && R.leaf_cnt[v]) kids[R.parent[v]].push_back(v);
+    std::vector<uint32_t> off{0};
+    std::vector<uint16_t> bnd;
+    std::vector<uint8_t> par;
+    for (uint32_t u = 0; u < N; ++u) {
+        std::vector<uint32_t> &ks = kids[u];
+        const uint32_t has_parent = R.parent[u] >= 0 ? 1u : 0u;
+        if (ks.size() + has_parent < 3) continue;
+        std::sort(ks.begin(), ks.end(), [&](uint32_t x, uint32_t y) { return R.leaf_lo[x] < R.leaf_lo[y]; });
+        for (uint32_t v : ks) bnd.push_back((uint16_t)R.leaf_lo[v]);
+        bnd.push_back((uint16_t)(R.leaf_lo[ks.back()] + R.leaf_cnt[ks.back()]));
+        off.push_back((uint32_t)bnd.size());
+        par.push_back((uint8_t)has_parent);
+    }
+    QS_HIP(c, hipSetDevice(c->device));
+    QS_HIP(c, hipStreamSynchronize(c->stream));   // kernels of this context may still read the previous tree's arrays
+    if (c->agree_off) { (void)hipFree(c->agree_off); c->agree_off = nullptr; }
+    if (c->agree_bnd) { (void)hipFree(c->agree_bnd); c->agree_bnd = nullptr; }
+    if (c->agree_par) { (void)hipFree(c->agree_par); c->agree_par = nullptr; }
+    c->agree_parent.clear(); c->agree_leaf_node.clear();
+    QS_HIP(c, hipMalloc(&c->agree_off, off.size() * 4));
+    QS_HIP(c, hipMalloc(&c->agree_bnd, std::max<size_t>(bnd.size(), 1) * 2));
+    QS_HIP(c, hipMalloc(&c->agree_par, std::max<size_t>(par.size(), 1)));
+    QS_HIP(c, hipMemcpy(c->agree_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    if (!bnd.empty()) QS_HIP(c, hipMemcpy(c->agree_bnd, bnd.data(), bnd.size() * 2, hipMemcpyHostToDevice));
+    if (!par.empty()) QS_HIP(c, hipMemcpy(c->agree_par, par.data(), par.size(), hipMemcpyHostToDevice));
+    c->agree_n_u = (uint32_t)par.size();
+    c->agree_parent.assign(ref->parent, ref->parent + N);
+    c->agree_leaf_node.assign(ref->leaf_node, ref->leaf_node + n);
+    return QS_OK;
+}
+
+extern "C" int qs_tree_agreement(qs_ctx *c, const qs_ref_tree *ref, const qs_device_batch *b, uint64_t *dst_device) {
+    if (!c) return QS_ERR_ARG;
+    if (!b || !dst_device) return fail(c, QS_ERR_ARG, "qs_tree_agreement: NULL argument");
+    if (c->d_lo != 0 || c->d_hi != c->n)
+        return fail(c, QS_ERR_UNSUPPORTED, "qs_tree_agreement: whole-table contexts only (no table shards)");
+    if (reinterpret_cast<uintptr_t>(dst_device) % 8) return fail(c, QS_ERR_ARG, "qs_tree_agreement: dst_device is not 8-byte aligned");
+    if (int rc = agree_ref_upload(c, ref)) return rc;
+    const DeviceBatch &d = b->d;
+    if (d.n_trees && !d.node_off) return fail(c, QS_ERR_STATE, "qs_tree_agreement: the batch was uploaded without node ranges");
+    QS_HIP(c, hipSetDevice(c->device));
+    if (d.ready) QS_HIP(c, hipStreamWaitEvent(c->stream, d.ready, 0));
+    QS_HIP(c, launch_tree_agree(c->stream, d, c->n, d.max_tree_nodes, c->agree_off, c->agree_bnd, c->agree_par, c->agree_n_u,
+                                reinterpret_cast<unsigned long long *>(dst_device)));
+    return QS_OK;   // asynchronous on the context's stream
 }
 
 // ---- issue probe: how fast does THIS device run the count kernel's instruction mix? ------------------------------------
@@ -1377,6 +1452,7 @@ extern "C" int qs_batch_upload(qs_ctx *c, const qs_tree_batch *hb, qs_device_bat
         node_tree.resize(d.n_nodes);
         for (uint32_t t = 0; t < nt; ++t) {
             const uint32_t L = hb->leaf_off[t + 1] - hb->leaf_off[t];
+            d.max_tree_nodes = std::max(d.max_tree_nodes, hb->node_off[t + 1] - hb->node_off[t]);
             for (uint32_t v = hb->node_off[t]; v < hb->node_off[t + 1]; ++v) {
                 node_tree[v] = t;
                 for (uint32_t k = hb->rng_off[v]; k < hb->rng_off[v + 1]; ++k)
@@ -1825,7 +1901,8 @@ static double host_log_score(uint64_t q1, uint64_t q2, uint64_t q3) {
 }
 
 
-static int build_ref(qs_ctx *c, const qs_ref_tree *ref, RefHost &R) {
+// the checks of a flattened reference tree, its depths, children counts and the id interval of every node
+static int build_ref_shape(qs_ctx *c, const qs_ref_tree *ref, RefHost &R) {
     if (!ref || !ref->parent || !ref->leaf_node) return fail(c, QS_ERR_ARG, "reference tree: NULL arrays");
     if (c && ref->n_taxa != c->n) return fail(c, QS_ERR_ARG, "reference tree: n_taxa differs from the context");
     const uint32_t N = ref->n_nodes, n = ref->n_taxa;
@@ -1884,6 +1961,13 @@ static int build_ref(qs_ctx *c, const qs_ref_tree *ref, RefHost &R) {
     }
     R.bifurcating = (max_rank == 2);
     R.leaf_lo = lo; R.leaf_cnt = cnt;
+    return QS_OK;
+}
+
+static int build_ref(qs_ctx *c, const qs_ref_tree *ref, RefHost &R) {
+    if (int rc = build_ref_shape(c, ref, R)) return rc;
+    const uint32_t N = R.n_nodes, n = R.n;
+    const std::vector<uint32_t> &lo = R.leaf_lo, &cnt = R.leaf_cnt;
     R.root_deg2 = R.nchild[R.root] == 2;
     R.inner_id.assign(N, 0xFFFFFFFFu);
     R.inner_node.clear();

@@ -76,6 +76,7 @@ struct DeviceBatch {
     uint32_t n_nodes = 0, n_links = 0;
     uint32_t *node_off = nullptr, *rng_off = nullptr, *node_tree = nullptr;
     uint16_t *ranges = nullptr;
+    uint32_t max_tree_nodes = 0;    // most inner nodes of one tree (qs_tree_agreement's grid)
     // depth clamp (qs_abi.hip plan_depth_clamp): the correction units of the trees counted in a class below their own depth bits,
     // ordered by the tree's slot in the class-ordered batch (qs_device_batch::fix_slot = that slot per unit, host)
     FixUnit *fix_units = nullptr;   // device
@@ -137,6 +138,10 @@ hipError_t launch_lookup(hipStream_t s, uint32_t n, uint32_t d_lo, uint32_t d_hi
 // qs_remap.hip: dst (ids B) <- src (ids A); src_id_of_dev[i] = A-id of B-id i (a permutation of [0, n)); cell widths 32/32, 16/16 or 16 -> 32
 hipError_t launch_table_remap(hipStream_t s, const void *src, int src_bits, void *dst, int dst_bits, const uint16_t *src_id_of_dev,
                               uint32_t n, uint64_t n_tuples);
+// qs_agree.hip: per-tree quartet agreement with the reference (qs_tree_agreement); the reference's inner nodes with >= 3
+// links as id boundaries (ref_off / ref_bnd, ref_par = has a parent link); dst = 4 words per tree of the batch
+hipError_t launch_tree_agree(hipStream_t s, const DeviceBatch &b, uint32_t n, uint32_t max_tree_nodes, const uint32_t *ref_off,
+                             const uint16_t *ref_bnd, const uint8_t *ref_par, uint32_t n_u, unsigned long long *dst);
 size_t gather_lds_bytes(uint32_t d_hi);
 uint32_t gather_tiles_for_c(uint32_t c); // workgroups of the gather kernel per (d-block, c)
 

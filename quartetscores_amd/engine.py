@@ -42,6 +42,25 @@ for _kv in filter(None, os.environ.get("QS_PY_TUNING", "").split(",")):
     DEFAULT_TUNING[int(_kv.split("=")[0])] = int(_kv.split("=")[1])
 
 
+AGREEMENT_FIELDS = ("concordant", "discordant", "resolved_eval", "resolved_ref")
+
+
+def agreement_columns(counts, taxa) -> dict:
+    """The derived columns of Context.tree_agreement: counts (n, 4) uint64 in AGREEMENT_FIELDS order, taxa (n,) = n_t per tree
+    -> dict of int64 arrays quartets = C(n_t,4), concordant, discordant, eval_only, ref_only, unresolved, and the float64
+    array concordance = concordant / (concordant + discordant) (nan where that sum is 0)."""
+    a = np.asarray(counts, dtype=np.int64).reshape(-1, 4)
+    n = np.asarray(taxa, dtype=np.int64)
+    conc, disc, res_e, res_r = a[:, 0], a[:, 1], a[:, 2], a[:, 3]
+    quartets = np.where(n >= 4, n * (n - 1) * (n - 2) * (n - 3) // 24, 0)
+    eval_only, ref_only = res_e - conc - disc, res_r - conc - disc
+    both = conc + disc
+    with np.errstate(invalid="ignore", divide="ignore"):
+        concordance = np.where(both > 0, conc / np.maximum(both, 1), np.nan)
+    return {"quartets": quartets, "concordant": conc, "discordant": disc, "eval_only": eval_only, "ref_only": ref_only,
+            "unresolved": quartets - both - eval_only - ref_only, "concordance": concordance}
+
+
 class Context:
     """Thin RAII wrapper of qs_ctx."""
 
@@ -54,7 +73,9 @@ class Context:
         self.h = h
         self.n = n_taxa
         self.count_bits = count_bits
+        self.device = device
         self.d_lo, self.d_hi = d_lo, d_hi or n_taxa
+        self._batch_trees = {}  # uploaded batch handle -> its number of trees (tree_agreement)
         self._attached = None  # keeps an attached torch tensor alive
         for key, value in DEFAULT_TUNING.items():
             self.set_tuning(key, value)
@@ -150,6 +171,19 @@ class Context:
             raise ValueError(f"table_remap: src_id_of needs {self.n} entries, got {perm.shape}")
         self._chk(self.L.qs_table_remap(self.h, src.h, perm.ctypes.data_as(C.c_void_p)))
 
+    def tree_agreement(self, ref: flatten.RefTree, hb) -> np.ndarray:
+        """qs_tree_agreement: per tree of the uploaded batch `hb` (uploaded with its node ranges) its quartet agreement with `ref`
+        -> uint64 (n_trees, 4) in AGREEMENT_FIELDS order (agreement_columns derives the rest). Allocates the device buffer,
+        waits for the result and downloads it."""
+        import torch
+        n_trees = self._batch_trees[hb.value]
+        buf = torch.empty(max(1, 4 * n_trees), dtype=torch.int64, device=f"cuda:{self.device}")
+        s, keep = self._ref_struct(ref)
+        self._chk(self.L.qs_tree_agreement(self.h, C.byref(s), hb, C.c_void_p(buf.data_ptr())))
+        self.sync()
+        del keep
+        return buf[: 4 * n_trees].cpu().numpy().view(np.uint64).reshape(n_trees, 4)
+
     def table_clear(self):
         self._chk(self.L.qs_table_clear(self.h))
 
@@ -179,6 +213,7 @@ class Context:
         h = C.c_void_p()
         self._chk(self.L.qs_batch_upload(self.h, C.byref(s), C.byref(h)))
         del keep
+        self._batch_trees[h.value] = b.n_trees
         return h
 
     def batch_flags(self, hb) -> int:
@@ -186,6 +221,7 @@ class Context:
         return int(self.L.qs_batch_flags(hb))
 
     def batch_free(self, hb):
+        self._batch_trees.pop(hb.value, None)
         self.L.qs_batch_free(self.h, hb)
 
     def count_batch(self, hb, algo=QS_ALGO_AUTO):
