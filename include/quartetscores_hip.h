@@ -17,6 +17,8 @@
  *   qs_table_*                    QuartetLookupTable<T> storage (quartet_lookup_table.hpp:19-228);
  *                                 qs_table_remap replaces nothing (the reference recounts per reference tree)
  *   qs_tree_agreement             replaces nothing in the reference (it reports no per-tree agreement)
+ *   qs_taxon_support              replaces nothing in the reference (the nearest is printRawQICScores, :612-680: one text
+ *                                 line per quartet, which a user would reduce per taxon on the host)
  *   qs_score                      QuartetScoreComputer: processNodePair /
  *                                 computeQuartetScoresBifurcating / ...Multifurcating
  *                                 (QuartetScoreComputer.hpp:379-593) + getLQIC/QPIC/EQPICScores (:106-125)
@@ -330,6 +332,24 @@ int qs_lookup(qs_ctx *ctx, uint64_t nq, const uint16_t *abcd, uint64_t *out3);
  * from the context's or its ids are not in depth-first order; QS_ERR_UNSUPPORTED = a table-shard context (use a whole-table one).
  * Asynchronous on the context's stream, ordered behind the batch's upload. */
 int qs_tree_agreement(qs_ctx *ctx, const qs_ref_tree *ref, const qs_device_batch *b, uint64_t *dst_device);
+
+/* Per-taxon quartet support from the count table: which taxa carry the conflict with the reference tree. Taxa are lookup ids
+ * (the reference's depth-first leaf order). For a 4-set with table tuple (n0,n1,n2) the reference's topology is decided as in
+ * qs_score / qs_raw_qic (q1 = its count, q2, q3 = the two alternatives; unresolved under a multifurcation). dst_device
+ * (caller-owned device memory, 8-byte aligned, 6 * n_taxa words [taxon][k]) is OVERWRITTEN with, for every taxon x, over the
+ * 4-sets of THIS context's table (whole table or [d_lo, d_hi) shard: the caller adds the shards) that contain x:
+ *   k = 0 ref_resolved  4-sets the reference resolves        k = 3 eval_only   sum of n0+n1+n2 over the unresolved ones
+ *   k = 1 concordant    sum of q1 over the resolved ones      k = 4 outvoted    resolved ones with max(q2,q3) > q1
+ *   k = 2 discordant    sum of q2+q3 over the resolved ones   k = 5 uninformed  resolved ones with q1+q2+q3 = 0
+ * Exact integers, independent of grid and order. Quartet topologies do not depend on the root: QS_SCORE_ROOT_AS_EDGE and quirk
+ * Q5 play no part. One read of the table; changes neither the table nor trees-counted nor a pending score log
+ * of the same reference tree; a scoring view (qs_score_set_view) is not looked at. The reference tree is checked and uploaded
+ * as by qs_score (cached per context).
+ * Errors: QS_ERR_STATE = no table; QS_ERR_ARG = NULL / misaligned dst, malformed reference, n_taxa differs from the context's,
+ * ids not in depth-first order; QS_ERR_OVERFLOW = C(n_taxa-1,3) x (the trees behind the table -- counted, or
+ * QS_TUNE_TABLE_TREES -- if known, else the largest count a cell holds) exceeds 63 bits; QS_ERR_UNSUPPORTED = more than 3413 taxa
+ * (table-shard contexts only; a whole table ends at 2259). Asynchronous on the context's stream. */
+int qs_taxon_support(qs_ctx *ctx, const qs_ref_tree *ref, int64_t *dst_device);
 
 /* ---- scoring (QuartetScoreComputer) ----------------------------------------------------- */
 

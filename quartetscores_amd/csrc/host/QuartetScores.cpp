@@ -55,6 +55,7 @@ struct AlsoRef {
 struct Args {
     std::string ref, eval, out, raw, raw_bin;
     std::string per_tree;   // --per-tree FILE: quartet agreement of every evaluation tree with -r (TSV)
+    std::string per_taxon;  // --per-taxon FILE: quartet support per taxon of -r from the count table (TSV)
     std::vector<AlsoRef> also;
     size_t threads = 0;
     bool verbose = false, savemem = false, raw_rank_order = false, fail_fast = false, clean_exit = false;
@@ -110,7 +111,12 @@ void usage(std::ostream &os) {
           "   --per-tree F   write the quartet agreement of every evaluation tree with the -r tree to F (TSV, one line per tree in\n"
           "                  -e order after a header: tree taxa quartets concordant discordant eval_only ref_only unresolved\n"
           "                  concordance); computed on the device behind the counting; one GPU that counts (not with --gpus /\n"
-          "                  --table-shards / --load-table)\n";
+          "                  --table-shards / --load-table)\n"
+          "   --per-taxon F  write, per taxon of the -r tree, the support its quartets get from the count table to F (TSV, one line per\n"
+          "                  taxon in lookup-id order after a header: taxon name quartets ref_resolved concordant discordant eval_only\n"
+          "                  outvoted uninformed concordance concordance_without); one more read of the table on the device; a taxon\n"
+          "                  whose concordance_without lies clearly above the others' is a rogue taxon; one GPU with the whole table\n"
+          "                  (not with --gpus / --table-shards); works with --load-table, --also-ref (still the -r tree) and --per-tree\n";
 }
 
 // returns 0 ok, 1 error (message printed like the reference prints TCLAP::ArgException), 2 exit quietly
@@ -182,6 +188,7 @@ int parse(int argc, char **argv, Args &a) {
         else if (f == "--save-table") { if (!(v = need(i, "--save-table"))) return 1; a.dev.save_table = v; }
         else if (f == "--qic-binary") { if (!(v = need(i, "--qic-binary"))) return 1; a.raw_bin = v; }
         else if (f == "--per-tree") { if (!(v = need(i, "--per-tree"))) return 1; a.per_tree = v; }
+        else if (f == "--per-taxon") { if (!(v = need(i, "--per-taxon"))) return 1; a.per_taxon = v; }
         else if (f == "--load-table") { if (!(v = need(i, "--load-table"))) return 1; a.dev.load_table = v; }
         else if (f == "--also-ref") {
             if (i + 2 >= argc || argv[i + 2][0] == '-') {
@@ -271,7 +278,7 @@ void check_per_tree(const Args &a) {
     if (a.per_tree.empty()) return;
     if (a.gpus > 0 || a.table_shards >= 0 || !a.dev.load_table.empty())
         throw std::runtime_error("--per-tree needs the evaluation trees counted on one GPU: omit --gpus / --table-shards / --load-table");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table};
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_taxon};
     for (const AlsoRef &x : a.also) others.insert(x.out);
     if (others.count(a.per_tree)) throw std::runtime_error("--per-tree: " + a.per_tree + " is also another output file");
     if (std::ifstream(a.per_tree).good()) throw std::runtime_error("--per-tree: the output file " + a.per_tree + " already exists");
@@ -321,6 +328,51 @@ struct PerTree {
         if (!f) throw std::runtime_error("cannot write " + path);
     }
 };
+
+// --per-taxon: refused before the device is touched where the whole table is not on one GPU, and where FILE exists or is another output
+void check_per_taxon(const Args &a) {
+    if (a.per_taxon.empty()) return;
+    if (a.gpus > 0 || a.table_shards >= 0)
+        throw std::runtime_error("--per-taxon needs the whole count table on one GPU: omit --gpus / --table-shards");
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree};
+    for (const AlsoRef &x : a.also) others.insert(x.out);
+    if (others.count(a.per_taxon)) throw std::runtime_error("--per-taxon: " + a.per_taxon + " is also another output file");
+    if (std::ifstream(a.per_taxon).good()) throw std::runtime_error("--per-taxon: the output file " + a.per_taxon + " already exists");
+}
+
+// --per-taxon: one qs_taxon_support over the counted (or loaded) table, 6 x n words downloaded, one TSV line per taxon
+void write_per_taxon(qs_ctx *ctx, const RefFlat &ref, int device, const std::string &path) {
+    const size_t n = ref.names.size();
+    qs_ref_tree rt;
+    rt.n_nodes = (uint32_t)ref.parent.size(); rt.n_taxa = (uint32_t)n;
+    rt.parent = ref.parent.data(); rt.leaf_node = ref.leaf_node.data();
+    struct Dev { int64_t *p = nullptr; ~Dev() { if (p) (void)hipFree(p); } } dev;
+    if (hipSetDevice(device) != hipSuccess || hipMalloc((void **)&dev.p, 6 * n * 8) != hipSuccess) throw std::runtime_error("--per-taxon: Insufficient memory!");
+    if (qs_taxon_support(ctx, &rt, dev.p) != QS_OK || qs_sync(ctx) != QS_OK) throw std::runtime_error(std::string("--per-taxon: ") + qs_last_error(ctx));
+    std::vector<int64_t> w(6 * n);
+    if (hipMemcpy(w.data(), dev.p, 6 * n * 8, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("--per-taxon: download failed");
+    int64_t conc = 0, disc = 0;   // of the whole table: every quartet is in four taxa's sums
+    for (size_t x = 0; x < n; ++x) { conc += w[6 * x + 1]; disc += w[6 * x + 2]; }
+    conc /= 4; disc /= 4;
+    std::ofstream f(path);
+    if (!f) throw std::runtime_error("cannot write " + path);
+    f << "taxon\tname\tquartets\tref_resolved\tconcordant\tdiscordant\teval_only\toutvoted\tuninformed\tconcordance\tconcordance_without\n";
+    const uint64_t quartets = n < 4 ? 0 : (uint64_t)(n - 1) * (n - 2) * (n - 3) / 6;
+    auto ratio = [](int64_t c, int64_t d, char (&buf)[64]) {
+        if (c + d) std::snprintf(buf, sizeof buf, "%.6f", (double)c / (double)(c + d));
+        else std::snprintf(buf, sizeof buf, "nan");
+    };
+    char own[64], without[64];
+    for (size_t x = 0; x < n; ++x) {
+        const int64_t *v = &w[6 * x];
+        ratio(v[1], v[2], own);
+        ratio(conc - v[1], disc - v[2], without);
+        f << x << '\t' << ref.names[x] << '\t' << quartets;
+        for (int k = 0; k < 6; ++k) f << '\t' << v[k];
+        f << '\t' << own << '\t' << without << '\n';
+    }
+    if (!f) throw std::runtime_error("cannot write " + path);
+}
 
 // --also-ref, after the primary tree's output is written: its table re-indexed into `table`'s context (allocated before the
 // counting), scored and written per further reference tree
@@ -443,6 +495,7 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
     if (!a.raw.empty()) qsc.printRawQICScores(referenceTree, a.raw);
     if (!a.raw_bin.empty()) qsc.printRawQICBinary(referenceTree, a.raw_bin);
     if (!a.per_tree.empty()) per_tree.write(a.per_tree);
+    if (!a.per_taxon.empty()) write_per_taxon(qsc.context(), qsc.reference(), a.dev.device, a.per_taxon);
     if (!a.also.empty()) {   // the primary tree's output first, exactly as without --also-ref
         write_annotated(referenceTree, a.out, lqic, qpic, eqpic);
         score_also_refs(a, qsc.context(), qsc.reference(), also_table);
@@ -467,6 +520,7 @@ int main(int argc, char *argv[]) {
     try {
         check_also_refs(a);
         check_per_tree(a);
+        check_per_taxon(a);
     } catch (const std::exception &e) {
         std::cerr << "ERROR: " << e.what() << std::endl;
         return 1;

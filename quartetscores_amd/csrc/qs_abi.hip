@@ -108,9 +108,9 @@ struct qs_ctx {
     uint32_t *ref_lca_dev = nullptr;
     uint16_t *ref_next_dev = nullptr;
     void *root_pairs_dev = nullptr;
-    BundlePlan bundle[2];              // rounds of the score bundle kernel in pass 1 / pass 2 for [bundle_r0, bundle_r1) (plan_bundles)
-    uint64_t bundle_r0[2] = {~0ull, ~0ull}, bundle_r1[2] = {~0ull, ~0ull};
-    uint32_t *bundle_dev[2] = {nullptr, nullptr};    // plo[n] | pcnt[n] | rounds[2 R]
+    BundlePlan bundle[3];              // rounds of the score bundle kernel in pass 1 / pass 2 for [bundle_r0, bundle_r1) (plan_bundles); [2]: qs_taxon_support
+    uint64_t bundle_r0[3] = {~0ull, ~0ull, ~0ull}, bundle_r1[3] = {~0ull, ~0ull, ~0ull};
+    uint32_t *bundle_dev[3] = {nullptr, nullptr, nullptr};    // plo[n] | pcnt[n] | rounds[2 R]
     int n_cu = 0;
     // tree batches go to the device through two pinned staging buffers on a copy stream of their own:
     // qs_batch_upload returns once the batch is in pinned memory, the copy of batch k+1 overlaps the counting of batch k
@@ -553,7 +553,7 @@ extern "C" void qs_destroy(qs_ctx *c) {
     if (c->ref_lca_dev) (void)hipFree(c->ref_lca_dev);
     if (c->ref_next_dev) (void)hipFree(c->ref_next_dev);
     if (c->root_pairs_dev) (void)hipFree(c->root_pairs_dev);
-    for (int w = 0; w < 2; ++w) if (c->bundle_dev[w]) (void)hipFree(c->bundle_dev[w]);
+    for (int w = 0; w < 3; ++w) if (c->bundle_dev[w]) (void)hipFree(c->bundle_dev[w]);
     for (int w = 0; w < 2; ++w) { if (c->pin_ev[w]) { (void)hipEventSynchronize(c->pin_ev[w]); (void)hipEventDestroy(c->pin_ev[w]); } if (c->pin[w]) (void)hipHostFree(c->pin[w]); }
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (BatchSlab &sl : c->slabs) { (void)hipFree(sl.p); if (sl.last_use) (void)hipEventDestroy(sl.last_use); }
@@ -2100,17 +2100,18 @@ static void fill_score_device(const qs_ctx *c, const RefHost &R, const uint32_t 
     sd.bundle_plo = sd.bundle_pcnt = sd.bundle_rounds = nullptr; sd.n_rounds = 0; sd.sample = 0;
 }
 
-// the bundle kernel's rounds for the rank range sd covers (own table, table shard or view): planned on the host, cached
+// the bundle kernel's rounds for the rank range sd covers (own table, table shard or view): planned on the host, cached;
+// pass 3 = the per-taxon pass (qs_taxon_support: its own slot and wave count, whatever the score tuning says)
 static int ensure_bundle_plan(qs_ctx *c, ScoreDevice &sd, int pass) {
     sd.bundle_plo = sd.bundle_pcnt = sd.bundle_rounds = nullptr; sd.n_rounds = 0;
-    if (c->tune_score_kernel == 1) return QS_OK;
+    if (c->tune_score_kernel == 1 && pass != 3) return QS_OK;
     if (c->n_cu == 0) { int v = 0; QS_HIP(c, hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device)); c->n_cu = std::max(1, v); }
     const int w = pass - 1;
     BundlePlan &plan = c->bundle[w];
     const uint64_t r0 = sd.rank_lo, r1 = sd.rank_lo + sd.n_tuples;
     if (c->bundle_r0[w] != r0 || c->bundle_r1[w] != r1 || !c->bundle_dev[w]) {
         if (c->bundle_dev[w]) { QS_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->bundle_dev[w]); c->bundle_dev[w] = nullptr; }
-        plan_bundles(c->n, r0, r1, score_bundle_waves(pass, c->tune_score_load == 1 || c->tune_score_load == 3), plan);
+        plan_bundles(c->n, r0, r1, pass == 3 ? (uint32_t)kTaxonWaves : score_bundle_waves(pass, c->tune_score_load == 1 || c->tune_score_load == 3), plan);
         const size_t words = 2 * (size_t)c->n + plan.rounds.size();
         if (hipMalloc(&c->bundle_dev[w], std::max<size_t>(words, 1) * 4) != hipSuccess) return fail(c, QS_ERR_OOM, "qs_score: round table of the bundle kernel");
         hipStream_t up = c->prep_stream ? c->prep_stream : c->stream;
@@ -2124,6 +2125,37 @@ static int ensure_bundle_plan(qs_ctx *c, ScoreDevice &sd, int pass) {
     sd.bundle_plo = c->bundle_dev[w]; sd.bundle_pcnt = c->bundle_dev[w] + c->n; sd.bundle_rounds = c->bundle_dev[w] + 2 * (size_t)c->n;
     sd.n_rounds = (uint32_t)(plan.rounds.size() / 2);
     return QS_OK;
+}
+
+// Per-taxon quartet support of this context's table against the reference tree (qs_taxon.hip). The reference has no such
+// output: this replaces nothing there (the nearest is printRawQICScores, one text line per quartet).
+extern "C" int qs_taxon_support(qs_ctx *c, const qs_ref_tree *ref, int64_t *dst_device) {
+    if (!c) return QS_ERR_ARG;
+    if (!dst_device) return fail(c, QS_ERR_ARG, "qs_taxon_support: NULL argument");
+    if (reinterpret_cast<uintptr_t>(dst_device) % 8) return fail(c, QS_ERR_ARG, "qs_taxon_support: dst_device is not 8-byte aligned");
+    if (!c->table) return fail(c, QS_ERR_STATE, "qs_taxon_support: no table");
+    if (taxon_lds_bytes(c->n) > 160u * 1024u) return fail(c, QS_ERR_UNSUPPORTED, "qs_taxon_support: more than 3413 taxa (the accumulators of a workgroup live in LDS)");
+    // every sum is at most C(n-1,3) x (largest count): the trees behind the table if known, else what a cell can hold
+    const uint64_t cell_max = c->count_bits == 16 ? 0xFFFFull : 0xFFFFFFFFull;
+    const uint64_t trees = std::max(c->trees_counted, c->table_trees_hint);
+    const uint64_t max_count = trees ? std::min(trees, cell_max) : cell_max;
+    const uint64_t per_taxon = c->n >= 4 ? (uint64_t)(c->n - 1) * (c->n - 2) / 2 * (c->n - 3) / 3 : 0;
+    if (per_taxon && max_count > (uint64_t)INT64_MAX / per_taxon)
+        return fail(c, QS_ERR_OVERFLOW, "qs_taxon_support: C(n-1,3) x the largest possible count exceeds 63 bits");
+    QS_HIP(c, hipSetDevice(c->device));
+    const RefHost *Rp = nullptr;
+    if (int rc = get_ref(c, ref, true, &Rp)) return rc;
+    ScoreDevice sd;
+    fill_score_device(c, *Rp, c->ref_lca_dev, sd);
+    sd.rank_lo = c->rank_lo; sd.n_tuples = c->n_tuples; sd.table = c->table; sd.count_bits = (int)c->count_bits;   // the context's own table, not a scoring view
+    sd.flags = nullptr;
+    if (int rc = ensure_bundle_plan(c, sd, 3)) return rc;
+    // (a context's table is cut by the largest id: it starts and ends at a row start, plan_bundles finds no partial rows)
+    if (c->bundle[2].n_parts) return fail(c, QS_ERR_UNSUPPORTED, "qs_taxon_support: the table does not start and end at a row start");
+    QS_HIP(c, hipMemsetAsync(dst_device, 0, (size_t)c->n * 6 * 8, c->stream));
+    const bool wide = max_count >= (1ull << 32) / 192;   // 64 lanes x 3 counts in a 32-bit partial sum
+    QS_HIP(c, launch_taxon_support(c->stream, sd, wide, c->n_cu, reinterpret_cast<unsigned long long *>(dst_device)));
+    return QS_OK;   // asynchronous on the context's stream
 }
 
 extern "C" int qs_score_plan(uint32_t n_taxa, uint64_t rank_lo, uint64_t n_tuples, uint32_t *first_pair, uint32_t *n_pairs, uint64_t parts[4]) {

@@ -142,6 +142,12 @@ hipError_t launch_table_remap(hipStream_t s, const void *src, int src_bits, void
 // links as id boundaries (ref_off / ref_bnd, ref_par = has a parent link); dst = 4 words per tree of the batch
 hipError_t launch_tree_agree(hipStream_t s, const DeviceBatch &b, uint32_t n, uint32_t max_tree_nodes, const uint32_t *ref_off,
                              const uint16_t *ref_bnd, const uint8_t *ref_par, uint32_t n_u, unsigned long long *dst);
+// qs_taxon.hip: per-taxon sums over the whole rows of the rank range of a ScoreDevice (qs_taxon_support); needs sd.bundle_* =
+// plan_bundles with kTaxonWaves waves; dst = 6 words per taxon, zeroed beforehand; wide: counts may reach 2^32 / 192
+struct ScoreDevice;
+constexpr int kTaxonWaves = 12;   // waves per workgroup = consecutive b per round (the logging pass 1's count, qs_score.hip)
+size_t taxon_lds_bytes(uint32_t n);
+hipError_t launch_taxon_support(hipStream_t s, const ScoreDevice &sd, bool wide, int n_cu, unsigned long long *dst);
 size_t gather_lds_bytes(uint32_t d_hi);
 uint32_t gather_tiles_for_c(uint32_t c); // workgroups of the gather kernel per (d-block, c)
 

@@ -61,6 +61,26 @@ def agreement_columns(counts, taxa) -> dict:
             "unresolved": quartets - both - eval_only - ref_only, "concordance": concordance}
 
 
+TAXON_FIELDS = ("ref_resolved", "concordant", "discordant", "eval_only", "outvoted", "uninformed")
+
+
+def taxon_columns(counts) -> dict:
+    """The named columns of Context.taxon_support: counts (n, 6) int64 in TAXON_FIELDS order (the sum over the shards of a
+    sharded table) -> dict of int64 arrays quartets = C(n-1,3) and the six fields, and the float64 arrays concordance =
+    concordant / (concordant + discordant) and concordance_without = the same ratio over the quartets that do NOT hold the
+    taxon (every quartet holds four taxa: the table's totals are the column sums / 4); nan where a denominator is 0."""
+    a = np.asarray(counts, dtype=np.int64).reshape(-1, 6)
+    n = len(a)
+    out = {"quartets": np.full(n, (n - 1) * (n - 2) * (n - 3) // 6 if n >= 4 else 0, dtype=np.int64)}
+    out.update({name: a[:, k] for k, name in enumerate(TAXON_FIELDS)})
+    conc, disc = a[:, 1], a[:, 2]
+    rest_c, rest_d = int(conc.sum()) // 4 - conc, int(disc.sum()) // 4 - disc
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["concordance"] = np.where(conc + disc > 0, conc / np.maximum(conc + disc, 1), np.nan)
+        out["concordance_without"] = np.where(rest_c + rest_d > 0, rest_c / np.maximum(rest_c + rest_d, 1), np.nan)
+    return out
+
+
 class Context:
     """Thin RAII wrapper of qs_ctx."""
 
@@ -183,6 +203,18 @@ class Context:
         self.sync()
         del keep
         return buf[: 4 * n_trees].cpu().numpy().view(np.uint64).reshape(n_trees, 4)
+
+    def taxon_support(self, ref: flatten.RefTree) -> np.ndarray:
+        """qs_taxon_support: per taxon (lookup id) the six sums of TAXON_FIELDS over the 4-sets of this context's table (whole
+        table or shard: add the shards) that hold it -> int64 (n, 6); taxon_columns names and derives the rest. Allocates the
+        device buffer, waits for the result and downloads it."""
+        import torch
+        buf = torch.empty(6 * self.n, dtype=torch.int64, device=f"cuda:{self.device}")
+        s, keep = self._ref_struct(ref)
+        self._chk(self.L.qs_taxon_support(self.h, C.byref(s), C.c_void_p(buf.data_ptr())))
+        self.sync()
+        del keep
+        return buf.cpu().numpy().reshape(self.n, 6)
 
     def table_clear(self):
         self._chk(self.L.qs_table_clear(self.h))
