@@ -68,7 +68,8 @@ enum {
     QS_ERR_HIP = -2,        /* HIP runtime error (message has the HIP string) */
     QS_ERR_OOM = -3,        /* "Insufficient memory!" (QuartetScoreComputer.hpp:735-737) */
     QS_ERR_STATE = -4,      /* call order (e.g. score before count) */
-    QS_ERR_OVERFLOW = -5,   /* a counter would exceed count_bits, or candidate buffer overflow */
+    QS_ERR_OVERFLOW = -5,   /* a counter would exceed count_bits, or candidate buffer overflow; after a counter
+                             * overflow (reported by qs_sync, every algorithm) the table's contents are unspecified */
     QS_ERR_NO_DEVICE = -6,  /* no gfx950 device: the library does not fall back to the CPU */
     QS_ERR_UNSUPPORTED = -7,
     QS_ERR_REFERENCE_THROWS = -8 /* the reference itself ends with an uncaught std::runtime_error on this input; qs_last_error()

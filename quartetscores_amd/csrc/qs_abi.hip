@@ -1504,7 +1504,7 @@ static hipError_t clamp_fix_slots(qs_ctx *c, const qs_device_batch *b, uint32_t 
     const auto lo = std::lower_bound(b->fix_slot.begin(), b->fix_slot.end(), slot_lo), hi = std::lower_bound(lo, b->fix_slot.end(), slot_hi);
     if (lo == hi) return hipSuccess;
     return launch_clamp_fix(c->stream, b->d, b->d.fix_units + (lo - b->fix_slot.begin()), (uint32_t)(hi - lo), std::max(c->d_lo, 3u), c->d_hi,
-                            c->rank_lo, c->table, (int)c->count_bits, mode, wire);
+                            c->rank_lo, c->table, (int)c->count_bits, mode, wire, c->dev_flags);
 }
 
 // QS_COUNT_WIRE16X2: count a binary_full batch straight into the attached wire buffer (one word per tuple)
@@ -1776,7 +1776,7 @@ extern "C" int qs_count_batch(qs_ctx *c, const qs_device_batch *b, uint32_t algo
     } else if (algo == QS_ALGO_SCATTER) {
         if (!d.node_off) return fail(c, QS_ERR_ARG, "qs_count_batch: QS_ALGO_SCATTER needs node_off/rng_off/ranges in the batch");
         if (c->n > 4096) return fail(c, QS_ERR_UNSUPPORTED, "scatter: n too large");
-        QS_HIP(c, launch_count_scatter(c->stream, d, c->n, c->d_lo, c->d_hi, c->rank_lo, c->table, (int)c->count_bits));
+        QS_HIP(c, launch_count_scatter(c->stream, d, c->n, c->d_lo, c->d_hi, c->rank_lo, c->table, (int)c->count_bits, c->dev_flags));
         if (timed) QS_HIP(c, mark(c, 1));
         c->variant = std::string("scatter/atomic/count_u") + std::to_string(c->count_bits);
     } else {

@@ -1027,14 +1027,16 @@ hipError_t launch_count_bitslice3(hipStream_t s, const CountGeometry &g_in, cons
 // scatter count kernel (tree-major, atomics)
 // ======================================================================================
 
-template <typename CT> __device__ __forceinline__ void table_atomic_inc(CT *table, uint64_t cell);
-template <> __device__ __forceinline__ void table_atomic_inc<uint32_t>(uint32_t *table, uint64_t cell) {
+template <typename CT> __device__ __forceinline__ void table_atomic_inc(CT *table, uint64_t cell, uint32_t *overflow_flag);
+template <> __device__ __forceinline__ void table_atomic_inc<uint32_t>(uint32_t *table, uint64_t cell, uint32_t *) {
     atomicAdd(&table[cell], 1u);
 }
-template <> __device__ __forceinline__ void table_atomic_inc<uint16_t>(uint16_t *table, uint64_t cell) {
-    // packed half-word increment: cell totals stay < 2^16, so no carry crosses the half-word
+template <> __device__ __forceinline__ void table_atomic_inc<uint16_t>(uint16_t *table, uint64_t cell, uint32_t *overflow_flag) {
+    // packed half-word increment. The host keeps the trees it counted below 2^16, but not what an uploaded or attached table
+    // held: a half that was full before this increment has wrapped (and, the low one, carried into its neighbour cell)
     uint32_t *w = reinterpret_cast<uint32_t *>(table) + (cell >> 1);
-    atomicAdd(w, (cell & 1) ? 0x10000u : 1u);
+    const uint32_t old = atomicAdd(w, (cell & 1) ? 0x10000u : 1u);
+    if (((cell & 1) ? old >> 16 : old & 0xFFFFu) == 0xFFFFu) atomicOr(overflow_flag, 1u);
 }
 
 constexpr int kScatterMaxLeaves = 4096;
@@ -1049,7 +1051,8 @@ __global__ __launch_bounds__(kWave) void count_scatter_kernel(const uint32_t *__
                                                               const uint32_t *__restrict__ node_tree,
                                                               const uint32_t *__restrict__ rng_off,
                                                               const uint16_t *__restrict__ ranges, uint32_t d_lo,
-                                                              uint32_t d_hi, uint64_t rank_lo, CT *__restrict__ table) {
+                                                              uint32_t d_hi, uint64_t rank_lo, CT *__restrict__ table,
+                                                              uint32_t *__restrict__ overflow_flag) {
     __shared__ uint16_t ids[kScatterMaxLeaves];
     const uint32_t v = blockIdx.x, lane = threadIdx.x;
     const uint32_t t = node_tree[v];
@@ -1086,7 +1089,7 @@ __global__ __launch_bounds__(kWave) void count_scatter_kernel(const uint32_t *__
                                     if (m3 < d_lo || m3 >= d_hi) continue;
                                     const int slot = slot_of_pairing(a, a2, bq, cr);
                                     const uint64_t cell = (rank4(s0, m1, m2, m3) - rank_lo) * 3 + (uint64_t)slot;
-                                    table_atomic_inc<CT>(table, cell);
+                                    table_atomic_inc<CT>(table, cell, overflow_flag);
                                 }
                             }
                         }
@@ -1096,16 +1099,16 @@ __global__ __launch_bounds__(kWave) void count_scatter_kernel(const uint32_t *__
 }
 
 hipError_t launch_count_scatter(hipStream_t s, const DeviceBatch &b, uint32_t n, uint32_t d_lo, uint32_t d_hi,
-                                uint64_t rank_lo, void *table, int count_bits) {
+                                uint64_t rank_lo, void *table, int count_bits, uint32_t *overflow_flag) {
     (void)n;
     if (b.n_nodes == 0) return hipSuccess;
     dim3 grid(b.n_nodes), block(kWave);
     if (count_bits == 32)
         hipLaunchKernelGGL(count_scatter_kernel<uint32_t>, grid, block, 0, s, b.leaf_off, b.leaf_ids, b.node_tree, b.rng_off,
-                           b.ranges, d_lo, d_hi, rank_lo, (uint32_t *)table);
+                           b.ranges, d_lo, d_hi, rank_lo, (uint32_t *)table, overflow_flag);
     else
         hipLaunchKernelGGL(count_scatter_kernel<uint16_t>, grid, block, 0, s, b.leaf_off, b.leaf_ids, b.node_tree, b.rng_off,
-                           b.ranges, d_lo, d_hi, rank_lo, (uint16_t *)table);
+                           b.ranges, d_lo, d_hi, rank_lo, (uint16_t *)table, overflow_flag);
     return hipGetLastError();
 }
 
@@ -1131,19 +1134,21 @@ constexpr int kFixMaxRun = 128;     // leaves of a run (longer runs: the tree ke
 constexpr int kFixThreads = 256;
 enum FixRule { FIX_BINARY = 0, FIX_GENERAL = 1, FIX_WIRE = 2 };
 
-template <typename CT> __device__ __forceinline__ void table_atomic_dec(CT *table, uint64_t cell);
-template <> __device__ __forceinline__ void table_atomic_dec<uint32_t>(uint32_t *table, uint64_t cell) { atomicSub(&table[cell], 1u); }
-template <> __device__ __forceinline__ void table_atomic_dec<uint16_t>(uint16_t *table, uint64_t cell) {
-    // the cell holds at least the tied quartet's own count at this point (the count kernel of the slice ran before): no borrow
+template <typename CT> __device__ __forceinline__ void table_atomic_dec(CT *table, uint64_t cell, uint32_t *overflow_flag);
+template <> __device__ __forceinline__ void table_atomic_dec<uint32_t>(uint32_t *table, uint64_t cell, uint32_t *) { atomicSub(&table[cell], 1u); }
+template <> __device__ __forceinline__ void table_atomic_dec<uint16_t>(uint16_t *table, uint64_t cell, uint32_t *overflow_flag) {
+    // the cell holds at least the tied quartet's own count at this point (the count kernel of the slice ran before): no borrow --
+    // unless that count wrapped the cell, which the count kernel has flagged; a half found empty here is flagged as well
     uint32_t *w = reinterpret_cast<uint32_t *>(table) + (cell >> 1);
-    atomicSub(w, (cell & 1) ? 0x10000u : 1u);
+    const uint32_t old = atomicSub(w, (cell & 1) ? 0x10000u : 1u);
+    if (((cell & 1) ? old >> 16 : old & 0xFFFFu) == 0u) atomicOr(overflow_flag, 1u);
 }
 
 template <typename CT, int RULE>
 __global__ __launch_bounds__(kFixThreads) void clamp_fix_kernel(const FixUnit *__restrict__ units, const uint32_t *__restrict__ leaf_off,
                                                                 const uint16_t *__restrict__ leaf_ids, const uint16_t *__restrict__ adj_depth,
                                                                 uint32_t d_lo, uint32_t d_hi, uint64_t rank_lo, CT *__restrict__ table,
-                                                                uint32_t *__restrict__ wire) {
+                                                                uint32_t *__restrict__ wire, uint32_t *__restrict__ overflow_flag) {
     __shared__ uint16_t ids[kScatterMaxLeaves];
     __shared__ uint16_t rm[kFixMaxRun][kFixMaxRun];   // rm[a][b], a < b: LCA depth of the run's leaves a and b
     const FixUnit u = units[blockIdx.x];
@@ -1190,19 +1195,19 @@ __global__ __launch_bounds__(kFixThreads) void clamp_fix_kernel(const FixUnit *_
             const int slot = slot_of_pairing(pa, pb, oa, ob);
             const uint64_t tup = rank4(s0, s1, s2, s3) - rank_lo;
             if (RULE == FIX_WIRE) { if (slot < 2) atomicAdd(&wire[tup], slot ? 0x10000u : 1u); }   // n0 | n1 << 16; n2 is implied
-            else if (RULE == FIX_GENERAL) table_atomic_inc<CT>(table, tup * 3 + (uint64_t)slot);    // the tie counted nothing
-            else if (slot != 2) { table_atomic_inc<CT>(table, tup * 3 + (uint64_t)slot); table_atomic_dec<CT>(table, tup * 3 + 2); }
+            else if (RULE == FIX_GENERAL) table_atomic_inc<CT>(table, tup * 3 + (uint64_t)slot, overflow_flag);    // the tie counted nothing
+            else if (slot != 2) { table_atomic_inc<CT>(table, tup * 3 + (uint64_t)slot, overflow_flag); table_atomic_dec<CT>(table, tup * 3 + 2, overflow_flag); }
         }
         if (++i == j) { i = 0; if (++j == k) { j = 1; ++k; } }
     }
 }
 
 hipError_t launch_clamp_fix(hipStream_t s, const DeviceBatch &b, const FixUnit *units, uint32_t n_units, uint32_t d_lo, uint32_t d_hi,
-                            uint64_t rank_lo, void *table, int count_bits, int mode, uint32_t *wire) {
+                            uint64_t rank_lo, void *table, int count_bits, int mode, uint32_t *wire, uint32_t *overflow_flag) {
     if (n_units == 0) return hipSuccess;
     dim3 grid(n_units), block(kFixThreads);
     const bool gen = mode == MODE_GENERAL_FULL || mode == MODE_PARTIAL;
-#define QS_FIX(CT, RULE) hipLaunchKernelGGL((clamp_fix_kernel<CT, RULE>), grid, block, 0, s, units, b.leaf_off, b.leaf_ids, b.adj_depth, d_lo, d_hi, rank_lo, (CT *)table, wire)
+#define QS_FIX(CT, RULE) hipLaunchKernelGGL((clamp_fix_kernel<CT, RULE>), grid, block, 0, s, units, b.leaf_off, b.leaf_ids, b.adj_depth, d_lo, d_hi, rank_lo, (CT *)table, wire, overflow_flag)
     if (wire) QS_FIX(uint32_t, FIX_WIRE);
     else if (count_bits == 32) { if (gen) QS_FIX(uint32_t, FIX_GENERAL); else QS_FIX(uint32_t, FIX_BINARY); }
     else { if (gen) QS_FIX(uint16_t, FIX_GENERAL); else QS_FIX(uint16_t, FIX_BINARY); }

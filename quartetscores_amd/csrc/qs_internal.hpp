@@ -122,10 +122,10 @@ hipError_t launch_count_bitslice3_fused(hipStream_t s, const CountGeometry &g, c
                                         const uint32_t seg_trees[4], int depth_bits, void *table, int count_bits, uint32_t *overflow_flag,
                                         bool overwrite);
 hipError_t launch_clamp_fix(hipStream_t s, const DeviceBatch &b, const FixUnit *units, uint32_t n_units, uint32_t d_lo, uint32_t d_hi,
-                            uint64_t rank_lo, void *table, int count_bits, int mode, uint32_t *wire); // corrections of the depth clamp (after the class's count kernel)
+                            uint64_t rank_lo, void *table, int count_bits, int mode, uint32_t *wire, uint32_t *overflow_flag); // corrections of the depth clamp (after the class's count kernel)
 uint32_t bitslice3_tiles_for_c(uint32_t c); // wave tiles per (d-block, c) of count_bitslice3_kernel
 hipError_t launch_count_scatter(hipStream_t s, const DeviceBatch &b, uint32_t n, uint32_t d_lo, uint32_t d_hi,
-                                uint64_t rank_lo, void *table, int count_bits);
+                                uint64_t rank_lo, void *table, int count_bits, uint32_t *overflow_flag);
 hipError_t launch_pack16(hipStream_t s, const void *table_u32, void *dst, uint64_t n_cells, uint32_t *overflow_flag);
 hipError_t launch_pack16x2(hipStream_t s, const void *table_u32, void *dst, uint64_t n_tuples, uint32_t trees,
                            uint32_t *overflow_flag, uint32_t *shape_flag);

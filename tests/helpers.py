@@ -1,4 +1,4 @@
-"""Shared test helpers: table remapping between taxon-id orders, ulp distance, D5 trees."""
+"""Shared test helpers: table remapping between taxon-id orders, ulp distance, D5 trees, batches of repeated trees."""
 import numpy as np
 
 
@@ -69,6 +69,39 @@ def d5_trees(n=64, block=16):
     ref = f"({X[0]},{X[1]},({X[2]},{X[3]}));"
     alt = f"({X[0]},{X[2]},({X[1]},{X[3]}));"
     return ref, alt
+
+
+def repeat_trees(batch, reps, with_nodes=True):
+    """A flattened batch whose trees are those of `batch` repeated: reps = [(tree index, copies), ...] in the order wanted
+    (a tree may appear several times). with_nodes=False leaves the inner-node arrays empty (gather counting needs none)."""
+    from quartetscores_amd.flatten import TreeBatch
+    one = [batch.slice(t, t + 1) for t, _ in reps]
+    k = [int(c) for _, c in reps]
+    m = sum(k)
+
+    def offsets(sizes):
+        return np.concatenate([[0], np.cumsum(np.concatenate(sizes))]).astype(np.uint32) if sizes else np.zeros(1, np.uint32)
+    leaf_off = offsets([np.full(c, len(s.leaf_ids), dtype=np.int64) for s, c in zip(one, k)])
+    ids = np.concatenate([np.tile(s.leaf_ids, c) for s, c in zip(one, k)])
+    dep = np.concatenate([np.tile(s.adj_depth, c) for s, c in zip(one, k)])
+    if not with_nodes:
+        return TreeBatch(m, leaf_off, ids, dep, np.zeros(m + 1, dtype=np.uint32), np.zeros(1, dtype=np.uint32), np.zeros(0, dtype=np.uint16))
+    node_off = offsets([np.full(c, int(s.node_off[1]), dtype=np.int64) for s, c in zip(one, k)])
+    rng_off = offsets([np.tile(np.diff(s.rng_off.astype(np.int64)), c) for s, c in zip(one, k)])
+    ranges = np.concatenate([np.tile(s.ranges, c) for s, c in zip(one, k)])
+    return TreeBatch(m, leaf_off, ids, dep, node_off, rng_off, ranges)
+
+
+def concat_batches(a, b):
+    """the trees of two flattened batches (with their inner-node arrays) as one batch"""
+    from quartetscores_amd.flatten import TreeBatch
+    return TreeBatch(
+        a.n_trees + b.n_trees,
+        np.concatenate([a.leaf_off, b.leaf_off[1:] + a.leaf_off[-1]]).astype(np.uint32),
+        np.concatenate([a.leaf_ids, b.leaf_ids]), np.concatenate([a.adj_depth, b.adj_depth]),
+        np.concatenate([a.node_off, b.node_off[1:] + a.node_off[-1]]).astype(np.uint32),
+        np.concatenate([a.rng_off, b.rng_off[1:] + a.rng_off[-1]]).astype(np.uint32),
+        np.concatenate([a.ranges, b.ranges]))
 
 
 def key_of(csv_names):

@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import d5_trees, key_of, ulp_diff
+from helpers import d5_trees, key_of, repeat_trees, ulp_diff
 from oracle_api import Oracle
 from quartetscores_amd import _lib, flatten, ranks, synth
 
@@ -795,17 +795,9 @@ def test_D5_u32_wrap_of_qp_sums(eng, golden):
     ref_nw, alt_nw = d5_trees(g["n"], g["block"])
     ref = flatten.flatten_reference(ref_nw)
     two = flatten.flatten_eval_trees([ref_nw, alt_nw], ref.name_to_id)
-    L = g["n"]
-
-    def tile(b, t, k):
-        s = b.slice(t, t + 1)
-        return s.leaf_ids, s.adj_depth, k
-    ids = np.concatenate([np.tile(two.slice(t, t + 1).leaf_ids, k) for t, k in ((0, g["mult"][0]), (1, g["mult"][1]))])
-    dep = np.concatenate([np.tile(two.slice(t, t + 1).adj_depth, k) for t, k in ((0, g["mult"][0]), (1, g["mult"][1]))])
     m = sum(g["mult"])
-    big = flatten.TreeBatch(m, (np.arange(m + 1, dtype=np.uint32) * L), ids, dep, np.zeros(m + 1, dtype=np.uint32),
-                            np.zeros(1, dtype=np.uint32), np.zeros(0, dtype=np.uint16))
-    del tile
+    big = repeat_trees(two, [(0, g["mult"][0]), (1, g["mult"][1])], with_nodes=False)
+    assert big.n_trees == m and len(big.leaf_ids) == m * g["n"]
     ctx = eng.Context(g["n"], 32)
     ctx.table_alloc()
     ctx.count_trees(big)
