@@ -61,13 +61,13 @@ struct qs_ctx {
     // geometry
     uint32_t *dprefix = nullptr, *cprefix = nullptr;
     uint32_t n_dblk = 0, total_tiles = 0;
-    uint32_t *dprefix3 = nullptr, *cprefix3 = nullptr; // tiling of count_bitslice3_kernel, binary batches (16x8 tiles, d-blocks counted down from d_hi)
+    uint32_t *dprefix3 = nullptr, *cprefix3 = nullptr; // tiling of count_bitslice3_kernel, every mode (16x8 tiles, d-blocks counted down from d_hi)
     uint32_t total_tiles3 = 0;
     // (a,b)-major launch order of count_bitslice3_kernel's tiles (tile_order below): launch slot -> tile id, built on
-    // first use; [0] binary tiling (16x8), [1] general / partial tiling (8x8). NULL = (d,c)-major (identity).
-    uint32_t *perm[2] = {nullptr, nullptr};
-    bool perm_built[2] = {false, false};
-    std::future<EarlyPerm> perm_early;                 // the binary tiling's launch order, started by qs_create before its first HIP call
+    // first use. NULL = (d,c)-major (identity).
+    uint32_t *perm = nullptr;
+    bool perm_built = false;
+    std::future<EarlyPerm> perm_early;                 // the launch order, started by qs_create before its first HIP call
     uint32_t tile_chunk = 2, tile_cblock = 32;         // a-block (pairs) per chunk / c values per c-block; chunk 0 = (d,c)-major (round 3: 4 | 16 -> 2 | 32, -1.5 %)
     uint32_t tile_cgroup = 0;                          // > 1: c innermost in groups of this many (the waves of a workgroup share M[ab], M[bd])
     // binary tiling, cooperative workgroups (count_bitslice4_kernel): launch slots in groups of 4 tiles of one (a-blocks,
@@ -76,9 +76,7 @@ struct qs_ctx {
     uint32_t *perm_coop = nullptr, *perm_rest = nullptr;
     uint32_t n_coop = 0, n_rest = 0;
     uint32_t tune_coop = 0;                            // QS_TUNE_COOP: 1 = cooperative workgroups on; 0 / 2 = off (the default: measured slower)
-    std::vector<uint32_t> h_cp3, h_dp3, h_cp, h_dp1t;  // host copies of the prefix arrays
-    uint32_t *dprefix1t = nullptr;                     // the same kernel on general / partial batches: 8x8 tiles (cprefix), d-blocks counted down
-    uint32_t total_tiles1t = 0;
+    std::vector<uint32_t> h_cp3, h_dp3;                // host copies of the prefix arrays
     // workspace
     void *panel = nullptr;
     size_t panel_bytes = 0;
@@ -230,14 +228,13 @@ extern "C" const char *qs_last_error(const qs_ctx *ctx) { return ctx ? ctx->err.
 // M[bd] elements of (Bk, d-block) and the M[xc] rows of the c-block, which stay in its 4 MB L2; per (c,d) a chunk still
 // writes 8 contiguous runs of the table. Diagonal tiles follow at the end. 512 taxa x 10000 trees: 568 -> 401 ms,
 // 256 taxa: -35 %. Shards with more than 2^26 tiles keep the (d,c)-major order (the slot array would be > 256 MB).
-// Host part of the launch order: the (a,b)-major enumeration of the tiles of one tiling (bin: 16x8 tiles of count_bitslice3_kernel's
-// two-column instances; else the 8x8 tiling) as launch slot -> tile id, checked to be a bijection. Pure host code (no context, no HIP):
+// Host part of the launch order: the (a,b)-major enumeration of the 16x8 tiles of count_bitslice3_kernel (two a-columns per lane in
+// every instance since round 4) as launch slot -> tile id, checked to be a bijection. Pure host code (no context, no HIP):
 // qs_create starts it on a helper thread BEFORE its first HIP call, so that in a fresh process the ~25 ms it takes at 512 taxa pass
 // while the HIP runtime comes up (round 5: the CLI's first launch 25 ms earlier).
-struct TilePermParams { uint32_t chunk, cblock_in, cgroup, d_hi, n_dblk, total; bool bin; };
+struct TilePermParams { uint32_t chunk, cblock_in, cgroup, d_hi, n_dblk, total; };
 static bool build_tile_perm(const TilePermParams &P, const std::vector<uint32_t> &cp, const std::vector<uint32_t> &dp, std::vector<uint32_t> &perm,
                             std::string &err) {
-    const bool bin = P.bin;
     const uint32_t total = P.total, chunk = P.chunk, d_hi = P.d_hi, n_dblk = P.n_dblk;
     perm.clear();
     perm.reserve(total);
@@ -248,9 +245,9 @@ static bool build_tile_perm(const TilePermParams &P, const std::vector<uint32_t>
     // off-diagonal tiles under b-block Bk. (Building the lists of several Bk on helper threads was tried: in the CLI, where 8 host
     // threads flatten the first batch at the same time, the set-up thread then was ready after 27-30 ms instead of 24.)
     auto emit_Bk = [&](uint32_t Bk, std::vector<uint32_t> &out) {
-        // binary: tile Bk^2/4 + j = a-blocks (2j, 2j+1); general: tile C(Bk,2) + j = a-block j (unrank2 in the kernel)
-        const uint32_t base = bin ? (Bk * Bk) / 4 : Bk * (Bk - 1) / 2;
-        const uint32_t nj = bin ? ((Bk + 1) * (Bk + 1)) / 4 - base : Bk;
+        // tile Bk^2/4 + j = a-blocks (2j, 2j+1)
+        const uint32_t base = (Bk * Bk) / 4;
+        const uint32_t nj = ((Bk + 1) * (Bk + 1)) / 4 - base;
         const uint32_t c_lo = std::max(2u, 8 * Bk + 1);      // T(c) > Bk
         for (uint32_t j0 = 0; j0 < nj; j0 += chunk) {
             const uint32_t j1 = std::min(nj, j0 + chunk);
@@ -279,7 +276,7 @@ static bool build_tile_perm(const TilePermParams &P, const std::vector<uint32_t>
             const uint32_t d1 = d_hi - k * kDB;
             for (uint32_t cc = 2; cc + 1 < d1; ++cc) {
                 const uint32_t T = T_of(cc);
-                if (kd < (T + 1) / 2) perm.push_back(dp[k] + cp[cc] + (bin ? (T * T) / 4 : T * (T - 1) / 2) + kd);
+                if (kd < (T + 1) / 2) perm.push_back(dp[k] + cp[cc] + (T * T) / 4 + kd);
             }
         }
     if (perm.size() != total) { err = "tile order: enumeration does not match the tiling"; return false; }
@@ -293,24 +290,23 @@ static bool build_tile_perm(const TilePermParams &P, const std::vector<uint32_t>
     return true;
 }
 
-static int tile_order(qs_ctx *c, int which, const uint32_t **out) {
+static int tile_order(qs_ctx *c, const uint32_t **out) {
     *out = nullptr;
-    if (c->perm_built[which]) { *out = c->perm[which]; return QS_OK; }
-    c->perm_built[which] = true;
-    const bool bin = which == 0;
-    const uint32_t total = bin ? c->total_tiles3 : c->total_tiles1t;
+    if (c->perm_built) { *out = c->perm; return QS_OK; }
+    c->perm_built = true;
+    const uint32_t total = c->total_tiles3;
     const uint32_t chunk = c->tile_chunk;
     if (chunk == 0 || total == 0 || total > (1u << 26)) {
-        if (bin && c->perm_early.valid()) c->perm_early.wait();
+        if (c->perm_early.valid()) c->perm_early.wait();
         return QS_OK;
     }
     const uint32_t d_hi = c->d_hi, n_dblk = c->n_dblk;
-    const std::vector<uint32_t> &cp = bin ? c->h_cp3 : c->h_cp, &dp = bin ? c->h_dp3 : c->h_dp1t;
-    const TilePermParams P{chunk, c->tile_cblock, c->tile_cgroup, d_hi, n_dblk, total, bin};
+    const std::vector<uint32_t> &cp = c->h_cp3, &dp = c->h_dp3;
+    const TilePermParams P{chunk, c->tile_cblock, c->tile_cgroup, d_hi, n_dblk, total};
     std::vector<uint32_t> perm;
     std::string perr;
     bool have = false;
-    if (bin && c->perm_early.valid()) {       // started by qs_create beside the HIP start-up
+    if (c->perm_early.valid()) {       // started by qs_create beside the HIP start-up
         EarlyPerm ep = c->perm_early.get();
         if (ep.ok && ep.chunk == P.chunk && ep.cblock_in == P.cblock_in && ep.cgroup == P.cgroup) { perm.swap(ep.perm); have = true; }
     }
@@ -321,7 +317,7 @@ static int tile_order(qs_ctx *c, int which, const uint32_t **out) {
     const uint32_t cblock = c->tile_cblock ? c->tile_cblock : cmax + 1;
     // Off unless asked for (QS_TUNE_COOP = 1): measured on MI355X the real barrier per 32-tree step costs more than the
     // shared loads save (512 taxa x 10000 trees: 368 ms against 354 ms; profiles/r03_experiments.md)
-    if (bin && c->tune_coop == 1) {
+    if (c->tune_coop == 1) {
         // Cooperative launch order: same nesting ((a,b)-major: b-block, chunk of a-block pairs, c-block, d-block), but
         // innermost FOUR consecutive c of one a-block pair -- one workgroup of count_bitslice4_kernel. A group short of
         // four valid c is filled with shadow copies of its first tile.
@@ -376,10 +372,10 @@ static int tile_order(qs_ctx *c, int which, const uint32_t **out) {
             c->n_coop = (uint32_t)coop.size(); c->n_rest = (uint32_t)rest.size();
         }
     }
-    if (hipMalloc(&c->perm[which], perm.size() * 4) != hipSuccess) return fail(c, QS_ERR_OOM, "hipMalloc tile order");
-    if (hipMemcpyAsync(c->perm[which], perm.data(), perm.size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+    if (hipMalloc(&c->perm, perm.size() * 4) != hipSuccess) return fail(c, QS_ERR_OOM, "hipMalloc tile order");
+    if (hipMemcpyAsync(c->perm, perm.data(), perm.size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, QS_ERR_HIP, "memcpy tile order");
-    *out = c->perm[which];
+    *out = c->perm;
     return QS_OK;
 }
 
@@ -399,7 +395,8 @@ extern "C" int qs_set_tuning(qs_ctx *c, uint32_t key, uint64_t value) {
         case QS_TUNE_TILE_ORDER:
             QS_HIP(c, hipSetDevice(c->device));
             QS_HIP(c, hipStreamSynchronize(c->stream));
-            for (int w = 0; w < 2; ++w) { if (c->perm[w]) (void)hipFree(c->perm[w]); c->perm[w] = nullptr; c->perm_built[w] = false; }
+            if (c->perm) (void)hipFree(c->perm);
+            c->perm = nullptr; c->perm_built = false;
             if (c->perm_coop) (void)hipFree(c->perm_coop);
             if (c->perm_rest) (void)hipFree(c->perm_rest);
             c->perm_coop = c->perm_rest = nullptr; c->n_coop = c->n_rest = 0;
@@ -433,8 +430,8 @@ extern "C" int qs_set_tuning(qs_ctx *c, uint32_t key, uint64_t value) {
             if (c->tune_coop != (uint32_t)value) {   // the launch lists depend on it: rebuild on next use
                 QS_HIP(c, hipSetDevice(c->device));
                 QS_HIP(c, hipStreamSynchronize(c->stream));
-                if (c->perm[0]) (void)hipFree(c->perm[0]);
-                c->perm[0] = nullptr; c->perm_built[0] = false;
+                if (c->perm) (void)hipFree(c->perm);
+                c->perm = nullptr; c->perm_built = false;
                 if (c->perm_coop) (void)hipFree(c->perm_coop);
                 if (c->perm_rest) (void)hipFree(c->perm_rest);
                 c->perm_coop = c->perm_rest = nullptr; c->n_coop = c->n_rest = 0;
@@ -484,19 +481,17 @@ extern "C" int qs_create(qs_ctx **out, uint32_t n_taxa, uint32_t count_bits, uin
     if (tiles64 >= (1ull << 31)) { delete c; return fail(nullptr, QS_ERR_UNSUPPORTED, "qs_create: shard too large for one launch; use a narrower [d_lo, d_hi)"); }
     c->total_tiles = dp[c->n_dblk];
     // the 16x8 tiles of count_bitslice3_kernel; block k = [max(d_start, d1 - 8), d1) with d1 = d_hi - 8k
-    std::vector<uint32_t> cp3(n_taxa + 2, 0), dp3(c->n_dblk + 1, 0), dp1(c->n_dblk + 1, 0);
+    std::vector<uint32_t> cp3(n_taxa + 2, 0), dp3(c->n_dblk + 1, 0);
     {
         for (uint32_t cc = 2; cc <= n_taxa; ++cc) cp3[cc + 1] = cp3[cc] + bitslice3_tiles_for_c(cc);
         uint64_t t3 = 0;
         for (uint32_t k = 0; k < c->n_dblk; ++k) { t3 += cp3[d_hi - k * kDB - 1]; dp3[k + 1] = (uint32_t)t3; }
         if (t3 >= (1ull << 31)) { delete c; return fail(nullptr, QS_ERR_UNSUPPORTED, "qs_create: shard too large for one launch; use a narrower [d_lo, d_hi)"); }
         c->total_tiles3 = dp3[c->n_dblk];
-        for (uint32_t k = 0; k < c->n_dblk; ++k) dp1[k + 1] = dp1[k] + cp[d_hi - k * kDB - 1]; // total equals total_tiles (< 2^31, checked above)
-        c->h_cp3 = cp3; c->h_dp3 = dp3; c->h_cp = cp; c->h_dp1t = dp1;
-        c->total_tiles1t = dp1[c->n_dblk];
+        c->h_cp3 = cp3; c->h_dp3 = dp3;
     }
     if (c->total_tiles3 >= (1u << 20) && c->total_tiles3 <= (1u << 26) && c->tile_chunk) {
-        const TilePermParams P{c->tile_chunk, c->tile_cblock, c->tile_cgroup, c->d_hi, c->n_dblk, c->total_tiles3, true};
+        const TilePermParams P{c->tile_chunk, c->tile_cblock, c->tile_cgroup, c->d_hi, c->n_dblk, c->total_tiles3};
         try {
             c->perm_early = std::async(std::launch::async, [P, cp3, dp3] {
                 EarlyPerm ep; ep.chunk = P.chunk; ep.cblock_in = P.cblock_in; ep.cgroup = P.cgroup;
@@ -515,15 +510,11 @@ extern "C" int qs_create(qs_ctx **out, uint32_t n_taxa, uint32_t count_bits, uin
     }
     if (device < 0 || device >= ndev) { delete c; return fail(nullptr, QS_ERR_ARG, "qs_create: bad device ordinal"); }
     if (hipSetDevice(device) != hipSuccess) { delete c; return fail(nullptr, QS_ERR_HIP, "qs_create: hipSetDevice"); }
-    // the kernels take d_lo as the first d of block 0
-    c->d_lo = d_lo; // shard boundary for ranks
     auto cleanup = [&](int code, const std::string &m) { qs_destroy(c); return fail(nullptr, code, m); };
     if (hipMalloc(&c->cprefix, cp.size() * 4) != hipSuccess) return cleanup(QS_ERR_OOM, "hipMalloc cprefix");
     if (hipMalloc(&c->dprefix, dp.size() * 4) != hipSuccess) return cleanup(QS_ERR_OOM, "hipMalloc dprefix");
     if (hipMemcpy(c->cprefix, cp.data(), cp.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return cleanup(QS_ERR_HIP, "memcpy cprefix");
     if (hipMemcpy(c->dprefix, dp.data(), dp.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return cleanup(QS_ERR_HIP, "memcpy dprefix");
-    if (hipMalloc(&c->dprefix1t, dp1.size() * 4) != hipSuccess) return cleanup(QS_ERR_OOM, "hipMalloc dprefix1t");
-    if (hipMemcpy(c->dprefix1t, dp1.data(), dp1.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return cleanup(QS_ERR_HIP, "memcpy dprefix1t");
     if (hipMalloc(&c->cprefix3, cp3.size() * 4) != hipSuccess) return cleanup(QS_ERR_OOM, "hipMalloc cprefix3");
     if (hipMalloc(&c->dprefix3, dp3.size() * 4) != hipSuccess) return cleanup(QS_ERR_OOM, "hipMalloc dprefix3");
     if (hipMemcpy(c->cprefix3, cp3.data(), cp3.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return cleanup(QS_ERR_HIP, "memcpy cprefix3");
@@ -542,11 +533,10 @@ extern "C" void qs_destroy(qs_ctx *c) {
     if (c->dprefix) (void)hipFree(c->dprefix);
     if (c->cprefix) (void)hipFree(c->cprefix);
     if (c->dprefix3) (void)hipFree(c->dprefix3);
-    for (int w = 0; w < 2; ++w) if (c->perm[w]) (void)hipFree(c->perm[w]);
+    if (c->perm) (void)hipFree(c->perm);
     if (c->perm_coop) (void)hipFree(c->perm_coop);
     if (c->perm_rest) (void)hipFree(c->perm_rest);
     if (c->dev_logk) (void)hipFree(c->dev_logk);
-    if (c->dprefix1t) (void)hipFree(c->dprefix1t);
     if (c->cprefix3) (void)hipFree(c->cprefix3);
     if (c->dev_flags) (void)hipFree(c->dev_flags);
     for (hipEvent_t e : c->evs) (void)hipEventDestroy(e);
@@ -588,7 +578,7 @@ extern "C" int qs_prepare(qs_ctx *c, uint64_t n_trees_hint) {
     }
     struct Join { std::thread &t; ~Join() { if (t.joinable()) t.join(); } } join_staging{staging};
     const uint32_t *order = nullptr;
-    int rc = tile_order(c, 0, &order);
+    int rc = tile_order(c, &order);
     if (rc != QS_OK) return rc;
     if (n_trees_hint && !c->panel) {
         const size_t group_bytes = (size_t)binom2(c->n) * 5 * 4;   // 5 planes: the common depth class
@@ -1507,7 +1497,122 @@ static hipError_t clamp_fix_slots(qs_ctx *c, const qs_device_batch *b, uint32_t 
                             c->rank_lo, c->table, (int)c->count_bits, mode, wire, c->dev_flags);
 }
 
-// QS_COUNT_WIRE16X2: count a binary_full batch straight into the attached wire buffer (one word per tuple)
+// the pair-depth panel holds `need` bytes (growing it waits for the launches that read the old one)
+static int ensure_panel(qs_ctx *c, size_t need) {
+    if (need <= c->panel_bytes) return QS_OK;
+    if (c->panel) { QS_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->panel); c->panel = nullptr; c->panel_bytes = 0; }
+    if (hipMalloc(&c->panel, need) != hipSuccess) return fail(c, QS_ERR_OOM, "Insufficient memory! (pair-depth panel)");
+    c->panel_bytes = need;
+    return QS_OK;
+}
+
+// The shard as a count kernel sees it: the 8x8 tiling of the byte-SWAR gather kernel, or (tiles16x8) the 16x8 tiling of the bit-sliced
+// kernels with its launch order -- asked for here, so that a batch without a bit-sliced launch never builds it -- and, for a
+// binary_full launch that is not fused (coop), the cooperative lists.
+static int count_geometry(qs_ctx *c, bool tiles16x8, bool coop, CountGeometry &g) {
+    g.n = c->n; g.d_lo = std::max(c->d_lo, 3u); g.d_hi = c->d_hi; g.rank_lo = c->rank_lo; g.n_dblk = c->n_dblk;
+    if (!tiles16x8) { g.total_tiles = c->total_tiles; g.dprefix = c->dprefix; g.cprefix = c->cprefix; return QS_OK; }
+    g.total_tiles = c->total_tiles3; g.dprefix = c->dprefix3; g.cprefix = c->cprefix3;
+    const int rc = tile_order(c, &g.perm);
+    if (rc == QS_OK && coop) { g.perm_coop = c->perm_coop; g.n_coop = c->n_coop; g.perm_rest = c->perm_rest; g.n_rest = c->n_rest; }
+    return rc;
+}
+
+// One launch of a count kernel = 1..4 segments; a segment = one class's share of it: the slots [slot0, slot0 + trees) of the
+// class-ordered batch in a panel of their own. (Classes = kernel mode x depth bits per TREE: qs_batch_upload.)
+struct Seg {
+    uint32_t slot0, trees;
+    int mode;             // CountMode of the kernel instance
+    bool part;            // panel elements carry a presence word
+    uint32_t nw;          // bit-sliced: words per compact panel element
+    uint32_t tpg;         // trees per group (= panel element along the tree axis): 32, byte-SWAR 16 / 8
+    size_t group_bytes;   // bytes of one group: an element per pair
+    uint32_t groups() const { return (trees + tpg - 1) / tpg; }
+};
+enum CountKernel { KERNEL_BITSLICE3, KERNEL_FUSED, KERNEL_SWAR };
+struct Launch {
+    CountKernel kernel;
+    int bits;             // depth bits of the bit-sliced instance, panel bits (8 / 16) of the byte-SWAR kernel
+    std::vector<Seg> segs;
+};
+
+static Seg bitslice_seg(const qs_ctx *c, uint32_t slot0, uint32_t trees, int mode, uint32_t depth_bits) {
+    const bool part = mode == MODE_PARTIAL || mode == MODE_BINARY_PARTIAL;
+    const uint32_t nw = std::max(depth_bits, 4u) + (part ? 1u : 0u);
+    return Seg{slot0, trees, mode, part, nw, 32u, (size_t)binom2(c->n) * nw * 4};
+}
+
+// a class in the variant string: [mode.]bitslice_b<planes>x2[:trees] or [mode.]depth_u<panel bits>[:trees]; the wire format names the
+// kernel family once, in front of its classes (family = false)
+static std::string class_name(const Launch &L, const Seg &sg, bool family, const char *mode, bool with_trees) {
+    std::string nm = L.kernel == KERNEL_SWAR ? "depth_u" + std::to_string(L.bits)
+                                             : (family ? "bitslice_b" : "b") + std::to_string(std::max(L.bits, 4)) + "x2";
+    if (mode) nm = std::string(mode) + "." + nm;
+    if (with_trees) nm += ":" + std::to_string(sg.trees);
+    return nm;
+}
+
+// Enqueue one launch, slice by slice (slice_groups over the concatenated group list [0, g_total) of its segments; slice [g0, g1)
+// takes from every segment the groups that fall into it): panel build(s), count kernel, depth-clamp corrections, and with
+// `timed` an event after each of the three. Into the table, or (wire != NULL) the two-cell wire words.
+static int run_launch(qs_ctx *c, const qs_device_batch *b, const Launch &L, uint32_t *wire, bool timed, bool overwrite, bool &first) {
+    const DeviceBatch &d = b->d;
+    const bool bitsliced = L.kernel != KERNEL_SWAR;
+    const int mode0 = L.segs[0].mode;
+    CountGeometry g;
+    int rc = count_geometry(c, bitsliced, L.kernel == KERNEL_BITSLICE3 && mode0 == MODE_BINARY_FULL, g);
+    if (rc != QS_OK) return rc;
+    uint32_t g_total = 0;
+    size_t group_bytes = 0;
+    for (const Seg &sg : L.segs) { g_total += sg.groups(); group_bytes = std::max(group_bytes, sg.group_bytes); }
+    const uint32_t per_slice = slice_groups(c, group_bytes, g_total, g.perm != nullptr);
+    // The segments of a slice lie one behind the other, each at a 256-byte boundary: only the gaps BETWEEN them need room. A launch
+    // of one segment so asks for per_slice groups exactly -- what qs_prepare has allocated ahead for the common 5-plane class; a
+    // byte more would make the CLI's first count wait for the stream, free that panel and allocate another.
+    rc = ensure_panel(c, (size_t)per_slice * group_bytes + 256 * (L.segs.size() - 1));
+    if (rc != QS_OK) return rc;
+    for (uint32_t g0 = 0; g0 < g_total; g0 += per_slice) {
+        const uint32_t g1 = std::min(g_total, g0 + per_slice);
+        // per CountMode, as the fused kernel takes them (a mode without trees in this slice: 0 groups)
+        const void *seg_panel[4] = {nullptr, nullptr, nullptr, nullptr};
+        uint32_t seg_groups[4] = {0, 0, 0, 0}, seg_trees[4] = {0, 0, 0, 0}, seg_slot[4] = {0, 0, 0, 0};
+        size_t off = 0;
+        uint32_t base = 0;
+        for (const Seg &sg : L.segs) {
+            const uint32_t a = std::max(g0, base), e_ = std::min(g1, base + sg.groups());
+            base += sg.groups();
+            if (a >= e_) continue;
+            const uint32_t ga = a - (base - sg.groups()), nch = e_ - a;
+            const uint32_t t0 = ga * sg.tpg, nt = std::min(nch * sg.tpg, sg.trees - t0);
+            DeviceBatch sub = d;
+            sub.slot0 = sg.slot0 + t0;        // slots [slot0, slot0 + nt) of the class-ordered batch
+            sub.n_trees = nt;
+            void *pp = (char *)c->panel + off;
+            if (bitsliced) QS_HIP(c, launch_build_bitpanel(c->stream, sub, c->n, sg.part, pp, nch, sg.nw, c->tune_panel_kernel == 1));
+            else QS_HIP(c, launch_build_panel(c->stream, sub, c->n, L.bits, sg.part, pp, nch));
+            seg_panel[sg.mode] = pp; seg_groups[sg.mode] = nch; seg_trees[sg.mode] = nt; seg_slot[sg.mode] = sub.slot0;
+            off += ((size_t)nch * sg.group_bytes + 255) & ~(size_t)255;
+        }
+        if (timed) QS_HIP(c, mark(c, 0));
+        const bool ow = overwrite && first;
+        if (L.kernel == KERNEL_FUSED)
+            QS_HIP(c, launch_count_bitslice3_fused(c->stream, g, seg_panel, seg_groups, seg_trees, L.bits, c->table, (int)c->count_bits, c->dev_flags, ow));
+        else if (L.kernel == KERNEL_BITSLICE3)
+            QS_HIP(c, launch_count_bitslice3(c->stream, g, seg_panel[mode0], L.bits, mode0, seg_groups[mode0], seg_trees[mode0], wire ? nullptr : c->table,
+                                             wire ? 32 : (int)c->count_bits, c->dev_flags, ow, wire));
+        else QS_HIP(c, launch_count_gather(c->stream, g, seg_panel[mode0], L.bits, mode0, seg_groups[mode0], seg_trees[mode0], c->table, (int)c->count_bits, c->dev_flags, ow));
+        first = false;
+        if (timed) QS_HIP(c, mark(c, 1));
+        if (bitsliced && d.n_fix) {   // (never the byte-SWAR kernel: its panel holds the trees' own depths)
+            for (int mo = 0; mo < 4; ++mo)   // (the rule of the correction depends on the mode: a tied quartet sits in the third cell of a binary tree)
+                if (seg_groups[mo]) QS_HIP(c, clamp_fix_slots(c, b, seg_slot[mo], seg_slot[mo] + seg_trees[mo], mo, wire));
+            if (timed) QS_HIP(c, mark(c, 2));
+        }
+    }
+    return QS_OK;
+}
+
+// QS_COUNT_WIRE16X2: count a binary_full batch straight into the attached wire buffer (one word per tuple), class by class
 static int count_batch_wire(qs_ctx *c, const qs_device_batch *b, uint32_t algo) {
     const DeviceBatch &d = b->d;
     if (!c->wire_out) return fail(c, QS_ERR_STATE, "QS_COUNT_WIRE16X2: no wire buffer (qs_wire_attach first)");
@@ -1526,42 +1631,17 @@ static int count_batch_wire(qs_ctx *c, const qs_device_batch *b, uint32_t algo) 
     if ((overwrite ? 0 : c->wire_trees) + d.n_trees > 0xFFFFull)
         return fail(c, QS_ERR_OVERFLOW, "QS_COUNT_WIRE16X2: more than 65535 trees do not fit 16-bit cells");
     if (d.class_bits[d.n_classes - 1] > 10) return fail(c, QS_ERR_UNSUPPORTED, "QS_COUNT_WIRE16X2: tree depth needs more than 10 bits; count into the table instead");
-    CountGeometry g;
-    g.n = c->n; g.d_lo = std::max(c->d_lo, 3u); g.d_hi = c->d_hi; g.rank_lo = c->rank_lo; g.n_dblk = c->n_dblk;
-    g.total_tiles = c->total_tiles3; g.dprefix = c->dprefix3; g.cprefix = c->cprefix3;
-    { int rc_o = tile_order(c, 0, &g.perm); if (rc_o != QS_OK) return rc_o; }
-    g.perm_coop = c->perm_coop; g.n_coop = c->n_coop; g.perm_rest = c->perm_rest; g.n_rest = c->n_rest;
+    { const uint32_t *order; int rc_o = tile_order(c, &order); if (rc_o != QS_OK) return rc_o; }   // (a failure here leaves the last call's events as they were)
     c->ev_used = 0;
     if (timed) QS_HIP(c, mark(c, 0));
     bool first = true;
     c->variant = "gather/binary_full/bitslice_";
     for (uint32_t k = 0; k < d.n_classes; ++k) {
-        const uint32_t s_lo = k ? d.class_end[k - 1] : 0, s_hi = d.class_end[k], depth_bits = d.class_bits[k];
-        const uint32_t compact_nw = std::max(depth_bits, 4u);
-        const size_t chunk_bytes = (size_t)binom2(c->n) * compact_nw * 4;
-        const uint32_t n_chunks_total = (s_hi - s_lo + 31) / 32;
-        const uint32_t chunks_per_slice = slice_groups(c, chunk_bytes, n_chunks_total, g.perm != nullptr);
-        const size_t need = (size_t)chunks_per_slice * chunk_bytes;
-        if (need > c->panel_bytes) {
-            if (c->panel) { QS_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->panel); c->panel = nullptr; c->panel_bytes = 0; }
-            if (hipMalloc(&c->panel, need) != hipSuccess) return fail(c, QS_ERR_OOM, "Insufficient memory! (pair-depth panel)");
-            c->panel_bytes = need;
-        }
-        for (uint32_t ch0 = 0; ch0 < n_chunks_total; ch0 += chunks_per_slice) {
-            const uint32_t nch = std::min(chunks_per_slice, n_chunks_total - ch0);
-            const uint32_t t0 = ch0 * 32, nt = std::min(nch * 32, s_hi - s_lo - t0);
-            DeviceBatch sub = d;
-            sub.slot0 = s_lo + t0;
-            sub.n_trees = nt;
-            QS_HIP(c, launch_build_bitpanel(c->stream, sub, c->n, false, c->panel, nch, compact_nw, c->tune_panel_kernel == 1));
-            if (timed) QS_HIP(c, mark(c, 0));
-            QS_HIP(c, launch_count_bitslice3(c->stream, g, c->panel, (int)depth_bits, MODE_BINARY_FULL, nch, nt, nullptr, 32, c->dev_flags,
-                                             overwrite && first, c->wire_out));
-            if (timed) QS_HIP(c, mark(c, 1));
-            if (d.n_fix) { QS_HIP(c, clamp_fix_slots(c, b, sub.slot0, sub.slot0 + nt, MODE_BINARY_FULL, c->wire_out)); if (timed) QS_HIP(c, mark(c, 2)); }
-            first = false;
-        }
-        c->variant += (k ? "+b" : "b") + std::to_string(depth_bits) + "x2" + (d.n_classes > 1 ? ":" + std::to_string(s_hi - s_lo) : "");
+        const uint32_t s_lo = k ? d.class_end[k - 1] : 0;
+        const Launch L{KERNEL_BITSLICE3, (int)d.class_bits[k], {bitslice_seg(c, s_lo, d.class_end[k] - s_lo, MODE_BINARY_FULL, d.class_bits[k])}};
+        int rc = run_launch(c, b, L, c->wire_out, timed, overwrite, first);
+        if (rc != QS_OK) return rc;
+        c->variant += (k ? "+" : "") + class_name(L, L.segs[0], false, nullptr, d.n_classes > 1);
     }
     c->variant += "/wire_u16x2";
     if (d.n_fix) c->variant += "/clamp:" + std::to_string(d.clamped_trees);
@@ -1599,12 +1679,8 @@ extern "C" int qs_count_batch(qs_ctx *c, const qs_device_batch *b, uint32_t algo
     if (timed) QS_HIP(c, mark(c, 0));
     if (algo == QS_ALGO_GATHER) {
         static const char *mode_names[4] = {"binary_full", "general_full", "partial", "binary_partial"};
-        CountGeometry g;
-        g.n = c->n; g.d_lo = std::max(c->d_lo, 3u); g.d_hi = c->d_hi; g.rank_lo = c->rank_lo;
-        g.n_dblk = c->n_dblk; g.total_tiles = c->total_tiles; g.dprefix = c->dprefix; g.cprefix = c->cprefix;
-        // One (panel build + count kernel) per slice of every class of the batch (classes = kernel mode x depth bits per TREE:
-        // qs_batch_upload; slices: slice_groups). With QS_IMPL_SWAR the whole batch is one class of the byte-SWAR kernel,
-        // in the mode the batch as a whole needs.
+        // This function only chooses the launches (run_launch enqueues them). With QS_IMPL_SWAR the whole batch is one class of the
+        // byte-SWAR kernel, in the mode the batch as a whole needs.
         const uint32_t top_bits = 10u;
         const bool all_swar = c->tune_gather_impl == QS_IMPL_SWAR;
         if (c->tune_gather_impl == QS_IMPL_BITSLICE)
@@ -1616,162 +1692,60 @@ extern "C" int qs_count_batch(qs_ctx *c, const qs_device_batch *b, uint32_t algo
         const int batch_mode = !d.all_full ? MODE_PARTIAL : (d.all_binary ? MODE_BINARY_FULL : MODE_GENERAL_FULL);
         std::string names;
         bool any_coop = false;
+        // several classes: "a:trees+b:trees", classes of several modes: "mode.a:trees+..."
+        auto run_and_name = [&](const Launch &L) {
+            const int rc = run_launch(c, b, L, nullptr, timed, overwrite, first);
+            for (const Seg &sg : L.segs)
+                if (rc == QS_OK) names += (names.empty() ? "" : "+") + class_name(L, sg, true, mixed ? mode_names[sg.mode] : nullptr, n_cls > 1);
+            return rc;
+        };
+        auto slot_lo = [&](uint32_t k) { return k ? d.class_end[k - 1] : 0u; };
         // ---- fused launches (QS_TUNE_FUSE_CLASSES): the bit-sliced classes that share their depth bits run as segments of ONE launch
         // of count_bitslice3_fused_kernel -- one pass over the table, one wave prologue / epilogue, whatever the mix of modes ----
         std::vector<bool> done(n_cls, false);
         uint32_t fused_launch_groups = 0;
-        if (c->tune_fuse && !all_swar) {
-            const uint32_t *order = nullptr;
-            for (uint32_t bb = 4; bb <= (uint32_t)kFusedMaxBits; ++bb) {
-                std::vector<uint32_t> ks;
-                for (uint32_t k = 0; k < n_cls; ++k) if (std::max(d.class_bits[k], 4u) == bb) ks.push_back(k);
-                // a lone binary_partial class at 4 or 5 bits takes the fused binary kernel too (with an empty binary_full segment): under the one
-                // dispatch it needs 123 VGPRs and spills nothing at 4 waves per SIMD, where the one-class instance is held to 128 with 6-24
-                // spilled: 512 taxa x 1500 trees with 10 % of the taxa dropped 64.95 -> 63.7 ms (profiles/r06_experiments.md 3)
-                const bool lone_bp4 = ks.size() == 1 && bb <= 5 && d.class_mode[ks[0]] == MODE_BINARY_PARTIAL;   // (5 bits: 4 waves instead of the one-class instance's 3)
-                if (ks.size() < 2 && !lone_bp4) continue;
-                if (!order) { int rc_o = tile_order(c, 0, &order); if (rc_o != QS_OK) return rc_o; }
-                struct Seg { uint32_t k, s_lo, trees, groups, mode, nw; bool part; size_t chunk_bytes; };
-                std::vector<Seg> segs;
-                uint32_t g_total = 0;
-                size_t max_chunk = 0;
-                for (uint32_t k : ks) {
-                    Seg sg;
-                    sg.k = k; sg.s_lo = k ? d.class_end[k - 1] : 0u; sg.trees = d.class_end[k] - sg.s_lo; sg.groups = (sg.trees + 31) / 32;
-                    sg.mode = d.class_mode[k]; sg.part = sg.mode == MODE_PARTIAL || sg.mode == MODE_BINARY_PARTIAL;
-                    sg.nw = bb + (sg.part ? 1u : 0u); sg.chunk_bytes = (size_t)binom2(c->n) * sg.nw * 4;
-                    g_total += sg.groups; max_chunk = std::max(max_chunk, sg.chunk_bytes);
-                    segs.push_back(sg);
-                }
-                const uint32_t per_slice = slice_groups(c, max_chunk, g_total, order != nullptr);
-                const size_t need = (size_t)per_slice * max_chunk + 256 * segs.size();
-                if (need > c->panel_bytes) {
-                    if (c->panel) { QS_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->panel); c->panel = nullptr; c->panel_bytes = 0; }
-                    if (hipMalloc(&c->panel, need) != hipSuccess) return fail(c, QS_ERR_OOM, "Insufficient memory! (pair-depth panel)");
-                    c->panel_bytes = need;
-                }
-                CountGeometry g3 = g;
-                g3.total_tiles = c->total_tiles3; g3.dprefix = c->dprefix3; g3.cprefix = c->cprefix3; g3.perm = order;
-                // slices of the concatenated group list [0, g_total): slice [g0, g1) takes from every class the groups that fall into it
-                for (uint32_t g0 = 0; g0 < g_total; g0 += per_slice) {
-                    const uint32_t g1 = std::min(g_total, g0 + per_slice);
-                    const void *seg_panel[4] = {nullptr, nullptr, nullptr, nullptr};
-                    uint32_t seg_groups[4] = {0, 0, 0, 0}, seg_trees[4] = {0, 0, 0, 0}, seg_slot[4] = {0, 0, 0, 0};
-                    size_t off = 0;
-                    uint32_t base = 0;
-                    for (const Seg &sg : segs) {
-                        const uint32_t a = std::max(g0, base), e_ = std::min(g1, base + sg.groups);
-                        base += sg.groups;
-                        if (a >= e_) continue;
-                        const uint32_t ga = a - (base - sg.groups), nch = e_ - a;
-                        const uint32_t t0 = ga * 32, nt = std::min(nch * 32, sg.trees - t0);
-                        DeviceBatch sub = d;
-                        sub.slot0 = sg.s_lo + t0;
-                        sub.n_trees = nt;
-                        void *pp = (char *)c->panel + off;
-                        QS_HIP(c, launch_build_bitpanel(c->stream, sub, c->n, sg.part, pp, nch, sg.nw, c->tune_panel_kernel == 1));
-                        seg_panel[sg.mode] = pp; seg_groups[sg.mode] = nch; seg_trees[sg.mode] = nt; seg_slot[sg.mode] = sub.slot0;
-                        off += ((size_t)nch * sg.chunk_bytes + 255) & ~(size_t)255;
-                    }
-                    if (timed) QS_HIP(c, mark(c, 0));
-                    QS_HIP(c, launch_count_bitslice3_fused(c->stream, g3, seg_panel, seg_groups, seg_trees, (int)bb, c->table, (int)c->count_bits, c->dev_flags, overwrite && first));
-                    first = false;
-                    if (timed) QS_HIP(c, mark(c, 1));
-                    if (d.n_fix) {
-                        bool any_fix = false;
-                        for (int mo = 0; mo < 4; ++mo)
-                            if (seg_groups[mo]) {   // (the rule of the correction depends on the mode: a tied quartet sits in the third cell of a binary tree)
-                                QS_HIP(c, clamp_fix_slots(c, b, seg_slot[mo], seg_slot[mo] + seg_trees[mo], mo, nullptr));
-                                any_fix = true;
-                            }
-                        if (timed && any_fix) QS_HIP(c, mark(c, 2));
-                    }
-                }
-                for (const Seg &sg : segs) {
-                    done[sg.k] = true;
-                    std::string nm = "bitslice_b" + std::to_string(bb) + "x2";          // (named as the class-by-class path names its classes)
-                    if (mixed) nm = std::string(mode_names[sg.mode]) + "." + nm;
-                    if (n_cls > 1) nm += ":" + std::to_string(sg.trees);
-                    names += (names.empty() ? "" : "+") + nm;
-                }
-                ++fused_launch_groups;
-            }
+        for (uint32_t bb = 4; c->tune_fuse && !all_swar && bb <= (uint32_t)kFusedMaxBits; ++bb) {
+            std::vector<uint32_t> ks;
+            for (uint32_t k = 0; k < n_cls; ++k) if (std::max(d.class_bits[k], 4u) == bb) ks.push_back(k);
+            // a lone binary_partial class at 4 or 5 bits takes the fused binary kernel too (with an empty binary_full segment): under the one
+            // dispatch it needs 123 VGPRs and spills nothing at 4 waves per SIMD, where the one-class instance is held to 128 with 6-24
+            // spilled: 512 taxa x 1500 trees with 10 % of the taxa dropped 64.95 -> 63.7 ms (profiles/r06_experiments.md 3)
+            const bool lone_bp4 = ks.size() == 1 && bb <= 5 && d.class_mode[ks[0]] == MODE_BINARY_PARTIAL;   // (5 bits: 4 waves instead of the one-class instance's 3)
+            if (ks.size() < 2 && !lone_bp4) continue;
+            Launch L{KERNEL_FUSED, (int)bb, {}};
+            for (uint32_t k : ks) { L.segs.push_back(bitslice_seg(c, slot_lo(k), d.class_end[k] - slot_lo(k), (int)d.class_mode[k], bb)); done[k] = true; }
+            const int rc = run_and_name(L);
+            if (rc != QS_OK) return rc;
+            ++fused_launch_groups;
         }
+        // ---- the other classes one by one: count_bitslice3_kernel on the compact panel, beyond its 10 depth bits the byte-SWAR kernel ----
         for (uint32_t k = 0; k < n_cls; ++k) {
             if (done[k]) continue;
-            const uint32_t s_lo = (all_swar || k == 0) ? 0u : d.class_end[k - 1], s_hi = all_swar ? d.n_trees : d.class_end[k];
+            const uint32_t s_lo = all_swar ? 0u : slot_lo(k), trees = (all_swar ? d.n_trees : d.class_end[k]) - s_lo;
             const uint32_t depth_bits = all_swar ? 11u : d.class_bits[k];   // 11 = beyond the bit-sliced instances
-            const uint32_t cls_max_depth = all_swar ? d.max_depth : d.class_max_depth[k];
-            const bool use_bitslice = depth_bits <= top_bits;
-            // the byte-SWAR kernel has no binary_partial instance: such trees are exact under its partial mode
             int mode = all_swar ? batch_mode : (int)d.class_mode[k];
-            if (!use_bitslice && mode == MODE_BINARY_PARTIAL) mode = MODE_PARTIAL;
-            const bool part = mode == MODE_PARTIAL || mode == MODE_BINARY_PARTIAL;           // panel elements carry a presence word
-            const bool bin_tiles = true;   // every instance of the bit-sliced kernel owns two a-columns per lane (16 a x 8 b tiles) since round 4
-            // bit-sliced classes run count_bitslice3_kernel on the compact panel
-            int bits = 8;
-            uint32_t tpc;            // trees per panel element
-            size_t elem_bytes;       // bytes per (pair, element)
-            const uint32_t compact_nw = std::max(depth_bits, 4u) + (part ? 1u : 0u); // words per compact panel element
-            if (use_bitslice) { tpc = 32; elem_bytes = compact_nw * 4; }
+            Launch L{KERNEL_BITSLICE3, (int)depth_bits, {}};
+            if (depth_bits <= top_bits) L.segs.push_back(bitslice_seg(c, s_lo, trees, mode, depth_bits));
             else {
-                const uint32_t lim8 = part ? kMaxDepthU8Partial : kMaxDepthU8Full;
-                const uint32_t lim16 = part ? kMaxDepthU16Partial : kMaxDepthU16Full;
-                if (cls_max_depth <= lim8) bits = 8;
-                else if (cls_max_depth <= lim16) bits = 16;
+                // the byte-SWAR kernel has no binary_partial instance: such trees are exact under its partial mode
+                if (mode == MODE_BINARY_PARTIAL) mode = MODE_PARTIAL;
+                const bool part = mode == MODE_PARTIAL;
+                const uint32_t cls_max_depth = all_swar ? d.max_depth : d.class_max_depth[k];
+                if (cls_max_depth <= (part ? kMaxDepthU8Partial : kMaxDepthU8Full)) L.bits = 8;
+                else if (cls_max_depth <= (part ? kMaxDepthU16Partial : kMaxDepthU16Full)) L.bits = 16;
                 else return fail(c, QS_ERR_UNSUPPORTED, "qs_count_batch: tree depth " + std::to_string(cls_max_depth) + " exceeds the panel range; re-root the tree at its centre");
-                tpc = 16 / (bits / 8); elem_bytes = 16;
+                L.kernel = KERNEL_SWAR;
+                L.segs.push_back(Seg{s_lo, trees, mode, part, 0u, 16u / (uint32_t)(L.bits / 8), (size_t)binom2(c->n) * 16});   // 16 bytes per (pair, group)
             }
-            const size_t chunk_bytes = (size_t)binom2(c->n) * elem_bytes;
-            const uint32_t n_chunks_total = (s_hi - s_lo + tpc - 1) / tpc;
-            const uint32_t *order = nullptr;   // launch order of the bit-sliced kernel's tiles for this class's tiling
-            if (use_bitslice) { int rc_o = tile_order(c, 0, &order); if (rc_o != QS_OK) return rc_o; }
-            const uint32_t chunks_per_slice = slice_groups(c, chunk_bytes, n_chunks_total, order != nullptr);
-            const size_t need = (size_t)chunks_per_slice * chunk_bytes;
-            if (need > c->panel_bytes) {
-                if (c->panel) { QS_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->panel); c->panel = nullptr; c->panel_bytes = 0; }
-                hipError_t e = hipMalloc(&c->panel, need);
-                if (e != hipSuccess) return fail(c, QS_ERR_OOM, "Insufficient memory! (pair-depth panel)");
-                c->panel_bytes = need;
-            }
-            for (uint32_t ch0 = 0; ch0 < n_chunks_total; ch0 += chunks_per_slice) {
-                const uint32_t nch = std::min(chunks_per_slice, n_chunks_total - ch0);
-                const uint32_t t0 = ch0 * tpc, nt = std::min(nch * tpc, s_hi - s_lo - t0);
-                DeviceBatch sub = d;
-                sub.slot0 = s_lo + t0;        // slots [slot0, slot0 + nt) of the class-ordered batch
-                sub.n_trees = nt;
-                if (use_bitslice) QS_HIP(c, launch_build_bitpanel(c->stream, sub, c->n, part, c->panel, nch, compact_nw, c->tune_panel_kernel == 1));
-                else QS_HIP(c, launch_build_panel(c->stream, sub, c->n, bits, part, c->panel, nch));
-                if (timed) QS_HIP(c, mark(c, 0));
-                if (use_bitslice) {
-                    CountGeometry g3 = g;
-                    if (bin_tiles) {
-                        g3.total_tiles = c->total_tiles3; g3.dprefix = c->dprefix3; g3.cprefix = c->cprefix3;
-                        if (mode == MODE_BINARY_FULL) { g3.perm_coop = c->perm_coop; g3.n_coop = c->n_coop; g3.perm_rest = c->perm_rest; g3.n_rest = c->n_rest; any_coop = any_coop || (c->n_coop && depth_bits <= 7); }   // (count_bitslice4_kernel carries at most 7 planes)
-                    }
-                    else { g3.total_tiles = c->total_tiles1t; g3.dprefix = c->dprefix1t; g3.cprefix = c->cprefix; }
-                    g3.perm = order;
-                    QS_HIP(c, launch_count_bitslice3(c->stream, g3, c->panel, (int)depth_bits, mode, nch, nt, c->table, (int)c->count_bits, c->dev_flags, overwrite && first, nullptr));
-                }
-                else QS_HIP(c, launch_count_gather(c->stream, g, c->panel, bits, mode, nch, nt, c->table, (int)c->count_bits, c->dev_flags, overwrite && first));
-                first = false;
-                if (timed) QS_HIP(c, mark(c, 1));
-                if (use_bitslice && d.n_fix) {   // (never with QS_IMPL_SWAR: the byte panel holds the trees' own depths)
-                    QS_HIP(c, clamp_fix_slots(c, b, sub.slot0, sub.slot0 + nt, mode, nullptr));
-                    if (timed) QS_HIP(c, mark(c, 2));
-                }
-            }
-            // kernel variant of the class; several classes: "a:trees+b:trees", classes of several modes: "mode.a:trees+..."
-            std::string nm = use_bitslice ? "bitslice_b" + std::to_string(std::max(depth_bits, 4u)) + (bin_tiles ? "x2" : "")
-                                          : "depth_u" + std::to_string(bits);
-            if (mixed) nm = std::string(mode_names[mode]) + "." + nm;
-            if (n_cls > 1) nm += ":" + std::to_string(s_hi - s_lo);
-            names += (names.empty() ? "" : "+") + nm;
+            const int rc = run_and_name(L);
+            if (rc != QS_OK) return rc;
+            // tiles with two a-blocks of binary_full classes: count_bitslice4_kernel (it carries at most 7 planes)
+            any_coop = any_coop || (L.kernel == KERNEL_BITSLICE3 && mode == MODE_BINARY_FULL && c->n_coop && depth_bits <= 7);
         }
         const int one_mode = all_swar ? batch_mode : (int)d.class_mode[0];
         c->variant = std::string("gather/") + (mixed ? "mixed" : mode_names[(!all_swar && d.class_bits[0] > top_bits && one_mode == MODE_BINARY_PARTIAL) ? (int)MODE_PARTIAL : one_mode]) + "/" + names + "/count_u" + std::to_string(c->count_bits);
         if (fused_launch_groups) c->variant += "/fused:" + std::to_string(fused_launch_groups);   // depth-bits groups whose classes shared a launch (count_bitslice3_fused_kernel)
-        if (any_coop) c->variant += "/coop4";   // tiles with two a-blocks of binary_full classes: count_bitslice4_kernel
+        if (any_coop) c->variant += "/coop4";
         if (!all_swar && d.n_fix) c->variant += "/clamp:" + std::to_string(d.clamped_trees);   // trees counted below their own depth bits + clamp_fix_kernel
     } else if (algo == QS_ALGO_SCATTER) {
         if (!d.node_off) return fail(c, QS_ERR_ARG, "qs_count_batch: QS_ALGO_SCATTER needs node_off/rng_off/ranges in the batch");
