@@ -5,6 +5,7 @@
 // work runs in the HIP kernels of qs_count.hip / qs_score.hip. There is no CPU fallback.
 #include "../../include/quartetscores_hip.h"
 #include "qs_common.hpp"
+#include "qs_devbuf.hpp"
 #include "qs_internal.hpp"
 
 #include <algorithm>
@@ -16,6 +17,7 @@
 #include <cstring>
 #include <future>
 #include <limits>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -53,19 +55,19 @@ struct qs_ctx {
     hipStream_t stream = nullptr;
     uint32_t d_lo = 0, d_hi = 0;
     uint64_t rank_lo = 0, n_tuples = 0;
-    void *table = nullptr;
-    bool table_owned = false;
+    void *table = nullptr;          // the context's own (table_mem) or the caller's (qs_table_attach)
+    DevBuf<void> table_mem;         // qs_table_alloc
     uint64_t trees_counted = 0;
     uint32_t *wire_out = nullptr;   // qs_wire_attach: destination of QS_COUNT_WIRE16X2 (one word per tuple)
     uint64_t wire_trees = 0;        // trees accumulated in it
     // geometry
-    uint32_t *dprefix = nullptr, *cprefix = nullptr;
+    DevBuf<uint32_t> dprefix, cprefix;
     uint32_t n_dblk = 0, total_tiles = 0;
-    uint32_t *dprefix3 = nullptr, *cprefix3 = nullptr; // tiling of count_bitslice3_kernel, every mode (16x8 tiles, d-blocks counted down from d_hi)
+    DevBuf<uint32_t> dprefix3, cprefix3; // tiling of count_bitslice3_kernel, every mode (16x8 tiles, d-blocks counted down from d_hi)
     uint32_t total_tiles3 = 0;
     // (a,b)-major launch order of count_bitslice3_kernel's tiles (tile_order below): launch slot -> tile id, built on
-    // first use. NULL = (d,c)-major (identity).
-    uint32_t *perm = nullptr;
+    // first use. Empty = (d,c)-major (identity).
+    DevBuf<uint32_t> perm;
     bool perm_built = false;
     std::future<EarlyPerm> perm_early;                 // the launch order, started by qs_create before its first HIP call
     uint32_t tile_chunk = 2, tile_cblock = 32;         // a-block (pairs) per chunk / c values per c-block; chunk 0 = (d,c)-major (round 3: 4 | 16 -> 2 | 32, -1.5 %)
@@ -73,14 +75,13 @@ struct qs_ctx {
     // binary tiling, cooperative workgroups (count_bitslice4_kernel): launch slots in groups of 4 tiles of one (a-blocks,
     // b-block, d-block) with consecutive c (bit 31 = shadow tile: takes part, does not store), and the list of the tiles
     // that stay with count_bitslice3_kernel (diagonal tiles, tiles without a second a-block)
-    uint32_t *perm_coop = nullptr, *perm_rest = nullptr;
+    DevBuf<uint32_t> perm_coop, perm_rest;
     uint32_t n_coop = 0, n_rest = 0;
     uint32_t tune_coop = 0;                            // QS_TUNE_COOP: 1 = cooperative workgroups on; 0 / 2 = off (the default: measured slower)
     std::vector<uint32_t> h_cp3, h_dp3;                // host copies of the prefix arrays
     // workspace
-    void *panel = nullptr;
-    size_t panel_bytes = 0;
-    uint32_t *dev_flags = nullptr; // [0] counter overflow, [1] score flags, [3] two-cell wire format: tuple sum mismatch
+    DevBuf<void> panel;
+    DevBuf<uint32_t> dev_flags; // [0] counter overflow, [1] score flags, [3] two-cell wire format: tuple sum mismatch
     std::vector<hipEvent_t> evs;   // QS_COUNT_TIMED: evs[0] = start, then one event after every kernel launch
     std::vector<uint8_t> ev_kind;  // per event after evs[0]: 0 = panel build, 1 = count kernel, 2 = depth-clamp corrections (clamp_fix_kernel)
     uint32_t ev_used = 0;
@@ -92,7 +93,7 @@ struct qs_ctx {
     uint32_t tune_cand_slots = kCand;  // candidate slots pass 2 fills per node pair (tests force overflows with fewer)
     int tune_score_kernel = 0;         // 0 = bundle kernel, 1 = scan kernel (QS_TUNE_SCORE_KERNEL)
     double tune_score_tol = 1e-12;     // pass 2 keeps triples whose device QIC is within this of the pair's minimum
-    double *dev_logk = nullptr;    // log(k) table of the device QIC (qs_score.hip), tbl_n entries
+    DevBuf<double> dev_logk;       // log(k) table of the device QIC (qs_score.hip), tbl_n entries
     uint32_t tbl_n = 0;
     // scoring view (qs_score_set_view): tuples [view_rank_lo, view_rank_lo + view_n) in caller-owned device memory
     const void *view_table = nullptr;
@@ -102,20 +103,19 @@ struct qs_ctx {
     std::string err;
     // the flattened reference tree of the last scoring call, its LCA matrix on the device (qs_score_pass1 / pass2 /
     // raw_qic / finish of one scoring run all get the same tree: built once, not three times)
-    RefHost *ref_cache = nullptr;
-    uint32_t *ref_lca_dev = nullptr;
-    uint16_t *ref_next_dev = nullptr;
-    void *root_pairs_dev = nullptr;
+    std::unique_ptr<RefHost> ref_cache;
+    DevBuf<uint32_t> ref_lca_dev;
+    DevBuf<uint16_t> ref_next_dev;
+    DevBuf<void> root_pairs_dev;
     BundlePlan bundle[3];              // rounds of the score bundle kernel in pass 1 / pass 2 for [bundle_r0, bundle_r1) (plan_bundles); [2]: qs_taxon_support
     uint64_t bundle_r0[3] = {~0ull, ~0ull, ~0ull}, bundle_r1[3] = {~0ull, ~0ull, ~0ull};
-    uint32_t *bundle_dev[3] = {nullptr, nullptr, nullptr};    // plo[n] | pcnt[n] | rounds[2 R]
+    DevBuf<uint32_t> bundle_dev[3];    // plo[n] | pcnt[n] | rounds[2 R]
     int n_cu = 0;
     // tree batches go to the device through two pinned staging buffers on a copy stream of their own:
     // qs_batch_upload returns once the batch is in pinned memory, the copy of batch k+1 overlaps the counting of batch k
     hipStream_t copy_stream = nullptr;
     hipStream_t prep_stream = nullptr;           // qs_score_prepare: uploads of the scoring set-up go here instead of `stream` (which may hold count kernels)
-    void *pin[2] = {nullptr, nullptr};
-    size_t pin_cap[2] = {0, 0};
+    PinBuf<void> pin[2];
     hipEvent_t pin_ev[2] = {nullptr, nullptr};   // recorded after the last copy out of the buffer
     unsigned pin_next = 0;
     std::vector<BatchSlab> slabs;                // device slabs of freed batches, for the next uploads
@@ -124,15 +124,15 @@ struct qs_ctx {
     hipEvent_t score_ev[3] = {nullptr, nullptr, nullptr};
     uint64_t table_trees_hint = 0;               // QS_TUNE_TABLE_TREES: trees behind an attached / uploaded / viewed table
     // single-read scoring (qs_score): pass 1 logs candidate (node pair, triple) records, score_log_kernel filters them
-    unsigned long long *score_log = nullptr;     // log_cap records of 4 words + 1 word counter behind them
-    uint64_t score_log_cap = 0, score_log_pairs = 0;
+    DevBuf<unsigned long long> score_log;        // log_cap records of 4 words + 1 word counter behind them
+    uint64_t score_log_cap = 0;
     bool log_valid = false;                      // the candidate log holds the last qs_score_pass1 of (log_table, log_rank_lo, log_n_tuples, log_ref)
     const void *log_table = nullptr, *log_ref = nullptr;
     uint64_t log_rank_lo = 0, log_n_tuples = 0;
     double log_tol = 0.0;
     uint32_t tune_score_passes = 0;              // QS_TUNE_SCORE_PASSES: 0 = automatic (default), 1 = two passes over the table, 2 = single read
-    void *score_acc = nullptr, *score_acc_host = nullptr;   // qs_score's accumulators on the device + their pinned host copy (cached)
-    size_t score_acc_cap = 0, score_acc_host_cap = 0;
+    DevBuf<void> score_acc;                      // qs_score's accumulators on the device + their pinned host copy (cached)
+    PinBuf<void> score_acc_host;
     uint64_t last_score_estimate = 0;            // automatic single-read mode: predicted log records of the last qs_score (sample x S)
     uint64_t last_score_log = 0;                 // records the last single-read qs_score logged (0 = two passes were used)
     uint32_t tune_class_min = 1024;              // QS_TUNE_CLASS_MIN_TREES
@@ -143,13 +143,13 @@ struct qs_ctx {
     uint32_t tune_score_dedupe = 1;              // QS_TUNE_SCORE_DEDUPE: the logging pass skips a quartet that repeats its node pair's last logged triple
     uint32_t tune_score_sample = 64u | 65536u;             // QS_TUNE_SCORE_SAMPLE: pre-pass of the single-read scoring (0 = none; S | by-round bit 16)
     uint64_t tune_score_log_cap = 0;             // QS_TUNE_SCORE_LOG_CAP: records the log may hold (0 = 8 M); tests force overflows
-    uint16_t *remap_ids = nullptr;               // qs_table_remap: src_id_of on the device (n entries)
+    DevBuf<uint16_t> remap_ids;                  // qs_table_remap: src_id_of on the device (n entries)
     // qs_tree_agreement: the reference tree's inner nodes (>= 3 links) as id boundaries on the device, and the tree they came from
     std::vector<int32_t> agree_parent;
     std::vector<uint32_t> agree_leaf_node;
-    uint32_t *agree_off = nullptr;
-    uint16_t *agree_bnd = nullptr;
-    uint8_t *agree_par = nullptr;
+    DevBuf<uint32_t> agree_off;
+    DevBuf<uint16_t> agree_bnd;
+    DevBuf<uint8_t> agree_par;
     uint32_t agree_n_u = 0;
 };
 
@@ -292,7 +292,7 @@ static bool build_tile_perm(const TilePermParams &P, const std::vector<uint32_t>
 
 static int tile_order(qs_ctx *c, const uint32_t **out) {
     *out = nullptr;
-    if (c->perm_built) { *out = c->perm; return QS_OK; }
+    if (c->perm_built) { *out = c->perm.get(); return QS_OK; }
     c->perm_built = true;
     const uint32_t total = c->total_tiles3;
     const uint32_t chunk = c->tile_chunk;
@@ -364,18 +364,27 @@ static int tile_order(qs_ctx *c, const uint32_t **out) {
             if (real != total || coop.size() % 4) return fail(c, QS_ERR_STATE, "tile order: cooperative + rest lists do not cover the tiling");
         }
         if (!coop.empty()) {
-            if (hipMalloc(&c->perm_coop, coop.size() * 4) != hipSuccess || hipMalloc(&c->perm_rest, std::max<size_t>(rest.size(), 1) * 4) != hipSuccess)
+            if (c->perm_coop.reserve(coop.size() * 4, nullptr) != hipSuccess || c->perm_rest.reserve(std::max<size_t>(rest.size(), 1) * 4, nullptr) != hipSuccess)
                 return fail(c, QS_ERR_OOM, "hipMalloc tile order (cooperative lists)");
-            if (hipMemcpyAsync(c->perm_coop, coop.data(), coop.size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-                (!rest.empty() && hipMemcpyAsync(c->perm_rest, rest.data(), rest.size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
+            if (hipMemcpyAsync(c->perm_coop.get(), coop.data(), coop.size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                (!rest.empty() && hipMemcpyAsync(c->perm_rest.get(), rest.data(), rest.size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
                 hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, QS_ERR_HIP, "memcpy tile order (cooperative lists)");
             c->n_coop = (uint32_t)coop.size(); c->n_rest = (uint32_t)rest.size();
         }
     }
-    if (hipMalloc(&c->perm, perm.size() * 4) != hipSuccess) return fail(c, QS_ERR_OOM, "hipMalloc tile order");
-    if (hipMemcpyAsync(c->perm, perm.data(), perm.size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+    if (c->perm.reserve(perm.size() * 4, nullptr) != hipSuccess) return fail(c, QS_ERR_OOM, "hipMalloc tile order");
+    if (hipMemcpyAsync(c->perm.get(), perm.data(), perm.size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, QS_ERR_HIP, "memcpy tile order");
-    *out = c->perm;
+    *out = c->perm.get();
+    return QS_OK;
+}
+
+// The launch-order lists depend on the tile-order tuning and on QS_TUNE_COOP: dropped here, tile_order rebuilds them on next use.
+static int drop_tile_order(qs_ctx *c) {
+    QS_HIP(c, hipSetDevice(c->device));
+    QS_HIP(c, hipStreamSynchronize(c->stream));
+    c->perm.reset(); c->perm_coop.reset(); c->perm_rest.reset();
+    c->perm_built = false; c->n_coop = c->n_rest = 0;
     return QS_OK;
 }
 
@@ -393,13 +402,7 @@ extern "C" int qs_set_tuning(qs_ctx *c, uint32_t key, uint64_t value) {
             if (value < 1 || value > 15) return fail(c, QS_ERR_ARG, "qs_set_tuning: QS_TUNE_SCORE_TOL_EXP takes 1..15 (tolerance 10^-value)");
             c->tune_score_tol = std::pow(10.0, -(double)value); return QS_OK;
         case QS_TUNE_TILE_ORDER:
-            QS_HIP(c, hipSetDevice(c->device));
-            QS_HIP(c, hipStreamSynchronize(c->stream));
-            if (c->perm) (void)hipFree(c->perm);
-            c->perm = nullptr; c->perm_built = false;
-            if (c->perm_coop) (void)hipFree(c->perm_coop);
-            if (c->perm_rest) (void)hipFree(c->perm_rest);
-            c->perm_coop = c->perm_rest = nullptr; c->n_coop = c->n_rest = 0;
+            if (int rc = drop_tile_order(c)) return rc;
             c->tile_chunk = (uint32_t)(value & 0xFFFF); c->tile_cblock = (uint32_t)((value >> 16) & 0xFFFF); c->tile_cgroup = (uint32_t)((value >> 32) & 0xFF);
             return QS_OK;
         case QS_TUNE_PANEL_SLICE_BYTES: c->tune_slice_bytes = value; return QS_OK;
@@ -427,15 +430,8 @@ extern "C" int qs_set_tuning(qs_ctx *c, uint32_t key, uint64_t value) {
             c->tune_score_passes = (uint32_t)value; return QS_OK;
         case QS_TUNE_COOP:
             if (value > 2) return fail(c, QS_ERR_ARG, "qs_set_tuning: QS_TUNE_COOP takes 0 (default: off), 1 (on) or 2 (off)");
-            if (c->tune_coop != (uint32_t)value) {   // the launch lists depend on it: rebuild on next use
-                QS_HIP(c, hipSetDevice(c->device));
-                QS_HIP(c, hipStreamSynchronize(c->stream));
-                if (c->perm) (void)hipFree(c->perm);
-                c->perm = nullptr; c->perm_built = false;
-                if (c->perm_coop) (void)hipFree(c->perm_coop);
-                if (c->perm_rest) (void)hipFree(c->perm_rest);
-                c->perm_coop = c->perm_rest = nullptr; c->n_coop = c->n_rest = 0;
-            }
+            if (c->tune_coop != (uint32_t)value)
+                if (int rc = drop_tile_order(c)) return rc;
             c->tune_coop = (uint32_t)value; return QS_OK;
         case QS_TUNE_GATHER_IMPL:
             if (value > QS_IMPL_BITSLICE) return fail(c, QS_ERR_ARG, "qs_set_tuning: QS_TUNE_GATHER_IMPL takes QS_IMPL_AUTO / _SWAR / _BITSLICE");
@@ -511,51 +507,31 @@ extern "C" int qs_create(qs_ctx **out, uint32_t n_taxa, uint32_t count_bits, uin
     if (device < 0 || device >= ndev) { delete c; return fail(nullptr, QS_ERR_ARG, "qs_create: bad device ordinal"); }
     if (hipSetDevice(device) != hipSuccess) { delete c; return fail(nullptr, QS_ERR_HIP, "qs_create: hipSetDevice"); }
     auto cleanup = [&](int code, const std::string &m) { qs_destroy(c); return fail(nullptr, code, m); };
-    if (hipMalloc(&c->cprefix, cp.size() * 4) != hipSuccess) return cleanup(QS_ERR_OOM, "hipMalloc cprefix");
-    if (hipMalloc(&c->dprefix, dp.size() * 4) != hipSuccess) return cleanup(QS_ERR_OOM, "hipMalloc dprefix");
-    if (hipMemcpy(c->cprefix, cp.data(), cp.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return cleanup(QS_ERR_HIP, "memcpy cprefix");
-    if (hipMemcpy(c->dprefix, dp.data(), dp.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return cleanup(QS_ERR_HIP, "memcpy dprefix");
-    if (hipMalloc(&c->cprefix3, cp3.size() * 4) != hipSuccess) return cleanup(QS_ERR_OOM, "hipMalloc cprefix3");
-    if (hipMalloc(&c->dprefix3, dp3.size() * 4) != hipSuccess) return cleanup(QS_ERR_OOM, "hipMalloc dprefix3");
-    if (hipMemcpy(c->cprefix3, cp3.data(), cp3.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return cleanup(QS_ERR_HIP, "memcpy cprefix3");
-    if (hipMemcpy(c->dprefix3, dp3.data(), dp3.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return cleanup(QS_ERR_HIP, "memcpy dprefix3");
-    if (hipMalloc(&c->dev_flags, 16) != hipSuccess) return cleanup(QS_ERR_OOM, "hipMalloc flags");
-    if (hipMemset(c->dev_flags, 0, 16) != hipSuccess) return cleanup(QS_ERR_HIP, "memset flags");
+    if (c->cprefix.reserve(cp.size() * 4, nullptr) != hipSuccess) return cleanup(QS_ERR_OOM, "hipMalloc cprefix");
+    if (c->dprefix.reserve(dp.size() * 4, nullptr) != hipSuccess) return cleanup(QS_ERR_OOM, "hipMalloc dprefix");
+    if (hipMemcpy(c->cprefix.get(), cp.data(), cp.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return cleanup(QS_ERR_HIP, "memcpy cprefix");
+    if (hipMemcpy(c->dprefix.get(), dp.data(), dp.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return cleanup(QS_ERR_HIP, "memcpy dprefix");
+    if (c->cprefix3.reserve(cp3.size() * 4, nullptr) != hipSuccess) return cleanup(QS_ERR_OOM, "hipMalloc cprefix3");
+    if (c->dprefix3.reserve(dp3.size() * 4, nullptr) != hipSuccess) return cleanup(QS_ERR_OOM, "hipMalloc dprefix3");
+    if (hipMemcpy(c->cprefix3.get(), cp3.data(), cp3.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return cleanup(QS_ERR_HIP, "memcpy cprefix3");
+    if (hipMemcpy(c->dprefix3.get(), dp3.data(), dp3.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return cleanup(QS_ERR_HIP, "memcpy dprefix3");
+    if (c->dev_flags.reserve(16, nullptr) != hipSuccess) return cleanup(QS_ERR_OOM, "hipMalloc flags");
+    if (hipMemset(c->dev_flags.get(), 0, 16) != hipSuccess) return cleanup(QS_ERR_HIP, "memset flags");
     *out = c;
     return QS_OK;
 }
 
+// Every device and pinned buffer of the context is a DevBuf member and goes with `delete c`; what is left to do by hand is what
+// has to happen before: wait for the copies out of the staging buffers, and release what the slab cache holds (BatchSlab is a
+// plain struct shared with the launch code).
 extern "C" void qs_destroy(qs_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->table && c->table_owned) (void)hipFree(c->table);
-    if (c->panel) (void)hipFree(c->panel);
-    if (c->dprefix) (void)hipFree(c->dprefix);
-    if (c->cprefix) (void)hipFree(c->cprefix);
-    if (c->dprefix3) (void)hipFree(c->dprefix3);
-    if (c->perm) (void)hipFree(c->perm);
-    if (c->perm_coop) (void)hipFree(c->perm_coop);
-    if (c->perm_rest) (void)hipFree(c->perm_rest);
-    if (c->dev_logk) (void)hipFree(c->dev_logk);
-    if (c->cprefix3) (void)hipFree(c->cprefix3);
-    if (c->dev_flags) (void)hipFree(c->dev_flags);
     for (hipEvent_t e : c->evs) (void)hipEventDestroy(e);
-    if (c->ref_lca_dev) (void)hipFree(c->ref_lca_dev);
-    if (c->ref_next_dev) (void)hipFree(c->ref_next_dev);
-    if (c->root_pairs_dev) (void)hipFree(c->root_pairs_dev);
-    for (int w = 0; w < 3; ++w) if (c->bundle_dev[w]) (void)hipFree(c->bundle_dev[w]);
-    for (int w = 0; w < 2; ++w) { if (c->pin_ev[w]) { (void)hipEventSynchronize(c->pin_ev[w]); (void)hipEventDestroy(c->pin_ev[w]); } if (c->pin[w]) (void)hipHostFree(c->pin[w]); }
+    for (hipEvent_t e : c->pin_ev) if (e) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    for (BatchSlab &sl : c->slabs) { (void)hipFree(sl.p); if (sl.last_use) (void)hipEventDestroy(sl.last_use); }
     for (hipEvent_t e : c->score_ev) if (e) (void)hipEventDestroy(e);
-    if (c->score_log) (void)hipFree(c->score_log);
-    if (c->score_acc) (void)hipFree(c->score_acc);
-    if (c->score_acc_host) (void)hipHostFree(c->score_acc_host);
-    if (c->remap_ids) (void)hipFree(c->remap_ids);
-    if (c->agree_off) (void)hipFree(c->agree_off);
-    if (c->agree_bnd) (void)hipFree(c->agree_bnd);
-    if (c->agree_par) (void)hipFree(c->agree_par);
-    delete c->ref_cache;
+    for (BatchSlab &sl : c->slabs) { (void)hipFree(sl.p); if (sl.last_use) (void)hipEventDestroy(sl.last_use); }
     delete c;
 }
 
@@ -564,7 +540,12 @@ extern "C" void qs_destroy(qs_ctx *c) {
 // kernel for binary batches (12 M slots at 512 taxa: ~60 ms of host work + a 47 MB copy) and the pair-depth panel for a
 // batch of n_trees_hint trees. Purely an optimisation: qs_count_batch builds whatever is missing. The reference does the
 // equivalent set-up in the table's constructor (QuartetCounterLookup.hpp:245-273).
-static size_t Stager_padded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }   // = Stager::padded (batches, below)
+static size_t padded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }   // the pieces of a staged batch start at 256-byte boundaries (Stager, below)
+// pinned staging buffer `slot` holds `need` bytes, with a quarter to spare when it has to grow (nothing reads it then: the
+// caller has waited for pin_ev[slot], or it has never been used)
+static hipError_t ensure_pinned(qs_ctx *c, int slot, size_t need) {
+    return c->pin[slot].bytes() >= need ? hipSuccess : c->pin[slot].reserve(need + need / 4 + 4096, nullptr);
+}
 static int prepare_staging(qs_ctx *c, uint64_t n_trees_hint);
 extern "C" int qs_prepare(qs_ctx *c, uint64_t n_trees_hint) {
     if (!c) return QS_ERR_ARG;
@@ -580,11 +561,10 @@ extern "C" int qs_prepare(qs_ctx *c, uint64_t n_trees_hint) {
     const uint32_t *order = nullptr;
     int rc = tile_order(c, &order);
     if (rc != QS_OK) return rc;
-    if (n_trees_hint && !c->panel) {
+    if (n_trees_hint && !c->panel) {   // (no stream to wait for: there is no panel yet)
         const size_t group_bytes = (size_t)binom2(c->n) * 5 * 4;   // 5 planes: the common depth class
         const uint32_t groups = slice_groups(c, group_bytes, (uint32_t)std::min<uint64_t>((n_trees_hint + 31) / 32, 1u << 20), order != nullptr);
-        if (hipMalloc(&c->panel, (size_t)groups * group_bytes) == hipSuccess) c->panel_bytes = (size_t)groups * group_bytes;
-        else { c->panel = nullptr; (void)hipGetLastError(); }       // not fatal here: the count reports it if it persists
+        if (c->panel.reserve((size_t)groups * group_bytes, nullptr) != hipSuccess) (void)hipGetLastError();   // not fatal here: the count reports it if it persists
     }
     return QS_OK;
 }
@@ -594,15 +574,10 @@ static int prepare_staging(qs_ctx *c, uint64_t n_trees_hint) {
         // both pinned staging buffers and one device slab for batches of that many full trees (qs_batch_upload's Stager
         // would allocate them on first use: hipHostMalloc + hipMalloc, tens of ms in front of the first count)
         const uint64_t nt = std::min<uint64_t>(n_trees_hint, 1u << 22);
-        const size_t need = Stager_padded(((size_t)nt + 1) * 4) + 2 * Stager_padded((size_t)nt * c->n * 2) + Stager_padded((size_t)nt * 4);
+        const size_t need = padded(((size_t)nt + 1) * 4) + 2 * padded((size_t)nt * c->n * 2) + padded((size_t)nt * 4);
         if (!c->copy_stream && hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess) { c->copy_stream = nullptr; (void)hipGetLastError(); return QS_ERR_HIP; }
         for (int slot = 0; slot < 2; ++slot)
-            if (c->pin_cap[slot] < need) {
-                if (c->pin[slot]) { (void)hipHostFree(c->pin[slot]); c->pin[slot] = nullptr; c->pin_cap[slot] = 0; }
-                const size_t cap = need + need / 4 + 4096;
-                if (hipHostMalloc(&c->pin[slot], cap, hipHostMallocDefault) == hipSuccess) c->pin_cap[slot] = cap;
-                else { c->pin[slot] = nullptr; (void)hipGetLastError(); }
-            }
+            if (ensure_pinned(c, slot, need) != hipSuccess) (void)hipGetLastError();   // (the first upload asks again and reports it)
         bool have = false;
         for (const BatchSlab &sl : c->slabs) have = have || sl.cap >= need;
         if (!have && c->slabs.size() < 4) {
@@ -614,14 +589,13 @@ static int prepare_staging(qs_ctx *c, uint64_t n_trees_hint) {
     // first use of the count kernels' code object (~5 ms of loading on MI355X: tools/modload_probe.py) here, beside the launch
     // order, instead of in front of the first count: one lookup of the quartet {0,1,2,3} on the copy stream
     if (c->table && c->n >= 4 && c->d_lo == 0) {
-        void *scratch = nullptr;
-        if (hipMalloc(&scratch, 64) == hipSuccess) {
+        DevBuf<char> scratch;
+        if (scratch.reserve(64, nullptr) == hipSuccess) {
             const uint16_t ids[4] = {0, 1, 2, 3};
-            if (hipMemcpyAsync(scratch, ids, sizeof ids, hipMemcpyHostToDevice, c->copy_stream) == hipSuccess)
-                (void)launch_lookup(c->copy_stream, c->n, c->d_lo, c->d_hi, c->rank_lo, c->table, (int)c->count_bits, 1, (const uint16_t *)scratch,
-                                    (uint64_t *)((char *)scratch + 16));
+            if (hipMemcpyAsync(scratch.get(), ids, sizeof ids, hipMemcpyHostToDevice, c->copy_stream) == hipSuccess)
+                (void)launch_lookup(c->copy_stream, c->n, c->d_lo, c->d_hi, c->rank_lo, c->table, (int)c->count_bits, 1, (const uint16_t *)scratch.get(),
+                                    (uint64_t *)(scratch.get() + 16));
             (void)hipStreamSynchronize(c->copy_stream);
-            (void)hipFree(scratch);
         }
         (void)hipGetLastError();
     }
@@ -639,14 +613,13 @@ extern "C" int qs_table_alloc(qs_ctx *c) {
     if (c) c->log_valid = false;   // (the table / view / tuning may change: a logged pass 1 no longer describes it)
     if (!c) return QS_ERR_ARG;
     QS_HIP(c, hipSetDevice(c->device));
-    if (c->table && c->table_owned) { (void)hipFree(c->table); c->table = nullptr; }
+    if (c->table_mem) { c->table_mem.reset(); c->table = nullptr; }
     size_t bytes = (size_t)qs_table_bytes(c);
     size_t freeb = 0, total = 0;
     QS_HIP(c, hipMemGetInfo(&freeb, &total));
     if (bytes + (64u << 20) > freeb) return fail(c, QS_ERR_OOM, "Insufficient memory!");
-    hipError_t e = hipMalloc(&c->table, bytes + 16);
-    if (e != hipSuccess) { c->table = nullptr; return fail(c, QS_ERR_OOM, "Insufficient memory!"); }
-    c->table_owned = true;
+    if (c->table_mem.reserve(bytes + 16, nullptr) != hipSuccess) { c->table = nullptr; return fail(c, QS_ERR_OOM, "Insufficient memory!"); }
+    c->table = c->table_mem.get();
     c->trees_counted = 0;
     QS_HIP(c, hipMemsetAsync(c->table, 0, bytes + 16, c->stream));
     return QS_OK;
@@ -658,10 +631,10 @@ extern "C" int qs_table_attach(qs_ctx *c, void *device_ptr, uint64_t bytes) {
     if (!device_ptr) {
         // detach: the caller takes its buffer back (e.g. to free a full table once its reduce-scattered shard is the scoring view)
         if (bytes != 0) return fail(c, QS_ERR_ARG, "qs_table_attach: NULL pointer with a size (detach = NULL, 0)");
-        if (c->table && c->table_owned) return fail(c, QS_ERR_STATE, "qs_table_attach: detach of a table the context owns (qs_table_alloc)");
+        if (c->table_mem) return fail(c, QS_ERR_STATE, "qs_table_attach: detach of a table the context owns (qs_table_alloc)");
         QS_HIP(c, hipSetDevice(c->device));
         QS_HIP(c, hipStreamSynchronize(c->stream));   // nothing of this context may still be writing the buffer
-        c->table = nullptr; c->table_owned = false;
+        c->table = nullptr;
         return QS_OK;
     }
     // 16-bit cells are updated through their 32-bit word (packed half-word atomics of the scatter kernel, word-wise
@@ -669,9 +642,8 @@ extern "C" int qs_table_attach(qs_ctx *c, void *device_ptr, uint64_t bytes) {
     const uint64_t need = (qs_table_bytes(c) + 3) & ~3ull;
     if (bytes < need) return fail(c, QS_ERR_ARG, "qs_table_attach: buffer smaller than qs_table_bytes() rounded up to a multiple of 4");
     if ((uintptr_t)device_ptr & 3) return fail(c, QS_ERR_ARG, "qs_table_attach: pointer must be 4-byte aligned");
-    if (c->table && c->table_owned) (void)hipFree(c->table);
+    c->table_mem.reset();   // (the context's own table, if it had one)
     c->table = device_ptr;
-    c->table_owned = false;
     return QS_OK;
 }
 
@@ -709,7 +681,7 @@ extern "C" int qs_table_pack16(qs_ctx *c, void *dst_device, uint64_t dst_bytes) 
     const uint64_t cells = c->n_tuples * 3, need = ((cells + 1) / 2) * 4;
     if (dst_bytes < need) return fail(c, QS_ERR_ARG, "qs_table_pack16: destination smaller than " + std::to_string(need) + " bytes");
     QS_HIP(c, hipSetDevice(c->device));
-    QS_HIP(c, launch_pack16(c->stream, c->table, dst_device, cells, c->dev_flags));
+    QS_HIP(c, launch_pack16(c->stream, c->table, dst_device, cells, c->dev_flags.get()));
     return QS_OK;
 }
 
@@ -729,7 +701,7 @@ extern "C" int qs_table_pack16x2(qs_ctx *c, void *dst_device, uint64_t dst_bytes
     if (c->trees_counted > 0xFFFFull) return fail(c, QS_ERR_OVERFLOW, "qs_table_pack16x2: more than 65535 trees counted");
     if (dst_bytes < c->n_tuples * 4) return fail(c, QS_ERR_ARG, "qs_table_pack16x2: destination smaller than " + std::to_string(c->n_tuples * 4) + " bytes");
     QS_HIP(c, hipSetDevice(c->device));
-    QS_HIP(c, launch_pack16x2(c->stream, c->table, dst_device, c->n_tuples, (uint32_t)c->trees_counted, c->dev_flags, c->dev_flags + 3));
+    QS_HIP(c, launch_pack16x2(c->stream, c->table, dst_device, c->n_tuples, (uint32_t)c->trees_counted, c->dev_flags.get(), c->dev_flags.get() + 3));
     return QS_OK;
 }
 
@@ -738,7 +710,7 @@ extern "C" int qs_unpack16x2(qs_ctx *c, const void *src_device, uint64_t n_tuple
     if (!c || !src_device || !dst_device) return fail(c, QS_ERR_ARG, "qs_unpack16x2: NULL argument");
     if (total_trees > 0xFFFFu) return fail(c, QS_ERR_OVERFLOW, "qs_unpack16x2: more than 65535 trees");
     QS_HIP(c, hipSetDevice(c->device));
-    QS_HIP(c, launch_unpack16x2(c->stream, src_device, dst_device, n_tuples, total_trees, c->dev_flags + 3));
+    QS_HIP(c, launch_unpack16x2(c->stream, src_device, dst_device, n_tuples, total_trees, c->dev_flags.get() + 3));
     return QS_OK;
 }
 
@@ -750,7 +722,7 @@ extern "C" int qs_table_pack32x2(qs_ctx *c, void *dst_device, uint64_t dst_bytes
     if (c->trees_counted > 0xFFFFFFFFull) return fail(c, QS_ERR_OVERFLOW, "qs_table_pack32x2: more than 2^32 - 1 trees counted");
     if (dst_bytes < c->n_tuples * 8) return fail(c, QS_ERR_ARG, "qs_table_pack32x2: destination smaller than " + std::to_string(c->n_tuples * 8) + " bytes");
     QS_HIP(c, hipSetDevice(c->device));
-    QS_HIP(c, launch_pack32x2(c->stream, c->table, dst_device, c->n_tuples, (uint32_t)c->trees_counted, c->dev_flags + 3));
+    QS_HIP(c, launch_pack32x2(c->stream, c->table, dst_device, c->n_tuples, (uint32_t)c->trees_counted, c->dev_flags.get() + 3));
     return QS_OK;
 }
 
@@ -759,7 +731,7 @@ extern "C" int qs_unpack32x2(qs_ctx *c, const void *src_device, uint64_t n_tuple
     if (!c || !src_device || !dst_device) return fail(c, QS_ERR_ARG, "qs_unpack32x2: NULL argument");
     if (total_trees > 0xFFFFFFFFull) return fail(c, QS_ERR_OVERFLOW, "qs_unpack32x2: more than 2^32 - 1 trees");
     QS_HIP(c, hipSetDevice(c->device));
-    QS_HIP(c, launch_unpack32x2(c->stream, src_device, dst_device, n_tuples, (uint32_t)total_trees, c->dev_flags + 3));
+    QS_HIP(c, launch_unpack32x2(c->stream, src_device, dst_device, n_tuples, (uint32_t)total_trees, c->dev_flags.get() + 3));
     return QS_OK;
 }
 
@@ -796,7 +768,7 @@ extern "C" int qs_table_remap(qs_ctx *dst, const qs_ctx *src, const uint16_t *sr
         seen[src_id_of[i]] = 1;
     }
     QS_HIP(dst, hipSetDevice(dst->device));
-    if (!dst->remap_ids) QS_HIP(dst, hipMalloc(&dst->remap_ids, 4096 * sizeof(uint16_t)));
+    QS_HIP(dst, dst->remap_ids.reserve(4096 * sizeof(uint16_t), nullptr));
     if (src->stream != dst->stream) {   // the source's counting (or upload) first
         hipEvent_t ev = nullptr;
         QS_HIP(dst, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -805,8 +777,8 @@ extern "C" int qs_table_remap(qs_ctx *dst, const qs_ctx *src, const uint16_t *sr
         (void)hipEventDestroy(ev);
         QS_HIP(dst, e);
     }
-    QS_HIP(dst, hipMemcpyAsync(dst->remap_ids, src_id_of, dst->n * sizeof(uint16_t), hipMemcpyHostToDevice, dst->stream));
-    QS_HIP(dst, launch_table_remap(dst->stream, src->table, (int)src->count_bits, dst->table, (int)dst->count_bits, dst->remap_ids, dst->n, dst->n_tuples));
+    QS_HIP(dst, hipMemcpyAsync(dst->remap_ids.get(), src_id_of, dst->n * sizeof(uint16_t), hipMemcpyHostToDevice, dst->stream));
+    QS_HIP(dst, launch_table_remap(dst->stream, src->table, (int)src->count_bits, dst->table, (int)dst->count_bits, dst->remap_ids.get(), dst->n, dst->n_tuples));
     dst->trees_counted = src->trees_counted;   // sizes the log table and the 16-bit overflow guard of later counts
     return QS_OK;   // asynchronous on dst's stream
 }
@@ -842,16 +814,15 @@ static int agree_ref_upload(qs_ctx *c, const qs_ref_tree *ref) {
     }
     QS_HIP(c, hipSetDevice(c->device));
     QS_HIP(c, hipStreamSynchronize(c->stream));   // kernels of this context may still read the previous tree's arrays
-    if (c->agree_off) { (void)hipFree(c->agree_off); c->agree_off = nullptr; }
-    if (c->agree_bnd) { (void)hipFree(c->agree_bnd); c->agree_bnd = nullptr; }
-    if (c->agree_par) { (void)hipFree(c->agree_par); c->agree_par = nullptr; }
+    // The cache key goes BEFORE the first buffer: whatever fails below, the next call finds no tree cached and builds all three anew.
     c->agree_parent.clear(); c->agree_leaf_node.clear();
-    QS_HIP(c, hipMalloc(&c->agree_off, off.size() * 4));
-    QS_HIP(c, hipMalloc(&c->agree_bnd, std::max<size_t>(bnd.size(), 1) * 2));
-    QS_HIP(c, hipMalloc(&c->agree_par, std::max<size_t>(par.size(), 1)));
-    QS_HIP(c, hipMemcpy(c->agree_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-    if (!bnd.empty()) QS_HIP(c, hipMemcpy(c->agree_bnd, bnd.data(), bnd.size() * 2, hipMemcpyHostToDevice));
-    if (!par.empty()) QS_HIP(c, hipMemcpy(c->agree_par, par.data(), par.size(), hipMemcpyHostToDevice));
+    c->agree_off.reset(); c->agree_bnd.reset(); c->agree_par.reset();   // (each tree gets arrays of its own size, as before)
+    QS_HIP(c, c->agree_off.reserve(off.size() * 4, nullptr));
+    QS_HIP(c, c->agree_bnd.reserve(std::max<size_t>(bnd.size(), 1) * 2, nullptr));
+    QS_HIP(c, c->agree_par.reserve(std::max<size_t>(par.size(), 1), nullptr));
+    QS_HIP(c, hipMemcpy(c->agree_off.get(), off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    if (!bnd.empty()) QS_HIP(c, hipMemcpy(c->agree_bnd.get(), bnd.data(), bnd.size() * 2, hipMemcpyHostToDevice));
+    if (!par.empty()) QS_HIP(c, hipMemcpy(c->agree_par.get(), par.data(), par.size(), hipMemcpyHostToDevice));
     c->agree_n_u = (uint32_t)par.size();
     c->agree_parent.assign(ref->parent, ref->parent + N);
     c->agree_leaf_node.assign(ref->leaf_node, ref->leaf_node + n);
@@ -869,7 +840,7 @@ extern "C" int qs_tree_agreement(qs_ctx *c, const qs_ref_tree *ref, const qs_dev
     if (d.n_trees && !d.node_off) return fail(c, QS_ERR_STATE, "qs_tree_agreement: the batch was uploaded without node ranges");
     QS_HIP(c, hipSetDevice(c->device));
     if (d.ready) QS_HIP(c, hipStreamWaitEvent(c->stream, d.ready, 0));
-    QS_HIP(c, launch_tree_agree(c->stream, d, c->n, d.max_tree_nodes, c->agree_off, c->agree_bnd, c->agree_par, c->agree_n_u,
+    QS_HIP(c, launch_tree_agree(c->stream, d, c->n, d.max_tree_nodes, c->agree_off.get(), c->agree_bnd.get(), c->agree_par.get(), c->agree_n_u,
                                 reinterpret_cast<unsigned long long *>(dst_device)));
     return QS_OK;   // asynchronous on the context's stream
 }
@@ -912,8 +883,9 @@ extern "C" int qs_issue_probe(qs_ctx *c, uint32_t iterations, float *ns_per_inst
     QS_HIP(c, hipSetDevice(c->device));
     if (c->n_cu == 0) { int v = 0; QS_HIP(c, hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device)); c->n_cu = std::max(1, v); }
     const uint32_t blocks = (uint32_t)c->n_cu * 4u;              // 4 workgroups of 4 waves per CU = 4 waves per SIMD
-    uint32_t *buf = nullptr;
-    QS_HIP(c, hipMalloc((void **)&buf, (1024 + (size_t)blocks * 256) * 4));
+    DevBuf<uint32_t> mem;
+    QS_HIP(c, mem.reserve((1024 + (size_t)blocks * 256) * 4, nullptr));
+    uint32_t *const buf = mem.get();
     std::vector<uint32_t> host(1024);
     uint32_t x = 0x9E3779B9u;
     for (uint32_t &w : host) { x ^= x << 13; x ^= x >> 17; x ^= x << 5; w = x; }   // random operands: all-zero words let the clock rise
@@ -932,7 +904,6 @@ extern "C" int qs_issue_probe(qs_ctx *c, uint32_t iterations, float *ns_per_inst
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(buf);
     if (e != hipSuccess) return fail(c, QS_ERR_HIP, std::string("qs_issue_probe: ") + hipGetErrorString(e));
     // per SIMD: 4 waves x iterations x 4 slots x 28 instructions
     *ns_per_instruction = ms * 1e6f / ((float)iterations * 4.f * 28.f * 4.f);
@@ -965,19 +936,13 @@ extern "C" void qs_batch_free(qs_ctx *c, qs_device_batch *b) {
 struct Stager {
     qs_ctx *c = nullptr; int slot = 0; size_t off = 0, need = 0; hipError_t err = hipSuccess;
     BatchSlab slab;
-    static size_t padded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
     hipError_t begin(qs_ctx *ctx, size_t bytes) {
         c = ctx; need = std::max<size_t>(bytes, 256); slot = (int)(c->pin_next++ & 1u);
         hipError_t e = hipSuccess;
         if (!c->copy_stream) e = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking);
         if (e == hipSuccess && !c->pin_ev[slot]) e = hipEventCreateWithFlags(&c->pin_ev[slot], hipEventDisableTiming);
         else if (e == hipSuccess) e = hipEventSynchronize(c->pin_ev[slot]);      // its previous contents are on the device
-        if (e == hipSuccess && c->pin_cap[slot] < need) {
-            if (c->pin[slot]) { (void)hipHostFree(c->pin[slot]); c->pin[slot] = nullptr; c->pin_cap[slot] = 0; }
-            const size_t cap = need + need / 4 + 4096;
-            e = hipHostMalloc(&c->pin[slot], cap, hipHostMallocDefault);
-            if (e == hipSuccess) c->pin_cap[slot] = cap;
-        }
+        if (e == hipSuccess) e = ensure_pinned(c, slot, need);
         if (e != hipSuccess) return err = e;
         // device slab: the smallest cached one that is large enough, else a new one
         int best = -1;
@@ -996,7 +961,7 @@ struct Stager {
     template <typename T> T *put(const T *src, size_t count) {
         if (err != hipSuccess) return nullptr;
         const size_t bytes = count * sizeof(T);
-        if (count) std::memcpy(static_cast<unsigned char *>(c->pin[slot]) + off, src, bytes);
+        if (count) std::memcpy(static_cast<unsigned char *>(c->pin[slot].get()) + off, src, bytes);
         T *dev = reinterpret_cast<T *>(static_cast<unsigned char *>(slab.p) + off);
         off += padded(bytes);
         return dev;
@@ -1004,7 +969,7 @@ struct Stager {
     // `ready` fires when the batch is on the device; the staging buffer is free again at the same moment
     hipError_t finish(hipEvent_t *ready) {
         if (err != hipSuccess) return err;
-        err = hipMemcpyAsync(slab.p, c->pin[slot], std::max<size_t>(off, 1), hipMemcpyHostToDevice, c->copy_stream);
+        err = hipMemcpyAsync(slab.p, c->pin[slot].get(), std::max<size_t>(off, 1), hipMemcpyHostToDevice, c->copy_stream);
         if (err == hipSuccess) err = hipEventCreateWithFlags(ready, hipEventDisableTiming);
         if (err == hipSuccess) err = hipEventRecord(*ready, c->copy_stream);
         if (err == hipSuccess) err = hipEventRecord(c->pin_ev[slot], c->copy_stream);
@@ -1456,9 +1421,9 @@ extern "C" int qs_batch_upload(qs_ctx *c, const qs_tree_batch *hb, qs_device_bat
     hipError_t e = hipSetDevice(c->device);
     Stager st;
     if (e == hipSuccess) {
-        size_t need = Stager::padded(((size_t)nt + 1) * 4) + 2 * Stager::padded((size_t)d.total_leaves * 2) + Stager::padded(order_host.size() * 4) +
-                      Stager::padded(fix_units.size() * sizeof(FixUnit));
-        if (with_nodes) need += Stager::padded(((size_t)nt + 1) * 4) + Stager::padded(((size_t)d.n_nodes + 1) * 4) + Stager::padded((size_t)d.n_nodes * 4) + Stager::padded((size_t)2 * d.n_links * 2);
+        size_t need = padded(((size_t)nt + 1) * 4) + 2 * padded((size_t)d.total_leaves * 2) + padded(order_host.size() * 4) +
+                      padded(fix_units.size() * sizeof(FixUnit));
+        if (with_nodes) need += padded(((size_t)nt + 1) * 4) + padded(((size_t)d.n_nodes + 1) * 4) + padded((size_t)d.n_nodes * 4) + padded((size_t)2 * d.n_links * 2);
         e = st.begin(c, need);
     }
     if (e == hipSuccess) {
@@ -1494,15 +1459,14 @@ static hipError_t clamp_fix_slots(qs_ctx *c, const qs_device_batch *b, uint32_t 
     const auto lo = std::lower_bound(b->fix_slot.begin(), b->fix_slot.end(), slot_lo), hi = std::lower_bound(lo, b->fix_slot.end(), slot_hi);
     if (lo == hi) return hipSuccess;
     return launch_clamp_fix(c->stream, b->d, b->d.fix_units + (lo - b->fix_slot.begin()), (uint32_t)(hi - lo), std::max(c->d_lo, 3u), c->d_hi,
-                            c->rank_lo, c->table, (int)c->count_bits, mode, wire, c->dev_flags);
+                            c->rank_lo, c->table, (int)c->count_bits, mode, wire, c->dev_flags.get());
 }
 
 // the pair-depth panel holds `need` bytes (growing it waits for the launches that read the old one)
 static int ensure_panel(qs_ctx *c, size_t need) {
-    if (need <= c->panel_bytes) return QS_OK;
-    if (c->panel) { QS_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->panel); c->panel = nullptr; c->panel_bytes = 0; }
-    if (hipMalloc(&c->panel, need) != hipSuccess) return fail(c, QS_ERR_OOM, "Insufficient memory! (pair-depth panel)");
-    c->panel_bytes = need;
+    const hipError_t e = c->panel.reserve(need, &c->stream);   // exactly `need`: see run_launch
+    if (e == hipErrorOutOfMemory) return fail(c, QS_ERR_OOM, "Insufficient memory! (pair-depth panel)");
+    QS_HIP(c, e);   // (the wait for the stream)
     return QS_OK;
 }
 
@@ -1511,10 +1475,10 @@ static int ensure_panel(qs_ctx *c, size_t need) {
 // binary_full launch that is not fused (coop), the cooperative lists.
 static int count_geometry(qs_ctx *c, bool tiles16x8, bool coop, CountGeometry &g) {
     g.n = c->n; g.d_lo = std::max(c->d_lo, 3u); g.d_hi = c->d_hi; g.rank_lo = c->rank_lo; g.n_dblk = c->n_dblk;
-    if (!tiles16x8) { g.total_tiles = c->total_tiles; g.dprefix = c->dprefix; g.cprefix = c->cprefix; return QS_OK; }
-    g.total_tiles = c->total_tiles3; g.dprefix = c->dprefix3; g.cprefix = c->cprefix3;
+    if (!tiles16x8) { g.total_tiles = c->total_tiles; g.dprefix = c->dprefix.get(); g.cprefix = c->cprefix.get(); return QS_OK; }
+    g.total_tiles = c->total_tiles3; g.dprefix = c->dprefix3.get(); g.cprefix = c->cprefix3.get();
     const int rc = tile_order(c, &g.perm);
-    if (rc == QS_OK && coop) { g.perm_coop = c->perm_coop; g.n_coop = c->n_coop; g.perm_rest = c->perm_rest; g.n_rest = c->n_rest; }
+    if (rc == QS_OK && coop) { g.perm_coop = c->perm_coop.get(); g.n_coop = c->n_coop; g.perm_rest = c->perm_rest.get(); g.n_rest = c->n_rest; }
     return rc;
 }
 
@@ -1587,7 +1551,7 @@ static int run_launch(qs_ctx *c, const qs_device_batch *b, const Launch &L, uint
             DeviceBatch sub = d;
             sub.slot0 = sg.slot0 + t0;        // slots [slot0, slot0 + nt) of the class-ordered batch
             sub.n_trees = nt;
-            void *pp = (char *)c->panel + off;
+            void *pp = (char *)c->panel.get() + off;
             if (bitsliced) QS_HIP(c, launch_build_bitpanel(c->stream, sub, c->n, sg.part, pp, nch, sg.nw, c->tune_panel_kernel == 1));
             else QS_HIP(c, launch_build_panel(c->stream, sub, c->n, L.bits, sg.part, pp, nch));
             seg_panel[sg.mode] = pp; seg_groups[sg.mode] = nch; seg_trees[sg.mode] = nt; seg_slot[sg.mode] = sub.slot0;
@@ -1596,11 +1560,11 @@ static int run_launch(qs_ctx *c, const qs_device_batch *b, const Launch &L, uint
         if (timed) QS_HIP(c, mark(c, 0));
         const bool ow = overwrite && first;
         if (L.kernel == KERNEL_FUSED)
-            QS_HIP(c, launch_count_bitslice3_fused(c->stream, g, seg_panel, seg_groups, seg_trees, L.bits, c->table, (int)c->count_bits, c->dev_flags, ow));
+            QS_HIP(c, launch_count_bitslice3_fused(c->stream, g, seg_panel, seg_groups, seg_trees, L.bits, c->table, (int)c->count_bits, c->dev_flags.get(), ow));
         else if (L.kernel == KERNEL_BITSLICE3)
             QS_HIP(c, launch_count_bitslice3(c->stream, g, seg_panel[mode0], L.bits, mode0, seg_groups[mode0], seg_trees[mode0], wire ? nullptr : c->table,
-                                             wire ? 32 : (int)c->count_bits, c->dev_flags, ow, wire));
-        else QS_HIP(c, launch_count_gather(c->stream, g, seg_panel[mode0], L.bits, mode0, seg_groups[mode0], seg_trees[mode0], c->table, (int)c->count_bits, c->dev_flags, ow));
+                                             wire ? 32 : (int)c->count_bits, c->dev_flags.get(), ow, wire));
+        else QS_HIP(c, launch_count_gather(c->stream, g, seg_panel[mode0], L.bits, mode0, seg_groups[mode0], seg_trees[mode0], c->table, (int)c->count_bits, c->dev_flags.get(), ow));
         first = false;
         if (timed) QS_HIP(c, mark(c, 1));
         if (bitsliced && d.n_fix) {   // (never the byte-SWAR kernel: its panel holds the trees' own depths)
@@ -1750,7 +1714,7 @@ extern "C" int qs_count_batch(qs_ctx *c, const qs_device_batch *b, uint32_t algo
     } else if (algo == QS_ALGO_SCATTER) {
         if (!d.node_off) return fail(c, QS_ERR_ARG, "qs_count_batch: QS_ALGO_SCATTER needs node_off/rng_off/ranges in the batch");
         if (c->n > 4096) return fail(c, QS_ERR_UNSUPPORTED, "scatter: n too large");
-        QS_HIP(c, launch_count_scatter(c->stream, d, c->n, c->d_lo, c->d_hi, c->rank_lo, c->table, (int)c->count_bits, c->dev_flags));
+        QS_HIP(c, launch_count_scatter(c->stream, d, c->n, c->d_lo, c->d_hi, c->rank_lo, c->table, (int)c->count_bits, c->dev_flags.get()));
         if (timed) QS_HIP(c, mark(c, 1));
         c->variant = std::string("scatter/atomic/count_u") + std::to_string(c->count_bits);
     } else {
@@ -1766,13 +1730,13 @@ extern "C" int qs_sync(qs_ctx *c) {
     QS_HIP(c, hipSetDevice(c->device));
     QS_HIP(c, hipStreamSynchronize(c->stream));
     uint32_t fl[4] = {0, 0, 0, 0};
-    QS_HIP(c, hipMemcpy(fl, c->dev_flags, 16, hipMemcpyDeviceToHost));
+    QS_HIP(c, hipMemcpy(fl, c->dev_flags.get(), 16, hipMemcpyDeviceToHost));
     if (fl[0]) {
-        (void)hipMemset(c->dev_flags, 0, 4);
+        (void)hipMemset(c->dev_flags.get(), 0, 4);
         return fail(c, QS_ERR_OVERFLOW, "count table overflow: a counter exceeded count_bits");
     }
     if (fl[3]) {
-        (void)hipMemset(c->dev_flags + 3, 0, 4);
+        (void)hipMemset(c->dev_flags.get() + 3, 0, 4);
         return fail(c, QS_ERR_STATE, "two-cell wire format: a tuple does not sum to the number of trees (the batch was not binary with all taxa)");
     }
     return QS_OK;
@@ -1847,15 +1811,13 @@ extern "C" int qs_lookup(qs_ctx *c, uint64_t nq, const uint16_t *abcd, uint64_t 
     for (uint64_t i = 0; i < nq * 4; ++i)
         if (abcd[i] >= c->n) return fail(c, QS_ERR_ARG, "qs_lookup: id out of range");
     QS_HIP(c, hipSetDevice(c->device));
-    uint16_t *dq = nullptr; uint64_t *dout = nullptr;
-    QS_HIP(c, hipMalloc(&dq, nq * 8));
-    hipError_t e = hipMalloc(&dout, nq * 24);
-    if (e != hipSuccess) { (void)hipFree(dq); return fail(c, QS_ERR_OOM, "qs_lookup: hipMalloc"); }
-    e = hipMemcpyAsync(dq, abcd, nq * 8, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_lookup(c->stream, c->n, c->d_lo, c->d_hi, c->rank_lo, c->table, (int)c->count_bits, nq, dq, dout);
-    if (e == hipSuccess) e = hipMemcpyAsync(out3, dout, nq * 24, hipMemcpyDeviceToHost, c->stream);
+    DevBuf<uint16_t> dq; DevBuf<uint64_t> dout;   // (freed on every way out; hipFree waits for the device)
+    QS_HIP(c, dq.reserve(nq * 8, nullptr));
+    if (dout.reserve(nq * 24, nullptr) != hipSuccess) return fail(c, QS_ERR_OOM, "qs_lookup: hipMalloc");
+    hipError_t e = hipMemcpyAsync(dq.get(), abcd, nq * 8, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_lookup(c->stream, c->n, c->d_lo, c->d_hi, c->rank_lo, c->table, (int)c->count_bits, nq, dq.get(), dout.get());
+    if (e == hipSuccess) e = hipMemcpyAsync(out3, dout.get(), nq * 24, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(dq); (void)hipFree(dout);
     if (e != hipSuccess) return fail(c, QS_ERR_HIP, std::string("qs_lookup: ") + hipGetErrorString(e));
     return QS_OK;
 }
@@ -2002,39 +1964,38 @@ static int build_ref(qs_ctx *c, const qs_ref_tree *ref, RefHost &R) {
 // caller passes a different tree.
 static int get_ref(qs_ctx *c, const qs_ref_tree *ref, bool want_dev, const RefHost **out) {
     if (!ref || !ref->parent || !ref->leaf_node) return fail(c, QS_ERR_ARG, "reference tree: NULL arrays");
-    RefHost *R = c->ref_cache;
+    RefHost *R = c->ref_cache.get();
     const bool same = R && R->n_nodes == ref->n_nodes && R->n == ref->n_taxa &&
                       memcmp(R->parent.data(), ref->parent, (size_t)ref->n_nodes * 4) == 0 &&
                       memcmp(R->leaf_node_in.data(), ref->leaf_node, (size_t)ref->n_taxa * 4) == 0;
     if (!same) {
-        RefHost *fresh = new RefHost();
+        std::unique_ptr<RefHost> fresh(new RefHost());
         int rc = build_ref(c, ref, *fresh);
-        if (rc != QS_OK) { delete fresh; return rc; }
+        if (rc != QS_OK) return rc;
         fresh->leaf_node_in.assign(ref->leaf_node, ref->leaf_node + ref->n_taxa);
-        if (c->ref_lca_dev) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->ref_lca_dev); (void)hipFree(c->ref_next_dev); (void)hipFree(c->root_pairs_dev); c->ref_lca_dev = nullptr; c->ref_next_dev = nullptr; c->root_pairs_dev = nullptr; }
-        delete c->ref_cache;
-        c->ref_cache = R = fresh;
+        if (c->ref_lca_dev) { (void)hipStreamSynchronize(c->stream); c->ref_lca_dev.reset(); c->ref_next_dev.reset(); c->root_pairs_dev.reset(); }
+        c->ref_cache = std::move(fresh);
+        R = c->ref_cache.get();
         c->log_valid = false;
     }
     if (want_dev && !c->ref_lca_dev) {
-        QS_HIP(c, hipMalloc(&c->ref_lca_dev, R->lca.size() * 4));
-        QS_HIP(c, hipMalloc(&c->ref_next_dev, R->next.size() * 2));
+        // The tree's device arrays are filled on the side and handed to the context together: ref_lca_dev says "all of them are
+        // there", so a call that fails half-way leaves none behind (the context's own are empty here: nothing is held twice).
+        DevBuf<uint32_t> lca; DevBuf<uint16_t> next; DevBuf<void> pairs;
+        QS_HIP(c, lca.reserve(R->lca.size() * 4, nullptr));
+        QS_HIP(c, next.reserve(R->next.size() * 2, nullptr));
         hipStream_t up = c->prep_stream ? c->prep_stream : c->stream;
-        QS_HIP(c, hipMemcpyAsync(c->ref_lca_dev, R->lca.data(), R->lca.size() * 4, hipMemcpyHostToDevice, up));
-        QS_HIP(c, hipMemcpyAsync(c->ref_next_dev, R->next.data(), R->next.size() * 2, hipMemcpyHostToDevice, up));
+        QS_HIP(c, hipMemcpyAsync(lca.get(), R->lca.data(), R->lca.size() * 4, hipMemcpyHostToDevice, up));
+        QS_HIP(c, hipMemcpyAsync(next.get(), R->next.data(), R->next.size() * 2, hipMemcpyHostToDevice, up));
         if (!R->root_pairs.empty()) {
-            QS_HIP(c, hipMalloc(&c->root_pairs_dev, R->root_pairs.size() * sizeof(RootPairHost)));
-            QS_HIP(c, hipMemcpyAsync(c->root_pairs_dev, R->root_pairs.data(), R->root_pairs.size() * sizeof(RootPairHost), hipMemcpyHostToDevice, up));
+            QS_HIP(c, pairs.reserve(R->root_pairs.size() * sizeof(RootPairHost), nullptr));
+            QS_HIP(c, hipMemcpyAsync(pairs.get(), R->root_pairs.data(), R->root_pairs.size() * sizeof(RootPairHost), hipMemcpyHostToDevice, up));
         }
+        c->ref_lca_dev = std::move(lca); c->ref_next_dev = std::move(next); c->root_pairs_dev = std::move(pairs);
     }
     *out = R;
     return QS_OK;
 }
-
-struct DevPtr { // RAII for a hipMalloc'ed pointer
-    void *p = nullptr;
-    ~DevPtr() { if (p) (void)hipFree(p); }
-};
 
 // log(k) and 1/k for the integer arguments of the device QIC: every count and every tuple sum is at most the
 // number of trees counted. Unknown (uploaded / attached tables, reduce-scattered shards): 65536 entries, larger
@@ -2045,14 +2006,14 @@ static int ensure_score_tables(qs_ctx *c) {
     const uint64_t want64 = std::min<uint64_t>(std::max<uint64_t>(std::max(c->trees_counted, c->table_trees_hint) + 1, 65536), 1ull << 20);
     const uint32_t want = (uint32_t)want64;
     if (c->tbl_n >= want) return QS_OK;
-    if (c->dev_logk) { QS_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->dev_logk); c->dev_logk = nullptr; c->tbl_n = 0; }
+    c->tbl_n = 0;   // (entries that are valid, not the capacity: set again once the new table is on the device)
     std::vector<double> lk(want);
     lk[0] = 0.0;
     for (uint32_t k = 1; k < want; ++k) lk[k] = std::log((double)k);
-    QS_HIP(c, hipMalloc(&c->dev_logk, (size_t)want * 8));
+    QS_HIP(c, c->dev_logk.reserve((size_t)want * 8, &c->stream));
     {   // (not the null stream: that one waits for count kernels still running on `stream`)
         hipStream_t up = c->prep_stream ? c->prep_stream : c->stream;
-        QS_HIP(c, hipMemcpyAsync(c->dev_logk, lk.data(), (size_t)want * 8, hipMemcpyHostToDevice, up));
+        QS_HIP(c, hipMemcpyAsync(c->dev_logk.get(), lk.data(), (size_t)want * 8, hipMemcpyHostToDevice, up));
         QS_HIP(c, hipStreamSynchronize(up));
     }
     c->tbl_n = want;
@@ -2060,14 +2021,14 @@ static int ensure_score_tables(qs_ctx *c) {
 }
 
 static void fill_score_device(const qs_ctx *c, const RefHost &R, const uint32_t *lca_dev, ScoreDevice &sd) {
-    sd.logk = c->dev_logk; sd.tbl_n = c->tbl_n;
+    sd.logk = c->dev_logk.get(); sd.tbl_n = c->tbl_n;
     // as much of the log table as fits goes to LDS (every tuple sum of up to 15743 trees); larger arguments are range-checked
     sd.coop_load = c->tune_score_load;
     sd.lds_n = (uint32_t)std::min<uint64_t>(c->tbl_n, score_scan_max_lds_log((c->tune_score_load == 1 || c->tune_score_load == 3) && c->tune_score_kernel == 0));
-    sd.ref_lca = lca_dev; sd.ref_next = c->ref_next_dev; sd.n = c->n; sd.n_inner = R.n_inner; sd.d_lo = c->d_lo; sd.d_hi = c->d_hi;
+    sd.ref_lca = lca_dev; sd.ref_next = c->ref_next_dev.get(); sd.n = c->n; sd.n_inner = R.n_inner; sd.d_lo = c->d_lo; sd.d_hi = c->d_hi;
     sd.rank_lo = c->rank_lo; sd.n_tuples = c->n_tuples; sd.table = c->table; sd.count_bits = (int)c->count_bits;
     if (c->view_table) { sd.rank_lo = c->view_rank_lo; sd.n_tuples = c->view_n; sd.table = const_cast<void *>(c->view_table); sd.count_bits = (int)c->view_bits; }
-    sd.pair_sums = nullptr; sd.pair_min = nullptr; sd.pair_cand = nullptr; sd.flags = c->dev_flags + 1;
+    sd.pair_sums = nullptr; sd.pair_min = nullptr; sd.pair_cand = nullptr; sd.flags = c->dev_flags.get() + 1;
     sd.cand_limit = c->tune_cand_slots; sd.list = nullptr; sd.list_count = nullptr; sd.list_cap = 0; sd.last_trip = nullptr;
     sd.frame = R.bifurcating ? 0 : 1;
     sd.root_split = (R.bifurcating && R.root_deg2) ? R.root_split : 0u;
@@ -2084,19 +2045,21 @@ static int ensure_bundle_plan(qs_ctx *c, ScoreDevice &sd, int pass) {
     BundlePlan &plan = c->bundle[w];
     const uint64_t r0 = sd.rank_lo, r1 = sd.rank_lo + sd.n_tuples;
     if (c->bundle_r0[w] != r0 || c->bundle_r1[w] != r1 || !c->bundle_dev[w]) {
-        if (c->bundle_dev[w]) { QS_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->bundle_dev[w]); c->bundle_dev[w] = nullptr; }
+        // (a new plan gets a table of its own size, never the old one's memory: kernels on `stream` may read that while `up` writes)
+        if (c->bundle_dev[w]) { QS_HIP(c, hipStreamSynchronize(c->stream)); c->bundle_dev[w].reset(); }
         plan_bundles(c->n, r0, r1, pass == 3 ? (uint32_t)kTaxonWaves : score_bundle_waves(pass, c->tune_score_load == 1 || c->tune_score_load == 3), plan);
         const size_t words = 2 * (size_t)c->n + plan.rounds.size();
-        if (hipMalloc(&c->bundle_dev[w], std::max<size_t>(words, 1) * 4) != hipSuccess) return fail(c, QS_ERR_OOM, "qs_score: round table of the bundle kernel");
+        if (c->bundle_dev[w].reserve(std::max<size_t>(words, 1) * 4, nullptr) != hipSuccess) return fail(c, QS_ERR_OOM, "qs_score: round table of the bundle kernel");
+        uint32_t *const dev = c->bundle_dev[w].get();
         hipStream_t up = c->prep_stream ? c->prep_stream : c->stream;
-        QS_HIP(c, hipMemcpyAsync(c->bundle_dev[w], plan.plo.data(), (size_t)c->n * 4, hipMemcpyHostToDevice, up));
-        QS_HIP(c, hipMemcpyAsync(c->bundle_dev[w] + c->n, plan.pcnt.data(), (size_t)c->n * 4, hipMemcpyHostToDevice, up));
+        QS_HIP(c, hipMemcpyAsync(dev, plan.plo.data(), (size_t)c->n * 4, hipMemcpyHostToDevice, up));
+        QS_HIP(c, hipMemcpyAsync(dev + c->n, plan.pcnt.data(), (size_t)c->n * 4, hipMemcpyHostToDevice, up));
         if (!plan.rounds.empty())
-            QS_HIP(c, hipMemcpyAsync(c->bundle_dev[w] + 2 * (size_t)c->n, plan.rounds.data(), plan.rounds.size() * 4, hipMemcpyHostToDevice, up));
+            QS_HIP(c, hipMemcpyAsync(dev + 2 * (size_t)c->n, plan.rounds.data(), plan.rounds.size() * 4, hipMemcpyHostToDevice, up));
         QS_HIP(c, hipStreamSynchronize(up));   // (the host vectors may be re-planned by the next call)
         c->bundle_r0[w] = r0; c->bundle_r1[w] = r1;
     }
-    sd.bundle_plo = c->bundle_dev[w]; sd.bundle_pcnt = c->bundle_dev[w] + c->n; sd.bundle_rounds = c->bundle_dev[w] + 2 * (size_t)c->n;
+    sd.bundle_plo = c->bundle_dev[w].get(); sd.bundle_pcnt = sd.bundle_plo + c->n; sd.bundle_rounds = sd.bundle_plo + 2 * (size_t)c->n;
     sd.n_rounds = (uint32_t)(plan.rounds.size() / 2);
     return QS_OK;
 }
@@ -2120,7 +2083,7 @@ extern "C" int qs_taxon_support(qs_ctx *c, const qs_ref_tree *ref, int64_t *dst_
     const RefHost *Rp = nullptr;
     if (int rc = get_ref(c, ref, true, &Rp)) return rc;
     ScoreDevice sd;
-    fill_score_device(c, *Rp, c->ref_lca_dev, sd);
+    fill_score_device(c, *Rp, c->ref_lca_dev.get(), sd);
     sd.rank_lo = c->rank_lo; sd.n_tuples = c->n_tuples; sd.table = c->table; sd.count_bits = (int)c->count_bits;   // the context's own table, not a scoring view
     sd.flags = nullptr;
     if (int rc = ensure_bundle_plan(c, sd, 3)) return rc;
@@ -2166,32 +2129,28 @@ extern "C" int qs_score_set_view(qs_ctx *c, const void *table_dev, uint32_t coun
 // qs_score's accumulators on the device and their pinned host copy, cached in the context
 static int ensure_score_accumulators(qs_ctx *c, size_t np) {
     const size_t need_dev = np * (size_t)(3 + 1 + kCand) * 8, need_host = np * (size_t)(3 + kCand) * 8;
-    if (c->score_acc_cap < need_dev) {
-        if (c->score_acc) { QS_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->score_acc); }
-        c->score_acc = nullptr; c->score_acc_cap = 0;
-        QS_HIP(c, hipMalloc(&c->score_acc, need_dev));
-        c->score_acc_cap = need_dev;
-    }
-    if (c->score_acc_host_cap < need_host) {
-        if (c->score_acc_host) { QS_HIP(c, hipStreamSynchronize(c->stream)); (void)hipHostFree(c->score_acc_host); }
-        c->score_acc_host = nullptr; c->score_acc_host_cap = 0;
-        QS_HIP(c, hipHostMalloc(&c->score_acc_host, need_host, hipHostMallocDefault));
-        c->score_acc_host_cap = need_host;
-    }
+    QS_HIP(c, c->score_acc.reserve(need_dev, &c->stream));
+    QS_HIP(c, c->score_acc_host.reserve(need_host, &c->stream));
     return QS_OK;
 }
 
 // the candidate log of the single-read scoring: records, the counter word, one word per node pair (tie filter)
 static bool ensure_score_log(qs_ctx *c, size_t np) {
     const uint64_t want_cap = c->tune_score_log_cap ? c->tune_score_log_cap : (1ull << 23);   // 8 M records = 256 MB
-    if (c->score_log && (c->score_log_cap != want_cap || c->score_log_pairs < np)) {
-        (void)hipStreamSynchronize(c->stream); (void)hipFree(c->score_log); c->score_log = nullptr; c->score_log_cap = 0; c->score_log_pairs = 0;
-    }
-    if (!c->score_log) {
-        if (hipMalloc((void **)&c->score_log, (want_cap * 4 + 1 + np) * 8) == hipSuccess) { c->score_log_cap = want_cap; c->score_log_pairs = np; }
-        else (void)hipGetLastError();   // no room for the log: two passes
-    }
-    return c->score_log != nullptr;
+    // (the counter sits behind the records: another capacity is another layout, and a buffer of its own size as before)
+    if (c->score_log && c->score_log_cap != want_cap) { (void)hipStreamSynchronize(c->stream); c->score_log.reset(); }
+    c->score_log_cap = 0;
+    if (c->score_log.reserve((want_cap * 4 + 1 + np) * 8, &c->stream) != hipSuccess) { (void)hipGetLastError(); return false; }   // no room for the log: two passes
+    c->score_log_cap = want_cap;
+    return true;
+}
+
+// Is the single-read scoring wanted for the tuples sd covers? The bundle kernel over whole rows (bundle[0]: the plan of pass 1);
+// QS_TUNE_SCORE_PASSES: 0 = automatic (tables from 1 GB, if there is a sample to predict the log from), 1 = never, 2 = always.
+static bool want_score_log(const qs_ctx *c, const ScoreDevice &sd) {
+    const uint64_t scored_bytes = sd.n_tuples * 3 * (uint64_t)(sd.count_bits / 8);
+    return c->tune_score_kernel == 0 && c->bundle[0].n_parts == 0 &&
+           (c->tune_score_passes == 2 || (c->tune_score_passes == 0 && c->tune_score_sample != 0 && scored_bytes >= (1ull << 30)));
 }
 
 extern "C" int qs_score_pass1(qs_ctx *c, const qs_ref_tree *ref, int64_t *sums_dev, int64_t *min_dev) {
@@ -2207,7 +2166,7 @@ extern "C" int qs_score_pass1(qs_ctx *c, const qs_ref_tree *ref, int64_t *sums_d
     QS_HIP(c, hipMemsetAsync(min_dev, 0x7F, np * 8, c->stream));
     { int rc_t = ensure_score_tables(c); if (rc_t != QS_OK) return rc_t; }
     ScoreDevice sd;
-    fill_score_device(c, R, c->ref_lca_dev, sd);
+    fill_score_device(c, R, c->ref_lca_dev.get(), sd);
     sd.pair_sums = (unsigned long long *)sums_dev; sd.pair_min = (long long *)min_dev;
     { int rc_b = ensure_bundle_plan(c, sd, 1); if (rc_b != QS_OK) return rc_b; }
     // Single-read scoring: this pass also LOGS every quartet whose device QIC is within the tolerance of the bound it knows for
@@ -2219,15 +2178,10 @@ extern "C" int qs_score_pass1(qs_ctx *c, const qs_ref_tree *ref, int64_t *sums_d
     // the pass runs plain when it would not hold), 1 = never, 2 = always (pass 2 reads the table if the log overflows).
     c->log_valid = false;
     c->last_score_estimate = 0;
-    const uint64_t scored_bytes = sd.n_tuples * 3 * (uint64_t)(sd.count_bits / 8);
-    const bool want_log = c->tune_score_kernel == 0 && c->bundle[0].n_parts == 0 && sd.n_rounds > 0 &&
-                          (c->tune_score_passes == 2 || (c->tune_score_passes == 0 && c->tune_score_sample != 0 && scored_bytes >= (1ull << 30)));
-    bool logging = false;
-    if (want_log) {
-        logging = ensure_score_log(c, np);
-    }
+    // (sd.n_rounds: pass 1's plan as ensure_bundle_plan has just left it -- a plan without rounds has nothing to log)
+    bool logging = want_score_log(c, sd) && sd.n_rounds > 0 && ensure_score_log(c, np);
     if (logging) {
-        sd.list = c->score_log; sd.list_count = c->score_log + 4 * c->score_log_cap; sd.list_cap = c->score_log_cap;
+        sd.list = c->score_log.get(); sd.list_count = sd.list + 4 * c->score_log_cap; sd.list_cap = c->score_log_cap;
         QS_HIP(c, hipMemsetAsync(sd.list_count, 0, 8, c->stream));
         if (c->tune_score_dedupe) {   // the tie filter (one word per node pair behind the log's counter)
             sd.last_trip = sd.list_count + 1;
@@ -2260,14 +2214,14 @@ extern "C" int qs_score_pass1(qs_ctx *c, const qs_ref_tree *ref, int64_t *sums_d
         }
         // waves reserve whole chunks of records: what they leave unwritten must read as "no record" (key = all ones)
         if (logging) {
-            QS_HIP(c, hipMemsetAsync(c->score_log, 0xFF, (size_t)c->score_log_cap * 32, c->stream));
+            QS_HIP(c, hipMemsetAsync(sd.list, 0xFF, (size_t)c->score_log_cap * 32, c->stream));
             c->log_valid = true;                 // until the table, the view or the tuning changes (invalidate_log)
             c->log_table = sd.table; c->log_rank_lo = sd.rank_lo; c->log_n_tuples = sd.n_tuples; c->log_ref = Rp; c->log_tol = c->tune_score_tol;
         }
     }
     QS_HIP(c, launch_score_pass1(c->stream, sd, c->tune_score_kernel, c->n_cu, c->bundle[0].part_lo, c->bundle[0].part_n, c->bundle[0].n_parts, c->tune_score_tol));
     // rooted reference (degree-2 root): the sums of the node pairs (root, v) as the reference enumerates them (quirk Q5)
-    if (c->root_pairs_dev) QS_HIP(c, launch_root_pair_sums(c->stream, sd, c->root_pairs_dev, (uint32_t)R.root_pairs.size(), R.root_items));
+    if (c->root_pairs_dev) QS_HIP(c, launch_root_pair_sums(c->stream, sd, c->root_pairs_dev.get(), (uint32_t)R.root_pairs.size(), R.root_items));
     return QS_OK;   // asynchronous on the context's stream
 }
 
@@ -2284,9 +2238,8 @@ extern "C" int qs_score_prepare(qs_ctx *c, const qs_ref_tree *ref, uint64_t n_tr
     // present in the context, and the kernels of a later qs_score run on `stream`, which has no ordering against `copy_stream`
     struct Restore { qs_ctx *c; ~Restore() { c->prep_stream = nullptr; (void)hipStreamSynchronize(c->copy_stream); } } restore{c};
     c->prep_stream = c->copy_stream;
-    const bool had_ref = c->ref_lca_dev != nullptr;
     const RefHost *Rp = nullptr;
-    int rc = get_ref(c, ref, !had_ref || true, &Rp);
+    int rc = get_ref(c, ref, true, &Rp);
     if (rc != QS_OK) return rc;
     const size_t np = (size_t)Rp->n_inner * Rp->n_inner;
     if (np == 0) return fail(c, QS_ERR_ARG, "qs_score_prepare: bad reference tree");
@@ -2296,18 +2249,17 @@ extern "C" int qs_score_prepare(qs_ctx *c, const qs_ref_tree *ref, uint64_t n_tr
     c->table_trees_hint = keep_hint;
     if (rc != QS_OK) return rc;
     ScoreDevice sd;
-    fill_score_device(c, *Rp, c->ref_lca_dev, sd);
+    fill_score_device(c, *Rp, c->ref_lca_dev.get(), sd);
     rc = ensure_bundle_plan(c, sd, 1);
     if (rc == QS_OK) rc = ensure_bundle_plan(c, sd, 2);
     if (rc != QS_OK) return rc;
     rc = ensure_score_accumulators(c, np);
     if (rc != QS_OK) return rc;
-    const uint64_t scored_bytes = sd.n_tuples * 3 * (uint64_t)(sd.count_bits / 8);
-    if (c->tune_score_kernel == 0 && c->bundle[0].n_parts == 0 && (c->tune_score_passes == 2 || (c->tune_score_passes == 0 && c->tune_score_sample != 0 && scored_bytes >= (1ull << 30))))
-        (void)ensure_score_log(c, np);
+    // (without pass 1's "the plan has rounds": sd holds pass 2's plan here, and a log that is never used costs only its memory)
+    if (want_score_log(c, sd)) (void)ensure_score_log(c, np);
     for (hipEvent_t &e : c->score_ev) if (!e) QS_HIP(c, hipEventCreate(&e));
     // first use of the pinned accumulator copy by the device (the first device-to-host copy into freshly pinned memory took 7 ms)
-    QS_HIP(c, hipMemcpyAsync(c->score_acc_host, c->score_acc, np * (size_t)(3 + kCand) * 8, hipMemcpyDeviceToHost, c->copy_stream));
+    QS_HIP(c, hipMemcpyAsync(c->score_acc_host.get(), c->score_acc.get(), np * (size_t)(3 + kCand) * 8, hipMemcpyDeviceToHost, c->copy_stream));
     QS_HIP(c, hipStreamSynchronize(c->copy_stream));
     return QS_OK;
 }
@@ -2322,10 +2274,10 @@ extern "C" int qs_score_pass2(qs_ctx *c, const qs_ref_tree *ref, const int64_t *
     const RefHost &R = *Rp;
     const size_t np = (size_t)R.n_inner * R.n_inner;
     QS_HIP(c, hipMemsetAsync(cand_dev, 0xFF, np * kCand * 8, c->stream));
-    QS_HIP(c, hipMemsetAsync(c->dev_flags + 1, 0, 4, c->stream));
+    QS_HIP(c, hipMemsetAsync(c->dev_flags.get() + 1, 0, 4, c->stream));
     { int rc_t = ensure_score_tables(c); if (rc_t != QS_OK) return rc_t; }
     ScoreDevice sd;
-    fill_score_device(c, R, c->ref_lca_dev, sd);
+    fill_score_device(c, R, c->ref_lca_dev.get(), sd);
     sd.pair_min = (long long *)min_dev; sd.pair_cand = (unsigned long long *)cand_dev;
     c->last_score_log = 0;
     if (c->log_valid && c->log_table == sd.table && c->log_rank_lo == sd.rank_lo && c->log_n_tuples == sd.n_tuples && c->log_ref == Rp &&
@@ -2333,13 +2285,13 @@ extern "C" int qs_score_pass2(qs_ctx *c, const qs_ref_tree *ref, const int64_t *
         // the preceding qs_score_pass1 over this very table logged its candidates: filter the log against min_dev
         c->log_valid = false;
         unsigned long long n_rec = 0;
-        QS_HIP(c, hipMemcpyAsync(&n_rec, c->score_log + 4 * c->score_log_cap, 8, hipMemcpyDeviceToHost, c->stream));
+        QS_HIP(c, hipMemcpyAsync(&n_rec, c->score_log.get() + 4 * c->score_log_cap, 8, hipMemcpyDeviceToHost, c->stream));
         QS_HIP(c, hipStreamSynchronize(c->stream));
         // A counter that reached the capacity is an overflow: waves reserve chunks of 64 records, the capacity is a multiple
         // of 64, so the counter can stop exactly AT the capacity while waves that found the log full at the start of a row
         // have skipped their hits without moving it. Only a log with room left is known to be complete.
         if (n_rec < c->score_log_cap) {
-            sd.list = c->score_log; sd.list_cap = c->score_log_cap;
+            sd.list = c->score_log.get(); sd.list_cap = c->score_log_cap;
             QS_HIP(c, launch_score_log(c->stream, sd, c->tune_score_tol, n_rec));
             c->last_score_log = n_rec;
             return QS_OK;
@@ -2362,31 +2314,30 @@ extern "C" int qs_score_overflow(qs_ctx *c, const qs_ref_tree *ref, const int64_
     *list_out = nullptr; *n_out = 0;
     QS_HIP(c, hipSetDevice(c->device));
     uint32_t fl = 0;
-    QS_HIP(c, hipMemcpyAsync(&fl, c->dev_flags + 1, 4, hipMemcpyDeviceToHost, c->stream));
+    QS_HIP(c, hipMemcpyAsync(&fl, c->dev_flags.get() + 1, 4, hipMemcpyDeviceToHost, c->stream));
     QS_HIP(c, hipStreamSynchronize(c->stream));
     if ((fl & 3u) == 0) return QS_OK;
     const RefHost *Rp = nullptr;
     int rc = get_ref(c, ref, true, &Rp);
     if (rc != QS_OK) return rc;
     ScoreDevice sd;
-    fill_score_device(c, *Rp, c->ref_lca_dev, sd);
+    fill_score_device(c, *Rp, c->ref_lca_dev.get(), sd);
     sd.pair_min = (long long *)const_cast<int64_t *>(min_dev); sd.pair_cand = (unsigned long long *)const_cast<int64_t *>(cand_dev);
-    DevPtr cnt, list;
-    QS_HIP(c, hipMalloc(&cnt.p, 8));
+    DevBuf<unsigned long long> cnt, list;
+    QS_HIP(c, cnt.reserve(8, nullptr));
     uint64_t cap = 1ull << 20;
     std::vector<unsigned long long> host;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        if (list.p) { (void)hipFree(list.p); list.p = nullptr; }
-        if (hipMalloc(&list.p, cap * 32) != hipSuccess) return fail(c, QS_ERR_OOM, "qs_score_overflow: list of " + std::to_string(cap) + " quartets does not fit");
-        QS_HIP(c, hipMemsetAsync(cnt.p, 0, 8, c->stream));
-        sd.list = (unsigned long long *)list.p; sd.list_count = (unsigned long long *)cnt.p; sd.list_cap = cap;
+        if (list.reserve(cap * 32, nullptr) != hipSuccess) return fail(c, QS_ERR_OOM, "qs_score_overflow: list of " + std::to_string(cap) + " quartets does not fit");
+        QS_HIP(c, hipMemsetAsync(cnt.get(), 0, 8, c->stream));
+        sd.list = list.get(); sd.list_count = cnt.get(); sd.list_cap = cap;
         QS_HIP(c, launch_score_overflow_list(c->stream, sd, c->tune_score_tol));
         unsigned long long got = 0;
-        QS_HIP(c, hipMemcpyAsync(&got, cnt.p, 8, hipMemcpyDeviceToHost, c->stream));
+        QS_HIP(c, hipMemcpyAsync(&got, cnt.get(), 8, hipMemcpyDeviceToHost, c->stream));
         QS_HIP(c, hipStreamSynchronize(c->stream));
         if (got <= cap) {
             host.resize(got * 4);
-            if (got) QS_HIP(c, hipMemcpy(host.data(), list.p, got * 32, hipMemcpyDeviceToHost));
+            if (got) QS_HIP(c, hipMemcpy(host.data(), list.get(), got * 32, hipMemcpyDeviceToHost));
             break;
         }
         if (attempt == 1 || got > (1ull << 28)) return fail(c, QS_ERR_OVERFLOW, "qs_score_overflow: " + std::to_string(got) + " near-minimal quartets");
@@ -2628,7 +2579,7 @@ extern "C" int qs_score(qs_ctx *c, const qs_ref_tree *ref, uint32_t flags, doubl
     // hipMalloc / hipFree pairs and a pageable 22 MB copy per call were 1 ms of a 15 ms call
     struct Ptr { void *p; } sums{nullptr}, mn{nullptr}, cand{nullptr};
     { int rc_a = ensure_score_accumulators(c, np); if (rc_a != QS_OK) return rc_a; }
-    sums.p = c->score_acc; mn.p = (char *)c->score_acc + np * 3 * 8; cand.p = (char *)c->score_acc + np * 4 * 8;
+    sums.p = c->score_acc.get(); mn.p = (char *)sums.p + np * 3 * 8; cand.p = (char *)sums.p + np * 4 * 8;
     {   // the cached pieces both passes need (reference tree + LCA matrix, log table, bundle plans): built here so that
         // the first call's set-up cost shows as its own phase and the events below bracket kernels only
         const RefHost *Rp = nullptr;
@@ -2657,7 +2608,7 @@ extern "C" int qs_score(qs_ctx *c, const qs_ref_tree *ref, uint32_t flags, doubl
     // it). The first large device-to-host copy enqueued on a stream that has run kernels costs ~8 ms on the host, once per
     // stream (tools/d2h_cold.hip); a stream that only ever copies does not pay it -- that was most of a first call's
     // "wait + copies" phase.
-    int64_t *hs = (int64_t *)c->score_acc_host, *hc = hs + np * 3;
+    int64_t *hs = (int64_t *)c->score_acc_host.get(), *hc = hs + np * 3;
     if (!c->copy_stream) QS_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     QS_HIP(c, hipMemcpyAsync(hs, sums.p, np * 3 * 8, hipMemcpyDeviceToHost, c->copy_stream));
     QS_HIP(c, hipMemcpyAsync(hc, cand.p, np * kCand * 8, hipMemcpyDeviceToHost, c->copy_stream));
@@ -2696,19 +2647,18 @@ static int raw_qic_impl(qs_ctx *c, const qs_ref_tree *ref, uint64_t r0, uint64_t
     int rc = get_ref(c, ref, true, &Rp);
     if (rc != QS_OK) return rc;
     const RefHost &R = *Rp;
-    uint8_t *dt = nullptr; unsigned long long *dq = nullptr;
-    QS_HIP(c, hipMalloc(&dt, nq));
-    hipError_t e = hipMalloc(&dq, nq * 24);
-    if (e != hipSuccess) { (void)hipFree(dt); return fail(c, QS_ERR_OOM, "qs_raw_qic: hipMalloc"); }
+    DevBuf<uint8_t> dt_mem; DevBuf<unsigned long long> dq_mem;   // (freed on every way out; hipFree waits for the device)
+    QS_HIP(c, dt_mem.reserve(nq, nullptr));
+    if (dq_mem.reserve(nq * 24, nullptr) != hipSuccess) return fail(c, QS_ERR_OOM, "qs_raw_qic: hipMalloc");
+    uint8_t *const dt = dt_mem.get(); unsigned long long *const dq = dq_mem.get();
     { int rc_t = ensure_score_tables(c); if (rc_t != QS_OK) return rc_t; }
     ScoreDevice sd;
-    fill_score_device(c, R, c->ref_lca_dev, sd);
+    fill_score_device(c, R, c->ref_lca_dev.get(), sd);
     sd.frame = 1; // printRawQICScores uses the multifurcating loop's argument order
-    e = lex ? launch_raw_qic_lex(c->stream, sd, r0, nq, dt, dq) : launch_raw_qic(c->stream, sd, r0, nq, dt, dq);
+    hipError_t e = lex ? launch_raw_qic_lex(c->stream, sd, r0, nq, dt, dq) : launch_raw_qic(c->stream, sd, r0, nq, dt, dq);
     if (e == hipSuccess) e = hipMemcpyAsync(topo, dt, nq, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(q, dq, nq * 24, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(dt); (void)hipFree(dq);
     if (e != hipSuccess) return fail(c, QS_ERR_HIP, std::string("qs_raw_qic: ") + hipGetErrorString(e));
     return QS_OK;
 }
