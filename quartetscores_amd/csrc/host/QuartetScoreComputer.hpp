@@ -8,8 +8,7 @@
 // libquartetscores_hip.so on the GPU; this header flattens trees and forwards.
 #pragma once
 
-#include "../../../include/quartetscores_hip.h"
-#include "flatten.hpp"
+#include "host_common.hpp"
 #include "ingest.hpp"
 #include "newick.hpp"
 
@@ -58,38 +57,6 @@ inline std::shared_ptr<const EvalFile> loadEvalFile(const std::string &evalTrees
 }
 // Count the number of evaluation trees: one scan for top-level ';' (ingest.hpp).
 inline size_t countEvalTrees(const std::string &evalTreesPath) { return loadEvalFile(evalTreesPath)->spans.size(); }
-
-struct DeviceOptions {
-    int device = 0;
-    uint32_t algo = QS_ALGO_AUTO;
-    size_t batch_trees = 8192;   // trees per device batch = 256 groups of 32 = one panel slice = one launch of the count kernel per depth
-                                 // class (each launch reads and writes the whole table once); batch k+1 is parsed and flattened on the
-                                 // host threads while batch k counts
-    size_t first_batch_trees = 2048;   // ... and only the FIRST batch's parse is exposed: it is a small one (the device starts after
-                                 // ~1/4 of the time; 512 taxa x 10000 trees: counting phase 0.43 -> 0.39 s at -t 8)
-    unsigned ingest_threads = 0; // host threads that parse + flatten (0 = hardware concurrency); the CLI's -t
-    bool qp_exact64 = false;
-    bool root_as_edge = false;   // QS_SCORE_ROOT_AS_EDGE: a degree-2 root as a subdivision of one edge (not the reference's quirk Q5)
-    bool savemem_lookups = false; // QS_SCORE_SAVEMEM_LOOKUPS (the CLI's -s): a rooted reference tree ends the run with the
-                                 // std::runtime_error the reference's compact table throws (quartet_lookup_table.hpp:79-85)
-    std::string reduce = "rccl"; // --gpus N: "rccl" (ncclReduceScatter / ncclAllReduce) or "p2p" (peer access, no communicator: multi_gpu.hpp)
-    bool gpus_on_one_device = false; // test hook of --reduce p2p: the N "GPUs" are N contexts on device `device`
-    bool comm_overlap = false;   // --gpus N, rccl: count while ncclCommInitAll runs (false: the first launch waits for the communicators)
-    std::string load_table, save_table; // count-table persistence
-    bool trace = false;          // --trace: time stamps of the counting pipeline on stderr
-    std::string per_tree;        // --per-tree FILE: batches carry their node ranges (qs_tree_agreement reads them)
-    // called behind every batch's qs_count_batch (first tree of the batch, the flattened batch) and behind the final qs_sync
-    std::function<void(qs_ctx *, const qs_device_batch *, size_t, const BatchFlat &)> after_count;
-    std::function<void(qs_ctx *)> after_sync;
-};
-
-// --trace: "[trace] +12.3 ms  what" relative to the first call (process start for practical purposes)
-inline void trace_mark(const DeviceOptions &opt, const char *what) {
-    if (!opt.trace) return;
-    static const auto t0 = std::chrono::steady_clock::now();
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    std::fprintf(stderr, "[trace] +%8.1f ms  %s\n", ms, what);
-}
 
 template <typename CINT> class QuartetCounterLookup {
 public:
@@ -194,8 +161,7 @@ private:
             return;
         }
         const auto &spans = ef->spans;
-        const bool want_ranges = wants_ranges(opt);
-        std::vector<qs_device_batch *> in_flight;
+        BatchQueue queue(ctx_);
         unsigned progress = 1;
         const float onePercent = (float)m / 100;
         // Batch k + 1 is parsed and flattened (on the host threads) while this thread validates, stages and enqueues batch k:
@@ -210,20 +176,7 @@ private:
                 const size_t i1 = batch_end(i0, spans.size(), opt);
                 BatchFlat b = i0 == 0 ? std::move(first) : ahead.get();
                 if (i1 < spans.size()) ahead = flatten_ahead(i1);
-                qs_tree_batch hb;
-                hb.n_trees = b.n_trees; hb.leaf_off = b.leaf_off.data(); hb.leaf_ids = b.leaf_ids.data();
-                hb.adj_depth = b.adj_depth.data();
-                hb.node_off = want_ranges ? b.node_off.data() : nullptr; hb.rng_off = want_ranges ? b.rng_off.data() : nullptr;
-                hb.ranges = b.ranges.data();
-                // at most two device batches alive: the one being counted and the one being uploaded. Freeing is cheap
-                // (the library keeps the device slab for the next upload and orders its reuse behind the kernels).
-                if (in_flight.size() == 2) { qs_batch_free(ctx_, in_flight.front()); in_flight.erase(in_flight.begin()); }
-                qs_device_batch *db = nullptr;
-                // the batch is copied into pinned staging memory here (`b` may go away); the copy to the device runs on
-                // the library's copy stream while the previous batch is still being counted
-                if (qs_batch_upload(ctx_, &hb, &db) != QS_OK) fail();
-                in_flight.push_back(db);
-                if (qs_count_batch(ctx_, db, opt.algo) != QS_OK) fail(); // asynchronous
+                const qs_device_batch *db = queue.submit(b, wants_ranges(opt), opt.algo);
                 if (opt.after_count) opt.after_count(ctx_, db, i0, b);
                 trace_mark(opt, "host: batch uploaded, count enqueued");
                 while ((float)i1 > progress * onePercent && progress <= 100) { // QCL:230-233
@@ -233,22 +186,18 @@ private:
             }
             {   // the scoring set-up (reference tree on the device, round tables, accumulators, candidate log) while the device
                 // still counts: this thread would only wait. Optional -- a failure here shows up again in qs_score.
-                qs_ref_tree rt;
-                rt.n_nodes = (uint32_t)ref_.parent.size(); rt.n_taxa = (uint32_t)ref_.names.size();
-                rt.parent = ref_.parent.data(); rt.leaf_node = ref_.leaf_node.data();
+                const qs_ref_tree rt = ref_view(ref_);
                 (void)qs_score_prepare(ctx_, &rt, (uint64_t)m);
                 trace_mark(opt, "host: scoring set-up done behind the enqueued counts");
             }
-            if (qs_sync(ctx_) != QS_OK) fail();
+            queue.sync();
             if (opt.after_sync) opt.after_sync(ctx_);
             trace_mark(opt, "host: all counts done (device synchronised)");
-        } catch (...) {
-            if (ahead.valid()) { try { (void)ahead.get(); } catch (...) {} }   // (the worker still reads the evaluation file)
-            (void)qs_sync(ctx_);
-            for (auto *db : in_flight) qs_batch_free(ctx_, db);
+        } catch (...) {   // (the worker still reads the evaluation file; then `queue` waits for the device and frees its batches)
+            if (ahead.valid()) { try { (void)ahead.get(); } catch (...) {} }
             throw;
         }
-        for (auto *db : in_flight) qs_batch_free(ctx_, db);
+        queue.release();
         if (!opt.save_table.empty()) {
             std::string bytes(qs_table_bytes(ctx_), '\0');
             if (qs_table_download(ctx_, &bytes[0], bytes.size()) != QS_OK) fail();
@@ -261,7 +210,6 @@ private:
 
     // rank -> sorted ids (rank = C(s3,4)+C(s2,3)+C(s1,2)+s0)
 inline void raw_unrank(uint64_t r, uint32_t &s0, uint32_t &s1, uint32_t &s2, uint32_t &s3) {
-        auto c4 = [](uint64_t x) { return x < 4 ? 0 : x * (x - 1) * (x - 2) * (x - 3) / 24; };
         auto c3 = [](uint64_t x) { return x < 3 ? 0 : x * (x - 1) * (x - 2) / 6; };
         auto c2 = [](uint64_t x) { return x * (x - 1) / 2; };
         uint64_t d = 3; while (c4(d + 1) <= r) ++d;
@@ -292,11 +240,9 @@ inline double raw_log_score(size_t q1, size_t q2, size_t q3) {
     // formats C(n,4) lines on one thread). Line order: the reference's own -- four nested loops over its Euler-tour
     // leaves = lexicographic in the sorted lookup ids (:626-630; qs_raw_qic_lex) -- or, with raw_rank_order, the
     // table's rank order (coalesced table reads; same set of lines).
-inline void print_raw_qic_scores(qs_ctx *ctx, const RefFlat &rf, Tree const &refTree, const std::string &rawPath, unsigned raw_threads, bool raw_rank_order) {
+inline void print_raw_qic_scores(qs_ctx *ctx, const RefFlat &rf, const std::string &rawPath, unsigned raw_threads, bool raw_rank_order) {
         std::ofstream outfile(rawPath, std::ios::binary);
-        qs_ref_tree rt;
-        rt.n_nodes = (uint32_t)refTree.node_count(); rt.n_taxa = (uint32_t)rf.names.size();
-        rt.parent = rf.parent.data(); rt.leaf_node = rf.leaf_node.data();
+        const qs_ref_tree rt = ref_view(rf);
         const uint64_t total = qs_table_tuples(ctx), chunk = 1u << 22;
         std::vector<uint8_t> topo(chunk);
         std::vector<uint64_t> q(chunk * 3);
@@ -349,12 +295,10 @@ inline void print_raw_qic_scores(qs_ctx *ctx, const RefFlat &rf, Tree const &ref
     //   u8  topo[n_quartets]                      per rank (rank = C(s3,4)+C(s2,3)+C(s1,2)+s0 of the sorted lookup ids):
     //                                             0 = s0 s1 | s2 s3, 2 = s0 s3 | s1 s2, 255 = not resolved in the reference
     //   f64 qic[n_quartets]                       raw QIC of the reference topology (NaN where topo = 255)
-inline void print_raw_qic_binary(qs_ctx *ctx, const RefFlat &rf, Tree const &refTree, const std::string &path) {
+inline void print_raw_qic_binary(qs_ctx *ctx, const RefFlat &rf, const std::string &path) {
         std::ofstream out(path, std::ios::binary);
         if (!out) throw std::runtime_error("cannot write " + path);
-        qs_ref_tree rt;
-        rt.n_nodes = (uint32_t)refTree.node_count(); rt.n_taxa = (uint32_t)rf.names.size();
-        rt.parent = rf.parent.data(); rt.leaf_node = rf.leaf_node.data();
+        const qs_ref_tree rt = ref_view(rf);
         const uint64_t total = qs_table_tuples(ctx), chunk = 1u << 22;
         const char magic[8] = {'Q', 'S', 'Q', 'I', 'C', '0', '1', 0};
         const uint32_t n32 = rt.n_taxa, zero = 0;
@@ -399,59 +343,38 @@ public:
         std::cout << "It took: " << std::chrono::duration_cast<std::chrono::microseconds>(end - begin).count()
                   << " microseconds." << std::endl;
         begin = std::chrono::steady_clock::now();
-        const RefFlat &rf = quartetCounterLookup->reference();
-        qs_ref_tree rt;
-        rt.n_nodes = (uint32_t)refTree.node_count(); rt.n_taxa = (uint32_t)n;
-        rt.parent = rf.parent.data(); rt.leaf_node = rf.leaf_node.data();
-        std::vector<double> lq(rt.n_nodes), qp(rt.n_nodes), eqp(rt.n_nodes);
-        int bif = 0;
-        if (qs_score(quartetCounterLookup->context(), &rt,
-                     (opt.qp_exact64 ? QS_SCORE_QP_EXACT64 : QS_SCORE_QP_WRAP32) | (opt.root_as_edge ? QS_SCORE_ROOT_AS_EDGE : 0u) |
-                         ((enforceSmallMem || opt.savemem_lookups) ? QS_SCORE_SAVEMEM_LOOKUPS : 0u),
-                     lq.data(), qp.data(), eqp.data(), &bif) != QS_OK)
-            throw std::runtime_error(qs_last_error(quartetCounterLookup->context()));
+        opt.savemem_lookups = enforceSmallMem || opt.savemem_lookups;
+        scores = score_table(context(), ref_view(reference()), score_flags(opt));
         if (opt.trace) {
             float ph[6] = {0, 0, 0, 0, 0, 0};
             (void)qs_last_score_ms(quartetCounterLookup->context(), ph);
             std::fprintf(stderr, "[trace] qs_score %.2f ms: set-up %.2f, pass 1 %.2f, pass 2 / log filter %.2f, wait + copies %.2f, host finish %.2f; log %llu records\n",
                          ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], (unsigned long long)qs_last_score_log(quartetCounterLookup->context()));
         }
-        // edge e = edge above node e+1 (preorder)
-        LQICScores.assign(lq.begin() + 1, lq.end());
-        if (bif) {
-            std::cout << "The reference tree is bifurcating.\n";
-            QPICScores.assign(qp.begin() + 1, qp.end());
-            EQPICScores.assign(eqp.begin() + 1, eqp.end());
-        } else {
-            std::cout << "The reference tree is multifurcating.\n";
-        }
+        std::cout << (scores.bifurcating ? "The reference tree is bifurcating.\n" : "The reference tree is multifurcating.\n");
         end = std::chrono::steady_clock::now();
         std::cout << "Finished computing scores.\n";
         std::cout << "It took: " << std::chrono::duration_cast<std::chrono::microseconds>(end - begin).count()
                   << " microseconds." << std::endl;
     }
 
-    std::vector<double> getLQICScores() { return LQICScores; }
-    std::vector<double> getQPICScores() { return QPICScores; }
-    std::vector<double> getEQPICScores() { return EQPICScores; }
+    std::vector<double> getLQICScores() { return scores.lq; }
+    std::vector<double> getQPICScores() { return scores.qp; }
+    std::vector<double> getEQPICScores() { return scores.eqp; }
     // the context that holds the count table and the flattened reference tree (--also-ref remaps that table)
     qs_ctx *context() const { return quartetCounterLookup->context(); }
     const RefFlat &reference() const { return quartetCounterLookup->reference(); }
 
     // -q dump and its binary sidecar (print_raw_qic_scores / print_raw_qic_binary above)
     bool raw_rank_order = false;
-    void printRawQICScores(Tree const &refTree, const std::string &rawPath) {
-        print_raw_qic_scores(quartetCounterLookup->context(), quartetCounterLookup->reference(), refTree, rawPath, raw_threads, raw_rank_order);
-    }
-    void printRawQICBinary(Tree const &refTree, const std::string &path) {
-        print_raw_qic_binary(quartetCounterLookup->context(), quartetCounterLookup->reference(), refTree, path);
-    }
+    void printRawQICScores(const std::string &rawPath) { print_raw_qic_scores(context(), reference(), rawPath, raw_threads, raw_rank_order); }
+    void printRawQICBinary(const std::string &path) { print_raw_qic_binary(context(), reference(), path); }
     unsigned raw_threads = 0; // threads that format the -q file (0 = hardware concurrency)
 
 private:
     Tree referenceTree;
     bool verbose;
-    std::vector<double> LQICScores, QPICScores, EQPICScores;
+    EdgeScores scores;
     std::unique_ptr<QuartetCounterLookup<CINT>> quartetCounterLookup;
 };
 

@@ -232,11 +232,6 @@ void write_annotated(const Tree &tree, const std::string &path, const std::vecto
     out << write_newick(tree, comment) << "\n";
 }
 
-uint32_t score_flags(const Args &a) {
-    return (a.dev.qp_exact64 ? QS_SCORE_QP_EXACT64 : QS_SCORE_QP_WRAP32) | (a.dev.root_as_edge ? QS_SCORE_ROOT_AS_EDGE : 0u) |
-           (a.savemem ? QS_SCORE_SAVEMEM_LOOKUPS : 0u);
-}
-
 // --also-ref: everything that needs no GPU, before the device is touched -- the files parse, every tree holds exactly the
 // taxa of -r, no OUT exists or repeats -o or another OUT, and qs_score_check passes for every tree with the run's flags
 void check_also_refs(Args &a) {
@@ -266,10 +261,8 @@ void check_also_refs(Args &a) {
         if (!missing.empty() || !extra.empty())
             throw std::runtime_error("--also-ref " + x.ref + ": the taxa differ from those of the reference tree " + a.ref + " (missing: " +
                                      (missing.empty() ? "none" : missing) + "; extra: " + (extra.empty() ? "none" : extra) + ")");
-        qs_ref_tree rt;
-        rt.n_nodes = (uint32_t)x.tree.node_count(); rt.n_taxa = (uint32_t)fx.names.size();
-        rt.parent = fx.parent.data(); rt.leaf_node = fx.leaf_node.data();
-        if (qs_score_check(nullptr, &rt, score_flags(a)) != QS_OK) throw std::runtime_error("--also-ref " + x.ref + ": " + qs_last_error(nullptr));
+        const qs_ref_tree rt = ref_view(fx);
+        if (qs_score_check(nullptr, &rt, score_flags(a.dev)) != QS_OK) throw std::runtime_error("--also-ref " + x.ref + ": " + qs_last_error(nullptr));
     }
 }
 
@@ -289,26 +282,23 @@ void check_per_tree(const Args &a) {
 struct PerTree {
     size_t m = 0;
     int device = 0;
-    uint64_t *dev = nullptr;
+    qs::DevBuf<uint64_t> dev;
     std::vector<uint64_t> counts;
     std::vector<uint32_t> taxa;
-    ~PerTree() { if (dev) (void)hipFree(dev); }
     void hook(DeviceOptions &opt, const RefFlat &ref) {
         taxa.assign(m, 0);
         opt.after_count = [this, &ref](qs_ctx *ctx, const qs_device_batch *db, size_t i0, const BatchFlat &b) {
             if (!dev) {
-                if (hipSetDevice(device) != hipSuccess || hipMalloc((void **)&dev, std::max<size_t>(1, 4 * m) * 8) != hipSuccess)
+                if (hipSetDevice(device) != hipSuccess || dev.reserve(std::max<size_t>(1, 4 * m) * 8, nullptr) != hipSuccess)
                     throw std::runtime_error("--per-tree: Insufficient memory!");
             }
             for (uint32_t t = 0; t < b.n_trees; ++t) taxa[i0 + t] = b.leaf_off[t + 1] - b.leaf_off[t];
-            qs_ref_tree rt;
-            rt.n_nodes = (uint32_t)ref.parent.size(); rt.n_taxa = (uint32_t)ref.names.size();
-            rt.parent = ref.parent.data(); rt.leaf_node = ref.leaf_node.data();
-            if (qs_tree_agreement(ctx, &rt, db, dev + 4 * i0) != QS_OK) throw std::runtime_error(qs_last_error(ctx));
+            const qs_ref_tree rt = ref_view(ref);
+            if (qs_tree_agreement(ctx, &rt, db, dev.get() + 4 * i0) != QS_OK) throw std::runtime_error(qs_last_error(ctx));
         };
         opt.after_sync = [this](qs_ctx *) {
             counts.assign(4 * m, 0);
-            if (m && hipMemcpy(counts.data(), dev, 4 * m * 8, hipMemcpyDeviceToHost) != hipSuccess)
+            if (m && hipMemcpy(counts.data(), dev.get(), 4 * m * 8, hipMemcpyDeviceToHost) != hipSuccess)
                 throw std::runtime_error("--per-tree: download failed");
         };
     }
@@ -319,7 +309,7 @@ struct PerTree {
         char conc[64];
         for (size_t t = 0; t < m; ++t) {
             const uint64_t n = taxa[t], c = counts[4 * t], d = counts[4 * t + 1], re = counts[4 * t + 2], rr = counts[4 * t + 3];
-            const uint64_t q = n < 4 ? 0 : n * (n - 1) * (n - 2) * (n - 3) / 24;
+            const uint64_t q = c4(n);
             const uint64_t eo = re - c - d, ro = rr - c - d;
             if (c + d) std::snprintf(conc, sizeof conc, "%.6f", (double)c / (double)(c + d));
             else std::snprintf(conc, sizeof conc, "nan");
@@ -343,14 +333,12 @@ void check_per_taxon(const Args &a) {
 // --per-taxon: one qs_taxon_support over the counted (or loaded) table, 6 x n words downloaded, one TSV line per taxon
 void write_per_taxon(qs_ctx *ctx, const RefFlat &ref, int device, const std::string &path) {
     const size_t n = ref.names.size();
-    qs_ref_tree rt;
-    rt.n_nodes = (uint32_t)ref.parent.size(); rt.n_taxa = (uint32_t)n;
-    rt.parent = ref.parent.data(); rt.leaf_node = ref.leaf_node.data();
-    struct Dev { int64_t *p = nullptr; ~Dev() { if (p) (void)hipFree(p); } } dev;
-    if (hipSetDevice(device) != hipSuccess || hipMalloc((void **)&dev.p, 6 * n * 8) != hipSuccess) throw std::runtime_error("--per-taxon: Insufficient memory!");
-    if (qs_taxon_support(ctx, &rt, dev.p) != QS_OK || qs_sync(ctx) != QS_OK) throw std::runtime_error(std::string("--per-taxon: ") + qs_last_error(ctx));
+    const qs_ref_tree rt = ref_view(ref);
+    qs::DevBuf<int64_t> dev;
+    if (hipSetDevice(device) != hipSuccess || dev.reserve(6 * n * 8, nullptr) != hipSuccess) throw std::runtime_error("--per-taxon: Insufficient memory!");
+    if (qs_taxon_support(ctx, &rt, dev.get()) != QS_OK || qs_sync(ctx) != QS_OK) throw std::runtime_error(std::string("--per-taxon: ") + qs_last_error(ctx));
     std::vector<int64_t> w(6 * n);
-    if (hipMemcpy(w.data(), dev.p, 6 * n * 8, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("--per-taxon: download failed");
+    if (hipMemcpy(w.data(), dev.get(), 6 * n * 8, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("--per-taxon: download failed");
     int64_t conc = 0, disc = 0;   // of the whole table: every quartet is in four taxa's sums
     for (size_t x = 0; x < n; ++x) { conc += w[6 * x + 1]; disc += w[6 * x + 2]; }
     conc /= 4; disc /= 4;
@@ -388,18 +376,9 @@ void score_also_refs(const Args &a, qs_ctx *src, const RefFlat &primary, qs_ctx 
         const auto remap_us = std::chrono::duration_cast<std::chrono::microseconds>(remapped - begin).count();
         std::cout << "Remapped the count table in " << remap_us << " microseconds.\n";
         if (a.dev.trace) std::fprintf(stderr, "[trace] qs_table_remap for %s: %.2f ms\n", x.ref.c_str(), remap_us / 1000.0);
-        qs_ref_tree rt;
-        rt.n_nodes = (uint32_t)x.tree.node_count(); rt.n_taxa = (uint32_t)fx.names.size();
-        rt.parent = fx.parent.data(); rt.leaf_node = fx.leaf_node.data();
-        std::vector<double> lq(rt.n_nodes), qp(rt.n_nodes), eqp(rt.n_nodes);
-        int bif = 0;
-        if (qs_score(table, &rt, score_flags(a), lq.data(), qp.data(), eqp.data(), &bif) != QS_OK) throw std::runtime_error(qs_last_error(table));
-        std::cout << (bif ? "The reference tree is bifurcating.\n" : "The reference tree is multifurcating.\n");
-        // edge e = edge above node e+1 (preorder), as QuartetScoreComputer hands them out
-        const std::vector<double> lqic(lq.begin() + 1, lq.end()), none;
-        const std::vector<double> qpic = bif ? std::vector<double>(qp.begin() + 1, qp.end()) : none;
-        const std::vector<double> eqpic = bif ? std::vector<double>(eqp.begin() + 1, eqp.end()) : none;
-        write_annotated(x.tree, x.out, lqic, qpic, eqpic);
+        const EdgeScores sc = score_table(table, ref_view(fx), score_flags(a.dev));
+        std::cout << (sc.bifurcating ? "The reference tree is bifurcating.\n" : "The reference tree is multifurcating.\n");
+        write_annotated(x.tree, x.out, sc.lq, sc.qp, sc.eqp);
         std::cout << "Finished computing scores.\n";
         std::cout << "It took: " << std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - begin).count()
                   << " microseconds." << std::endl;
@@ -413,8 +392,8 @@ void run_multi(const Tree &referenceTree, const Args &a, size_t m, uint32_t coun
     const bool need_full = !a.raw.empty() || !a.raw_bin.empty();   // the -q dump walks the whole table on one GPU
     MultiGpuQuartetScoreComputer mg(referenceTree, a.eval, m, count_bits, a.gpus, need_full, a.dev);
     lqic = mg.scores.lq; qpic = mg.scores.qp; eqpic = mg.scores.eqp;
-    if (!a.raw.empty()) print_raw_qic_scores(mg.context0(), mg.reference(), referenceTree, a.raw, a.dev.ingest_threads, a.raw_rank_order);
-    if (!a.raw_bin.empty()) print_raw_qic_binary(mg.context0(), mg.reference(), referenceTree, a.raw_bin);
+    if (!a.raw.empty()) print_raw_qic_scores(mg.context0(), mg.reference(), a.raw, a.dev.ingest_threads, a.raw_rank_order);
+    if (!a.raw_bin.empty()) print_raw_qic_binary(mg.context0(), mg.reference(), a.raw_bin);
 }
 
 // --table-shards K [--gpus N]: the table cut into K shards by the largest taxon id, shard s on GPU s mod N; every GPU counts
@@ -433,7 +412,7 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
     const uint32_t bits = sizeof(CINT) <= 2 ? 16u : 32u;
     size_t n = 0;
     for (size_t v = 0; v < referenceTree.node_count(); ++v) n += referenceTree.is_leaf(v);
-    const uint64_t bytes = (uint64_t)n * (n - 1) * (n - 2) * (n - 3) / 24 * 3 * (bits / 8);
+    const uint64_t bytes = c4(n) * 3 * (bits / 8);
     const int gpus = std::max(1, a.gpus);
     if (a.table_shards >= 0 || a.gpus > 0) {
         // shards one device's free memory asks for (0 / unset = automatic); with --gpus N at least one shard per GPU
@@ -492,8 +471,8 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
     eqpic = qsc.getEQPICScores();
     qsc.raw_threads = a.dev.ingest_threads;
     qsc.raw_rank_order = a.raw_rank_order;
-    if (!a.raw.empty()) qsc.printRawQICScores(referenceTree, a.raw);
-    if (!a.raw_bin.empty()) qsc.printRawQICBinary(referenceTree, a.raw_bin);
+    if (!a.raw.empty()) qsc.printRawQICScores(a.raw);
+    if (!a.raw_bin.empty()) qsc.printRawQICBinary(a.raw_bin);
     if (!a.per_tree.empty()) per_tree.write(a.per_tree);
     if (!a.per_taxon.empty()) write_per_taxon(qsc.context(), qsc.reference(), a.dev.device, a.per_taxon);
     if (!a.also.empty()) {   // the primary tree's output first, exactly as without --also-ref
@@ -511,6 +490,7 @@ int main(int argc, char *argv[]) {
     int pr = parse(argc, argv, a);
     if (pr == 1) return 1;
     if (pr == 2) return 0;
+    a.dev.savemem_lookups = a.savemem;   // -s: the reference's compact table behind the lookups of a rooted reference tree
 
     std::ifstream infile(a.out);
     if (infile.good()) {
@@ -526,7 +506,6 @@ int main(int argc, char *argv[]) {
         return 1;
     }
     a.dev.ingest_threads = (unsigned)a.threads;
-    a.dev.savemem_lookups = a.savemem;   // -s: the reference's compact table behind the lookups of a rooted reference tree
     trace_mark(a.dev, "main: arguments parsed");
     // HIP start-up (~0.1-0.2 s: driver, device, code objects) begins NOW on a helper thread, while this thread reads and
     // splits the Newick files; the counter's own set-up thread then finds the runtime initialised
@@ -550,9 +529,7 @@ int main(int argc, char *argv[]) {
         // says so NOW and then does the same -- or ends at once with --fail-fast.
         if (a.savemem) {
             const RefFlat rf0 = flatten_reference(referenceTree);
-            qs_ref_tree rt0;
-            rt0.n_nodes = (uint32_t)referenceTree.node_count(); rt0.n_taxa = (uint32_t)rf0.names.size();
-            rt0.parent = rf0.parent.data(); rt0.leaf_node = rf0.leaf_node.data();
+            const qs_ref_tree rt0 = ref_view(rf0);
             if (qs_score_check(nullptr, &rt0, QS_SCORE_SAVEMEM_LOOKUPS | (a.dev.root_as_edge ? QS_SCORE_ROOT_AS_EDGE : 0u)) == QS_ERR_REFERENCE_THROWS) {
                 const std::string what = qs_last_error(nullptr);
                 if (a.fail_fast) throw std::runtime_error(what);

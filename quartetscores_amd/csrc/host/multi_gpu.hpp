@@ -26,6 +26,7 @@
 #include <dlfcn.h>
 
 #include <atomic>
+#include <deque>
 #include <future>
 #include <mutex>
 
@@ -73,11 +74,6 @@ private:
         if (r__ != ncclSuccess) throw std::runtime_error(std::string(#expr) + ": " + Rccl::get().GetErrorString(r__)); \
     } while (0)
 
-struct MultiGpuScores {
-    std::vector<double> lq, qp, eqp; // per edge (edge e = edge above node e + 1), qp / eqp empty for a multifurcating reference
-    bool bifurcating = false;
-};
-
 class MultiGpuQuartetScoreComputer {
 public:
     // count_bits 16 | 32 (by m like QuartetScores.cpp:115-147); need_full_table: all-reduce instead of reduce-scatter
@@ -87,16 +83,15 @@ public:
         int ndev = 0;
         QSM_HIP(hipGetDeviceCount(&ndev));
         if (opt.gpus_on_one_device && opt.reduce != "p2p") throw std::runtime_error("--gpus-on-one-device needs --reduce p2p (RCCL refuses two ranks on one device)");
-        if (n_gpus < 1 || opt.device < 0 || opt.device + (opt.gpus_on_one_device ? 1 : n_gpus) > ndev)   // the devices used are opt.device .. opt.device + n_gpus - 1
-            throw std::runtime_error("--gpus " + std::to_string(n_gpus) + " from --device " + std::to_string(opt.device) + ": " + std::to_string(ndev) + " device(s) visible");
+        check_device_range(opt, n_gpus, ndev);
         G_ = n_gpus;
         std::cout << "There are " << m << " evaluation trees.\n";
         std::cout << "The reference tree has " << ref_.names.size() << " taxa.\n";
         std::cout << "Counting on " << G_ << " GPU(s): trees split over the GPUs, one " << (opt_.reduce == "p2p" ? "peer-access " : "RCCL ") << (full_ ? "all-reduce" : "reduce-scatter") << " of the count table.\n";
         const auto t0 = std::chrono::steady_clock::now();
         ctx_.assign(G_, nullptr);
-        table_.assign(G_, nullptr);
-        send_.assign(G_, nullptr);
+        table_.resize(G_);
+        send_.resize(G_);
         // RCCL's communicators take 1.7-5.6 s to create (ncclCommInitAll), on a helper thread that starts NOW. Nothing but the
         // collective itself needs them: the GPUs' host threads create their contexts, allocate and parse meanwhile. By DEFAULT
         // (opt.comm_overlap = false, `--comm-overlap 0`) the workers wait for the communicators before their first launch: the
@@ -124,7 +119,7 @@ public:
             trace_mark(opt_, "main: tables reduced");
             const auto t1 = std::chrono::steady_clock::now();
             std::cout << "Finished counting quartets.\nIt took: " << std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count() << " microseconds." << std::endl;
-            score(refTree);
+            score();
             const auto t2 = std::chrono::steady_clock::now();
             std::cout << (scores.bifurcating ? "The reference tree is bifurcating.\n" : "The reference tree is multifurcating.\n");
             std::cout << "Finished computing scores.\nIt took: " << std::chrono::duration_cast<std::chrono::microseconds>(t2 - t1).count() << " microseconds." << std::endl;
@@ -137,7 +132,7 @@ public:
     MultiGpuQuartetScoreComputer(const MultiGpuQuartetScoreComputer &) = delete;
     MultiGpuQuartetScoreComputer &operator=(const MultiGpuQuartetScoreComputer &) = delete;
 
-    MultiGpuScores scores;
+    EdgeScores scores;
     qs_ctx *context0() const { return ctx_[0]; }        // holds the whole table after an all-reduce (-q)
     const RefFlat &reference() const { return ref_; }
 
@@ -148,7 +143,7 @@ private:
     bool full_;
     int G_ = 1;
     std::vector<qs_ctx *> ctx_;
-    std::vector<void *> table_, send_;        // send_: the two-cell wire words (binary full trees, u32 tables)
+    std::vector<qs::DevBuf<char>> table_, send_;        // send_: the two-cell wire words (binary full trees, u32 tables)
     std::vector<ncclComm_t> comms_;
     std::shared_future<void> comm_ready_;      // the communicators exist (count kernels start only after that)
     std::atomic<uint32_t> flags_and_{~0u};     // AND of qs_batch_flags over every batch of every GPU
@@ -163,8 +158,7 @@ private:
         for (int g = 0; g < (int)ctx_.size(); ++g) {
             if (ctx_[g]) qs_destroy(ctx_[g]);
             (void)hipSetDevice(dev_of(g));
-            if (table_[g]) (void)hipFree(table_[g]);
-            if (g < (int)send_.size() && send_[g]) (void)hipFree(send_[g]);
+            table_[g].reset(); send_[g].reset();
         }
         ctx_.clear(); table_.clear(); send_.clear();
     }
@@ -177,7 +171,7 @@ private:
         std::vector<std::exception_ptr> errs(G_);
         std::mutex io;
         // geometry of the padded table: N chunks of T tuples (T even: whole 32-bit words for u16 cells too)
-        tuples_ = (uint64_t)n * (n - 1) * (n - 2) * (n - 3) / 24;
+        tuples_ = c4(n);
         chunk_tuples_ = (tuples_ + G_ - 1) / G_;
         chunk_tuples_ = (chunk_tuples_ + 7) & ~(uint64_t)7;   // chunks start on 16-byte boundaries in every wire format (qs_sum_words)
         chunk_words_ = chunk_tuples_ * 3 * (bits_ / 8) / 4;
@@ -188,42 +182,26 @@ private:
                 if (qs_create(&ctx_[g], n, bits_, QS_FLAG_NONE, dev, nullptr, 0, 0) != QS_OK) throw std::runtime_error(qs_last_error(nullptr));
                 QSM_HIP(hipSetDevice(dev));
                 const size_t bytes = (size_t)chunk_words_ * 4 * G_;
-                if (hipMalloc(&table_[g], bytes) != hipSuccess) throw std::runtime_error("Insufficient memory!");
-                QSM_HIP(hipMemset(table_[g], 0, bytes));
-                if (qs_table_attach(ctx_[g], table_[g], bytes) != QS_OK) throw std::runtime_error(qs_last_error(ctx_[g]));
+                if (table_[g].reserve(bytes, nullptr) != hipSuccess) throw std::runtime_error("Insufficient memory!");
+                QSM_HIP(hipMemset(table_[g].get(), 0, bytes));
+                if (qs_table_attach(ctx_[g], table_[g].get(), bytes) != QS_OK) throw std::runtime_error(qs_last_error(ctx_[g]));
                 // the two-cell wire words (8 bytes per tuple) are allocated HERE, beside the parse of the first batch, not
                 // between the count and the collective; freed again if the trees turn out not to be binary and full
                 if (!full_ && bits_ == 32 && (opt_.algo & 0xFFu) != QS_ALGO_SCATTER && G_ > 1) {
                     const size_t sb = (size_t)chunk_tuples_ * 2 * 4 * G_;
-                    if (hipMalloc(&send_[g], sb) == hipSuccess) QSM_HIP(hipMemset(send_[g], 0, sb));   // padding tuples stay zero (synchronous: ordered before the pack kernel on the context's stream and the peers' reads)
-                    else { send_[g] = nullptr; (void)hipGetLastError(); }
+                    if (send_[g].reserve(sb, nullptr) == hipSuccess) QSM_HIP(hipMemset(send_[g].get(), 0, sb));   // padding tuples stay zero (synchronous: ordered before the pack kernel on the context's stream and the peers' reads)
+                    else (void)hipGetLastError();
                 }
                 const size_t lo = spans.size() * g / G_, hi = spans.size() * (g + 1) / G_;
                 const bool want_ranges = (opt_.algo & 0xFFu) == QS_ALGO_SCATTER;
-                std::vector<qs_device_batch *> in_flight;
-                try {
-                    for (size_t i0 = lo; i0 < hi; i0 += opt_.batch_trees) {
-                        const size_t i1 = std::min(hi, i0 + opt_.batch_trees);
-                        BatchFlat b = flatten_parallel(ef->text, spans, i0, i1, ref_.name_to_id, host_threads, want_ranges);
-                        qs_tree_batch hb;
-                        hb.n_trees = b.n_trees; hb.leaf_off = b.leaf_off.data(); hb.leaf_ids = b.leaf_ids.data(); hb.adj_depth = b.adj_depth.data();
-                        hb.node_off = want_ranges ? b.node_off.data() : nullptr; hb.rng_off = want_ranges ? b.rng_off.data() : nullptr;
-                        hb.ranges = b.ranges.data();
-                        if (in_flight.size() == 2) { qs_batch_free(ctx_[g], in_flight.front()); in_flight.erase(in_flight.begin()); }
-                        if (i0 == lo && comm_ready_.valid()) comm_ready_.wait();   // --comm-overlap 0: first launch not beside RCCL's set-up
-                        qs_device_batch *db = nullptr;
-                        if (qs_batch_upload(ctx_[g], &hb, &db) != QS_OK) throw std::runtime_error(qs_last_error(ctx_[g]));
-                        flags_and_.fetch_and(qs_batch_flags(db));
-                        in_flight.push_back(db);
-                        if (qs_count_batch(ctx_[g], db, opt_.algo) != QS_OK) throw std::runtime_error(qs_last_error(ctx_[g]));
-                    }
-                    if (qs_sync(ctx_[g]) != QS_OK) throw std::runtime_error(qs_last_error(ctx_[g]));
-                } catch (...) {
-                    (void)qs_sync(ctx_[g]);
-                    for (auto *db : in_flight) qs_batch_free(ctx_[g], db);
-                    throw;
+                BatchQueue queue(ctx_[g]);
+                for (size_t i0 = lo; i0 < hi; i0 += opt_.batch_trees) {
+                    const size_t i1 = std::min(hi, i0 + opt_.batch_trees);
+                    BatchFlat b = flatten_parallel(ef->text, spans, i0, i1, ref_.name_to_id, host_threads, want_ranges);
+                    if (i0 == lo && comm_ready_.valid()) comm_ready_.wait();   // --comm-overlap 0: first launch not beside RCCL's set-up
+                    flags_and_.fetch_and(qs_batch_flags(queue.submit(b, want_ranges, opt_.algo)));
                 }
-                for (auto *db : in_flight) qs_batch_free(ctx_[g], db);
+                queue.finish();
                 std::lock_guard<std::mutex> lk(io);
                 std::cout << "GPU " << dev << ": counted trees [" << lo << ", " << hi << ")" << std::endl;
             } catch (...) { errs[g] = std::current_exception(); }
@@ -250,9 +228,9 @@ private:
             group_open = true;
             for (int g = 0; g < G_; ++g) {
                 QSM_HIP(hipSetDevice(dev_of(g)));
-                uint32_t *buf = (uint32_t *)table_[g];
+                uint32_t *buf = (uint32_t *)table_[g].get();
                 if (full_) QSM_NCCL(Rccl::get().AllReduce(buf, buf, chunk_words_ * G_, ncclUint32, ncclSum, comms_[g], nullptr));
-                else if (two_cell) { uint32_t *sb = (uint32_t *)send_[g]; QSM_NCCL(Rccl::get().ReduceScatter(sb, sb + (size_t)g * words2, words2, ncclUint32, ncclSum, comms_[g], nullptr)); }
+                else if (two_cell) { uint32_t *sb = (uint32_t *)send_[g].get(); QSM_NCCL(Rccl::get().ReduceScatter(sb, sb + (size_t)g * words2, words2, ncclUint32, ncclSum, comms_[g], nullptr)); }
                 else QSM_NCCL(Rccl::get().ReduceScatter(buf, buf + (size_t)g * chunk_words_, chunk_words_, ncclUint32, ncclSum, comms_[g], nullptr));
             }
             group_open = false;
@@ -270,12 +248,12 @@ private:
     void pack_two_cell(bool two_cell, uint64_t words2) {
         for (int g = 0; g < G_; ++g) {
             QSM_HIP(hipSetDevice(dev_of(g)));
-            if (!two_cell) { if (send_[g]) { (void)hipFree(send_[g]); send_[g] = nullptr; } continue; }
+            if (!two_cell) { send_[g].reset(); continue; }
             if (!send_[g]) {
-                if (hipMalloc(&send_[g], (size_t)words2 * 4 * G_) != hipSuccess) throw std::runtime_error("Insufficient memory!");
-                QSM_HIP(hipMemset(send_[g], 0, (size_t)words2 * 4 * G_));
+                if (send_[g].reserve((size_t)words2 * 4 * G_, nullptr) != hipSuccess) throw std::runtime_error("Insufficient memory!");
+                QSM_HIP(hipMemset(send_[g].get(), 0, (size_t)words2 * 4 * G_));
             }
-            if (qs_table_pack32x2(ctx_[g], send_[g], (uint64_t)words2 * 4 * G_) != QS_OK) throw std::runtime_error(qs_last_error(ctx_[g]));
+            if (qs_table_pack32x2(ctx_[g], send_[g].get(), (uint64_t)words2 * 4 * G_) != QS_OK) throw std::runtime_error(qs_last_error(ctx_[g]));
         }
         if (two_cell) for (int g = 0; g < G_; ++g) if (qs_sync(ctx_[g]) != QS_OK) throw std::runtime_error(qs_last_error(ctx_[g]));
     }
@@ -286,13 +264,13 @@ private:
         for (int g = 0; g < G_; ++g) {
             QSM_HIP(hipSetDevice(dev_of(g)));
             const uint64_t lo = std::min<uint64_t>((uint64_t)g * chunk_tuples_, tuples_), cnt = std::min<uint64_t>(lo + chunk_tuples_, tuples_) - lo;
-            char *shard = (char *)table_[g] + (size_t)g * chunk_words_ * 4;
-            if (cnt && qs_unpack32x2(ctx_[g], (const uint32_t *)send_[g] + (size_t)g * words2, cnt, (uint64_t)m, shard) != QS_OK) throw std::runtime_error(qs_last_error(ctx_[g]));
+            char *shard = table_[g].get() + (size_t)g * chunk_words_ * 4;
+            if (cnt && qs_unpack32x2(ctx_[g], (const uint32_t *)send_[g].get() + (size_t)g * words2, cnt, (uint64_t)m, shard) != QS_OK) throw std::runtime_error(qs_last_error(ctx_[g]));
         }
         for (int g = 0; g < G_; ++g) {
             if (qs_sync(ctx_[g]) != QS_OK) throw std::runtime_error(qs_last_error(ctx_[g]));
             QSM_HIP(hipSetDevice(dev_of(g)));
-            (void)hipFree(send_[g]); send_[g] = nullptr;
+            send_[g].reset();
         }
     }
 
@@ -321,9 +299,9 @@ private:
             std::vector<const void *> src;
             char *dst;
             uint64_t nw;
-            if (full_) { dst = (char *)table_[0]; nw = chunk_words_ * G_; for (int p = 1; p < G_; ++p) src.push_back(table_[p]); }
-            else if (two_cell) { dst = (char *)send_[g] + (size_t)g * words2 * 4; nw = words2; for (int p = 0; p < G_; ++p) if (p != g) src.push_back((const char *)send_[p] + (size_t)g * words2 * 4); }
-            else { dst = (char *)table_[g] + (size_t)g * chunk_words_ * 4; nw = chunk_words_; for (int p = 0; p < G_; ++p) if (p != g) src.push_back((const char *)table_[p] + (size_t)g * chunk_words_ * 4); }
+            if (full_) { dst = table_[0].get(); nw = chunk_words_ * G_; for (int p = 1; p < G_; ++p) src.push_back(table_[p].get()); }
+            else if (two_cell) { dst = send_[g].get() + (size_t)g * words2 * 4; nw = words2; for (int p = 0; p < G_; ++p) if (p != g) src.push_back(send_[p].get() + (size_t)g * words2 * 4); }
+            else { dst = table_[g].get() + (size_t)g * chunk_words_ * 4; nw = chunk_words_; for (int p = 0; p < G_; ++p) if (p != g) src.push_back(table_[p].get() + (size_t)g * chunk_words_ * 4); }
             if (qs_sum_words(ctx_[g], dst, src.data(), (uint32_t)src.size(), nw) != QS_OK) throw std::runtime_error(qs_last_error(ctx_[g]));
         }
         for (int g = 0; g < (full_ ? 1 : G_); ++g) if (qs_sync(ctx_[g]) != QS_OK) throw std::runtime_error(qs_last_error(ctx_[g]));
@@ -331,64 +309,37 @@ private:
         for (int g = 0; g < G_; ++g) (void)qs_set_tuning(ctx_[g], QS_TUNE_TABLE_TREES, (uint64_t)m);
     }
 
-    void score(Tree const &refTree) {
-        qs_ref_tree rt;
-        rt.n_nodes = (uint32_t)refTree.node_count(); rt.n_taxa = (uint32_t)ref_.names.size();
-        rt.parent = ref_.parent.data(); rt.leaf_node = ref_.leaf_node.data();
-        const uint32_t flags = (opt_.qp_exact64 ? QS_SCORE_QP_EXACT64 : QS_SCORE_QP_WRAP32) | (opt_.root_as_edge ? QS_SCORE_ROOT_AS_EDGE : 0u) |
-                                   (opt_.savemem_lookups ? QS_SCORE_SAVEMEM_LOOKUPS : 0u);
-        std::vector<double> lq(rt.n_nodes), qp(rt.n_nodes), eqp(rt.n_nodes);
-        int bif = 0;
-        if (full_) {   // every GPU holds the whole table: GPU 0 scores alone
-            if (qs_score(ctx_[0], &rt, flags, lq.data(), qp.data(), eqp.data(), &bif) != QS_OK) throw std::runtime_error(qs_last_error(ctx_[0]));
-        } else {
-            const size_t P = (size_t)qs_score_pair_slots(&rt);
-            if (P == 0) throw std::runtime_error("bad reference tree");
-            std::vector<int64_t *> d_sums(G_, nullptr), d_min(G_, nullptr), d_cand(G_, nullptr);
-            std::vector<int64_t> sums(P * 3, 0), mins(P, INT64_MAX), cand((size_t)G_ * P * QS_SCORE_CAND_SLOTS), extra;
-            auto free_all = [&]() {
-                for (int g = 0; g < G_; ++g) { (void)hipSetDevice(dev_of(g)); (void)hipFree(d_sums[g]); (void)hipFree(d_min[g]); (void)hipFree(d_cand[g]); }
-            };
-            try {
-                std::vector<int64_t> part_s(P * 3), part_m(P);
-                for (int g = 0; g < G_; ++g) {   // pass 1 on every GPU (asynchronous), on its shard of the reduced table
-                    QSM_HIP(hipSetDevice(dev_of(g)));
-                    QSM_HIP(hipMalloc((void **)&d_sums[g], P * 3 * 8)); QSM_HIP(hipMalloc((void **)&d_min[g], P * 8)); QSM_HIP(hipMalloc((void **)&d_cand[g], P * QS_SCORE_CAND_SLOTS * 8));
-                    const uint64_t lo = std::min<uint64_t>((uint64_t)g * chunk_tuples_, tuples_), cnt = std::min<uint64_t>(lo + chunk_tuples_, tuples_) - lo;
-                    const char *shard = (const char *)table_[g] + (size_t)g * chunk_words_ * 4;
-                    if (qs_score_set_view(ctx_[g], shard, bits_, lo, cnt) != QS_OK) throw std::runtime_error(qs_last_error(ctx_[g]));
-                    if (qs_score_pass1(ctx_[g], &rt, d_sums[g], d_min[g]) != QS_OK) throw std::runtime_error(qs_last_error(ctx_[g]));
-                }
-                for (int g = 0; g < G_; ++g) {   // SUM / MIN over the shards on the host (a few MB)
-                    QSM_HIP(hipSetDevice(dev_of(g)));
-                    QSM_HIP(hipMemcpy(part_s.data(), d_sums[g], P * 3 * 8, hipMemcpyDeviceToHost));
-                    QSM_HIP(hipMemcpy(part_m.data(), d_min[g], P * 8, hipMemcpyDeviceToHost));
-                    for (size_t i = 0; i < P * 3; ++i) sums[i] = (int64_t)((uint64_t)sums[i] + (uint64_t)part_s[i]);
-                    for (size_t i = 0; i < P; ++i) mins[i] = std::min(mins[i], part_m[i]);
-                }
-                for (int g = 0; g < G_; ++g) {
-                    QSM_HIP(hipSetDevice(dev_of(g)));
-                    QSM_HIP(hipMemcpy(d_min[g], mins.data(), P * 8, hipMemcpyHostToDevice));
-                    if (qs_score_pass2(ctx_[g], &rt, d_min[g], d_cand[g]) != QS_OK) throw std::runtime_error(qs_last_error(ctx_[g]));
-                }
-                for (int g = 0; g < G_; ++g) {
-                    QSM_HIP(hipSetDevice(dev_of(g)));
-                    int64_t *list = nullptr;
-                    uint64_t k = 0;
-                    if (qs_score_overflow(ctx_[g], &rt, d_min[g], d_cand[g], &list, &k) != QS_OK) throw std::runtime_error(qs_last_error(ctx_[g]));
-                    if (k) { extra.insert(extra.end(), list, list + 4 * k); qs_free_host(list); }
-                    QSM_HIP(hipMemcpy(cand.data() + (size_t)g * P * QS_SCORE_CAND_SLOTS, d_cand[g], P * QS_SCORE_CAND_SLOTS * 8, hipMemcpyDeviceToHost));
-                    (void)qs_score_set_view(ctx_[g], nullptr, 0, 0, 0);
-                }
-            } catch (...) { free_all(); throw; }
-            free_all();
-            if (qs_score_finish(ctx_[0], &rt, flags, sums.data(), cand.data(), (uint32_t)G_, extra.empty() ? nullptr : extra.data(), extra.size() / 4,
-                                lq.data(), qp.data(), eqp.data(), &bif) != QS_OK)
-                throw std::runtime_error(qs_last_error(ctx_[0]));
+    void score() {
+        const qs_ref_tree rt = ref_view(ref_);
+        if (full_) { scores = score_table(ctx_[0], rt, score_flags(opt_)); return; }   // every GPU holds the whole table: GPU 0 scores alone
+        const size_t P = (size_t)qs_score_pair_slots(&rt);
+        if (P == 0) throw std::runtime_error("bad reference tree");
+        ScoreFold fold(P, (size_t)G_);
+        std::deque<ScoreAcc> acc;
+        for (int g = 0; g < G_; ++g) {   // pass 1 on every GPU (asynchronous), on its shard of the reduced table
+            QSM_HIP(hipSetDevice(dev_of(g)));
+            acc.emplace_back(dev_of(g), P);
+            const uint64_t lo = std::min<uint64_t>((uint64_t)g * chunk_tuples_, tuples_), cnt = std::min<uint64_t>(lo + chunk_tuples_, tuples_) - lo;
+            const char *shard = table_[g].get() + (size_t)g * chunk_words_ * 4;
+            if (qs_score_set_view(ctx_[g], shard, bits_, lo, cnt) != QS_OK) throw std::runtime_error(qs_last_error(ctx_[g]));
+            fold.pass1_launch(ctx_[g], rt, acc[g]);
         }
-        scores.bifurcating = bif != 0;
-        scores.lq.assign(lq.begin() + 1, lq.end());
-        if (bif) { scores.qp.assign(qp.begin() + 1, qp.end()); scores.eqp.assign(eqp.begin() + 1, eqp.end()); }
+        for (int g = 0; g < G_; ++g) {   // SUM / MIN over the shards on the host (a few MB)
+            QSM_HIP(hipSetDevice(dev_of(g)));
+            fold.pass1_fold(acc[g]);
+        }
+        for (int g = 0; g < G_; ++g) {
+            QSM_HIP(hipSetDevice(dev_of(g)));
+            fold.upload_mins(acc[g]);
+            fold.pass2_launch(ctx_[g], rt, acc[g]);
+        }
+        for (int g = 0; g < G_; ++g) {
+            QSM_HIP(hipSetDevice(dev_of(g)));
+            fold.pass2_collect(ctx_[g], rt, acc[g], (size_t)g, fold);
+            (void)qs_score_set_view(ctx_[g], nullptr, 0, 0, 0);
+        }
+        acc.clear();
+        scores = fold.finish(ctx_[0], rt, score_flags(opt_));
     }
 };
 

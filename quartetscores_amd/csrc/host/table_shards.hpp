@@ -29,11 +29,6 @@
 
 namespace qsh {
 
-struct ShardedTableScores {
-    std::vector<double> lq, qp, eqp; // per edge (edge e = edge above node e + 1), qp / eqp empty for a multifurcating reference
-    bool bifurcating = false;
-};
-
 class ShardedTableQuartetScoreComputer {
 public:
     enum Spill { SPILL_AUTO, SPILL_HOST, SPILL_RECOUNT };
@@ -80,15 +75,13 @@ public:
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device (this program has no CPU fallback)");
         // (--gpus-on-one-device, a test hook: the N "GPUs" are N host threads with their own contexts on device opt.device)
-        if (G_ < 1 || opt_.device < 0 || opt_.device + (opt_.gpus_on_one_device ? 1 : G_) > ndev)
-            throw std::runtime_error("--gpus " + std::to_string(G_) + " from --device " + std::to_string(opt_.device) + ": " + std::to_string(ndev) + " device(s) visible");
+        check_device_range(opt_, G_, ndev);
         std::cout << "There are " << m << " evaluation trees.\n";
         std::cout << "The reference tree has " << n << " taxa.\n";
         const auto t0 = std::chrono::steady_clock::now();
         // shard bounds in the largest id d (qs_shard_bounds): one resident shard per GPU -> balanced by the count kernel's work;
         // more shards than GPUs (a table that passes through the devices shard by shard) -> by the tuples held, C(d,4): memory
         // decides there. Empty shards (small n) are dropped
-        auto c4 = [](uint64_t x) { return x < 4 ? (uint64_t)0 : x * (x - 1) * (x - 2) * (x - 3) / 24; };
         const uint64_t total = c4(n);
         std::vector<uint32_t> bounds((size_t)n_shards + 1, 0);
         const uint32_t by = (n_shards > 1 && n_shards <= n_gpus) ? QS_SHARDS_BY_COST : QS_SHARDS_BY_TUPLES;
@@ -123,43 +116,29 @@ public:
                 batches_.push_back(flatten_parallel(ef->text, ef->spans, i0, std::min(m, i0 + opt_.batch_trees), ref_.name_to_id, threads, want_ranges));
             loadEvalFile(std::string(), true);
         }
-        qs_ref_tree rt;
-        rt.n_nodes = (uint32_t)refTree.node_count(); rt.n_taxa = n;
-        rt.parent = ref_.parent.data(); rt.leaf_node = ref_.leaf_node.data();
+        const qs_ref_tree rt = ref_view(ref_);
         const size_t P = (size_t)qs_score_pair_slots(&rt);
         if (P == 0) throw std::runtime_error("bad reference tree");
         P_ = P; rt_ = &rt; m_ = m;
 
-        std::vector<int64_t> sums(P * 3, 0), mins(P, INT64_MAX), cand(K * P * QS_SCORE_CAND_SLOTS), extra;
-        gpu_.assign((size_t)G_, PerGpu());
+        ScoreFold all(P, K);
+        gpu_ = std::vector<PerGpu>((size_t)G_);
         for (int g = 0; g < G_; ++g) {
             gpu_[g].dev = opt_.gpus_on_one_device ? opt_.device : opt_.device + g;
             for (size_t s = (size_t)g; s < K; s += (size_t)G_) gpu_[g].shards.push_back(s);
-            gpu_[g].sums.assign(P * 3, 0); gpu_[g].mins.assign(P, INT64_MAX);
+            gpu_[g].fold = ScoreFold(P);
             gpu_[g].spilled.resize(gpu_[g].shards.size());
         }
         try {
             run_on_all([&](PerGpu &w) { round1(w); });
-            for (const PerGpu &w : gpu_) {                     // SUM / MIN over the GPUs (host, a few MB)
-                for (size_t i = 0; i < P * 3; ++i) sums[i] = (int64_t)((uint64_t)sums[i] + (uint64_t)w.sums[i]);
-                for (size_t i = 0; i < P; ++i) mins[i] = std::min(mins[i], w.mins[i]);
-            }
+            for (const PerGpu &w : gpu_) all.merge(w.fold);   // SUM / MIN over the GPUs (host, a few MB)
             const auto t1 = std::chrono::steady_clock::now();
             std::cout << "lookup table size in bytes: " << table_bytes << "\n";
             std::cout << "Finished counting quartets.\nIt took: " << std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count() << " microseconds." << std::endl;
-            run_on_all([&](PerGpu &w) { round2(w, mins, cand); });
-            for (PerGpu &w : gpu_) extra.insert(extra.end(), w.extra.begin(), w.extra.end());
+            run_on_all([&](PerGpu &w) { round2(w, all); });
+            for (PerGpu &w : gpu_) all.extra.insert(all.extra.end(), w.fold.extra.begin(), w.fold.extra.end());
             release();
-            const uint32_t flags = (opt_.qp_exact64 ? QS_SCORE_QP_EXACT64 : QS_SCORE_QP_WRAP32) | (opt_.root_as_edge ? QS_SCORE_ROOT_AS_EDGE : 0u) |
-                                   (opt_.savemem_lookups ? QS_SCORE_SAVEMEM_LOOKUPS : 0u);
-            std::vector<double> lq(rt.n_nodes), qp(rt.n_nodes), eqp(rt.n_nodes);
-            int bif = 0;
-            if (qs_score_finish(nullptr, &rt, flags, sums.data(), cand.data(), (uint32_t)K, extra.empty() ? nullptr : extra.data(), extra.size() / 4,
-                                lq.data(), qp.data(), eqp.data(), &bif) != QS_OK)
-                throw std::runtime_error(qs_last_error(nullptr));
-            scores.bifurcating = bif != 0;
-            scores.lq.assign(lq.begin() + 1, lq.end());
-            if (bif) { scores.qp.assign(qp.begin() + 1, qp.end()); scores.eqp.assign(eqp.begin() + 1, eqp.end()); }
+            scores = all.finish(nullptr, rt, score_flags(opt_));
             const auto t2 = std::chrono::steady_clock::now();
             std::cout << (scores.bifurcating ? "The reference tree is bifurcating.\n" : "The reference tree is multifurcating.\n");
             std::cout << "Finished computing scores.\nIt took: " << std::chrono::duration_cast<std::chrono::microseconds>(t2 - t1).count() << " microseconds." << std::endl;
@@ -174,18 +153,18 @@ public:
     ShardedTableQuartetScoreComputer(const ShardedTableQuartetScoreComputer &) = delete;
     ShardedTableQuartetScoreComputer &operator=(const ShardedTableQuartetScoreComputer &) = delete;
 
-    ShardedTableScores scores;
+    EdgeScores scores;
 
 private:
     struct PerGpu {
         int dev = 0;
         std::vector<size_t> shards;            // shard numbers this GPU owns (s mod N == g), in order
-        std::vector<int64_t> sums, mins, extra; // host accumulators of this GPU's shards
+        ScoreFold fold;                        // host accumulators of this GPU's shards (its candidates go to the run's fold)
         std::vector<std::string> spilled;      // spill = host: the finished shards
         qs_ctx *resident = nullptr;            // the one shard of a GPU that owns exactly one: stays on the device
-        int64_t *d_sums = nullptr, *d_min = nullptr, *d_cand = nullptr;
-        void *table_buf = nullptr;             // a GPU with several shards: ONE allocation of the largest, attached to each in turn
-        uint64_t table_buf_bytes = 0;          // (allocating and freeing 34 GB per shard cost ~1 s of the ~1.05 s a shard took)
+        std::unique_ptr<ScoreAcc> acc;
+        qs::DevBuf<char> table_buf;            // a GPU with several shards: ONE allocation of the largest, attached to each in turn
+                                               // (allocating and freeing 34 GB per shard cost ~1 s of the ~1.05 s a shard took)
     };
     RefFlat ref_;
     DeviceOptions opt_;
@@ -213,19 +192,14 @@ private:
         for (PerGpu &w : gpu_) {
             (void)hipSetDevice(w.dev);
             if (w.resident) { qs_destroy(w.resident); w.resident = nullptr; }
-            (void)hipFree(w.d_sums); (void)hipFree(w.d_min); (void)hipFree(w.d_cand); (void)hipFree(w.table_buf);
-            w.d_sums = w.d_min = w.d_cand = nullptr; w.table_buf = nullptr; w.table_buf_bytes = 0;
+            w.acc.reset(); w.table_buf.reset();
         }
     }
-    static void hip_ok(hipError_t e, const char *what) { if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e)); }
 
     void round1(PerGpu &w) {
         if (w.shards.empty()) return;
         hip_ok(hipSetDevice(w.dev), "hipSetDevice");
-        if (hipMalloc((void **)&w.d_sums, P_ * 3 * 8) != hipSuccess || hipMalloc((void **)&w.d_min, P_ * 8) != hipSuccess ||
-            hipMalloc((void **)&w.d_cand, P_ * QS_SCORE_CAND_SLOTS * 8) != hipSuccess)
-            throw std::runtime_error("Insufficient memory!");
-        std::vector<int64_t> part_s(P_ * 3), part_m(P_);
+        w.acc.reset(new ScoreAcc(w.dev, P_));
         for (size_t i = 0; i < w.shards.size(); ++i) {
             const size_t k = w.shards[i];
             qs_ctx *ctx = open_shard(k, w);
@@ -233,11 +207,9 @@ private:
             try {
                 count_all(ctx);
                 trace_mark(opt_, "shard: counted");
-                if (qs_score_pass1(ctx, rt_, w.d_sums, w.d_min) != QS_OK || qs_sync(ctx) != QS_OK) throw std::runtime_error(qs_last_error(ctx));
-                hip_ok(hipMemcpy(part_s.data(), w.d_sums, P_ * 3 * 8, hipMemcpyDeviceToHost), "copy of the score sums");
-                hip_ok(hipMemcpy(part_m.data(), w.d_min, P_ * 8, hipMemcpyDeviceToHost), "copy of the score minima");
-                for (size_t j = 0; j < P_ * 3; ++j) w.sums[j] = (int64_t)((uint64_t)w.sums[j] + (uint64_t)part_s[j]);
-                for (size_t j = 0; j < P_; ++j) w.mins[j] = std::min(w.mins[j], part_m[j]);
+                w.fold.pass1_launch(ctx, *rt_, *w.acc);
+                if (qs_sync(ctx) != QS_OK) throw std::runtime_error(qs_last_error(ctx));
+                w.fold.pass1_fold(*w.acc);
                 trace_mark(opt_, "shard: score pass 1 done");
                 const uint64_t bytes = qs_table_bytes(ctx);
                 if (w.shards.size() == 1) { w.resident = ctx; ctx = nullptr; }
@@ -252,10 +224,10 @@ private:
         }
     }
 
-    void round2(PerGpu &w, const std::vector<int64_t> &mins, std::vector<int64_t> &cand) {
+    void round2(PerGpu &w, ScoreFold &all) {
         if (w.shards.empty()) return;
         hip_ok(hipSetDevice(w.dev), "hipSetDevice");
-        hip_ok(hipMemcpy(w.d_min, mins.data(), P_ * 8, hipMemcpyHostToDevice), "copy of the minima");
+        all.upload_mins(*w.acc);
         for (size_t i = 0; i < w.shards.size(); ++i) {
             const size_t k = w.shards[i];
             qs_ctx *ctx = w.resident;
@@ -272,12 +244,8 @@ private:
                 } catch (...) { qs_destroy(ctx); throw; }
             }
             try {
-                if (qs_score_pass2(ctx, rt_, w.d_min, w.d_cand) != QS_OK) throw std::runtime_error(qs_last_error(ctx));
-                int64_t *list = nullptr;
-                uint64_t cnt = 0;
-                if (qs_score_overflow(ctx, rt_, w.d_min, w.d_cand, &list, &cnt) != QS_OK) throw std::runtime_error(qs_last_error(ctx));
-                if (cnt) { w.extra.insert(w.extra.end(), list, list + 4 * cnt); qs_free_host(list); }
-                hip_ok(hipMemcpy(cand.data() + k * P_ * QS_SCORE_CAND_SLOTS, w.d_cand, P_ * QS_SCORE_CAND_SLOTS * 8, hipMemcpyDeviceToHost), "copy of the candidates");
+                w.fold.pass2_launch(ctx, *rt_, *w.acc);
+                w.fold.pass2_collect(ctx, *rt_, *w.acc, k, all);   // (slot k of `all` is this thread's alone)
             } catch (...) { qs_destroy(ctx); throw; }
             qs_destroy(ctx);
         }
@@ -293,41 +261,21 @@ private:
         if (w.shards.size() == 1) rc = qs_table_alloc(ctx);
         else {
             if (!w.table_buf) {
-                auto c4 = [](uint64_t x) { return x < 4 ? (uint64_t)0 : x * (x - 1) * (x - 2) * (x - 3) / 24; };
                 uint64_t most = 0;
                 for (size_t s : w.shards) most = std::max(most, (c4(shards_[s].second) - c4(shards_[s].first)) * 3 * (bits_ / 8));
                 most = (most + 3) & ~(uint64_t)3;
-                if (hipMalloc(&w.table_buf, (size_t)most) != hipSuccess) { (void)hipGetLastError(); qs_destroy(ctx); throw std::runtime_error("Insufficient memory!"); }
-                w.table_buf_bytes = most;
+                if (w.table_buf.reserve((size_t)most, nullptr) != hipSuccess) { (void)hipGetLastError(); qs_destroy(ctx); throw std::runtime_error("Insufficient memory!"); }
             }
-            rc = qs_table_attach(ctx, w.table_buf, w.table_buf_bytes);
+            rc = qs_table_attach(ctx, w.table_buf.get(), w.table_buf.bytes());
             if (rc == QS_OK) rc = qs_table_clear(ctx);
         }
         if (rc != QS_OK) { std::string e = qs_last_error(ctx); qs_destroy(ctx); throw std::runtime_error(e); }
         return ctx;
     }
     void count_all(qs_ctx *ctx) {
-        const bool want_ranges = (opt_.algo & 0xFFu) == QS_ALGO_SCATTER;
-        std::vector<qs_device_batch *> in_flight;
-        try {
-            for (const BatchFlat &b : batches_) {
-                qs_tree_batch hb;
-                hb.n_trees = b.n_trees; hb.leaf_off = b.leaf_off.data(); hb.leaf_ids = b.leaf_ids.data(); hb.adj_depth = b.adj_depth.data();
-                hb.node_off = want_ranges ? b.node_off.data() : nullptr; hb.rng_off = want_ranges ? b.rng_off.data() : nullptr;
-                hb.ranges = b.ranges.data();
-                if (in_flight.size() == 2) { qs_batch_free(ctx, in_flight.front()); in_flight.erase(in_flight.begin()); }
-                qs_device_batch *db = nullptr;
-                if (qs_batch_upload(ctx, &hb, &db) != QS_OK) throw std::runtime_error(qs_last_error(ctx));
-                in_flight.push_back(db);
-                if (qs_count_batch(ctx, db, opt_.algo) != QS_OK) throw std::runtime_error(qs_last_error(ctx));
-            }
-            if (qs_sync(ctx) != QS_OK) throw std::runtime_error(qs_last_error(ctx));
-        } catch (...) {
-            (void)qs_sync(ctx);
-            for (auto *db : in_flight) qs_batch_free(ctx, db);
-            throw;
-        }
-        for (auto *db : in_flight) qs_batch_free(ctx, db);
+        BatchQueue queue(ctx);
+        for (const BatchFlat &b : batches_) queue.submit(b, (opt_.algo & 0xFFu) == QS_ALGO_SCATTER, opt_.algo);
+        queue.finish();
     }
 };
 
