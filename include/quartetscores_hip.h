@@ -15,7 +15,8 @@
  *   qs_lookup                     QuartetCounterLookup::countQuartetOccurrences
  *                                 (QuartetCounterLookup.hpp:299-318)
  *   qs_table_*                    QuartetLookupTable<T> storage (quartet_lookup_table.hpp:19-228);
- *                                 qs_table_remap replaces nothing (the reference recounts per reference tree)
+ *                                 qs_table_remap replaces nothing (the reference recounts per reference tree), nor does
+ *                                 qs_table_restrict (the reference recounts per taxon set)
  *   qs_tree_agreement             replaces nothing in the reference (it reports no per-tree agreement)
  *   qs_taxon_support              replaces nothing in the reference (the nearest is printRawQICScores, :612-680: one text
  *                                 line per quartet, which a user would reduce per taxon on the host)
@@ -262,6 +263,19 @@ int qs_sum_words(qs_ctx *ctx, void *dst_device, const void *const *src_device, u
  * dst's previous contents are overwritten, its trees-counted becomes src's. The reference recounts per run: this replaces
  * nothing there (like qs_depth_clamp_plan). */
 int qs_table_remap(qs_ctx *dst, const qs_ctx *src, const uint16_t *src_id_of);
+
+/* The table of `src` restricted to a subset of its taxa, into `dst`'s table: dst has n_dst = its n_taxa in [4, src's n_taxa], and
+ * src_id_of[i], i < n_dst (host; validated as injective into [0, src's n_taxa): a repeated or out-of-range id is QS_ERR_ARG) is the id in
+ * src's order of the taxon with id i in dst's order. The topology a tree displays for a 4-set does not depend on the tree's other taxa, so
+ * this is the table a count of the pruned evaluation trees under the pruned reference tree would give -- pruning keeps the depth-first
+ * order of the leaves that remain, so for a pruned reference tree src_id_of is strictly increasing (the fast instance of the kernel); any
+ * injective map is taken (restrict and re-order in one pass), and with n_dst = src's n_taxa the result is qs_table_remap's. Everything else
+ * as qs_table_remap: whole-table contexts on the same device (a table shard: QS_ERR_UNSUPPORTED); both need a table (QS_ERR_STATE); cells
+ * 32 -> 32, 16 -> 16 or 16 -> 32 (narrowing: QS_ERR_ARG); n_dst > src's n_taxa: QS_ERR_ARG. Waits for src's stream, then runs
+ * asynchronously on dst's stream; dst's previous contents are overwritten and its trees-counted becomes src's (a tree pruned below four
+ * taxa still counts towards it; scores never depend on it). The reference rejects an evaluation leaf it does not know and recounts per
+ * run: this replaces nothing there. */
+int qs_table_restrict(qs_ctx *dst, const qs_ctx *src, const uint16_t *src_id_of);
 
 /* Writes the u32 table as a u16 table (same [rank][3] layout, 2 bytes per cell, padded to a whole 32-bit word)
  * into caller-owned device memory: the wire format for the multi-GPU all-reduce while all totals stay below 2^16

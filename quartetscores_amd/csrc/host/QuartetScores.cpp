@@ -12,12 +12,15 @@
 // --save-table / --load-table write / read the raw count table (resume without recounting).
 // --also-ref REF OUT (repeatable) scores further reference trees over the same taxa from the same count table: the table is
 // re-indexed into REF's lookup-id order (qs_table_remap) instead of being counted again.
+// --without-taxa NAMES OUT (repeatable) scores the -r tree without the taxa listed in NAMES from the same count table: the tree is
+// pruned (newick.hpp prune) and the table cut down to the kept taxa (qs_table_restrict) instead of pruning every tree and recounting.
 #include "QuartetScoreComputer.hpp"
 #include "multi_gpu.hpp"
 #include "table_shards.hpp"
 
 #include <cerrno>
 #include <set>
+#include <sstream>
 #include <cstdlib>
 #include <unistd.h>
 #include <chrono>
@@ -52,11 +55,19 @@ struct AlsoRef {
     Tree tree;
 };
 
+// --without-taxa: a file of taxon labels to drop and the file the annotated pruned -r tree goes to
+struct WithoutTaxa {
+    std::string names, out;
+    std::set<std::string> drop;
+    Tree tree;   // the -r tree without them
+};
+
 struct Args {
     std::string ref, eval, out, raw, raw_bin;
     std::string per_tree;   // --per-tree FILE: quartet agreement of every evaluation tree with -r (TSV)
     std::string per_taxon;  // --per-taxon FILE: quartet support per taxon of -r from the count table (TSV)
     std::vector<AlsoRef> also;
+    std::vector<WithoutTaxa> without;
     size_t threads = 0;
     bool verbose = false, savemem = false, raw_rank_order = false, fail_fast = false, clean_exit = false;
     int table_shards = -1;   // -1 = off (the whole table on the device); 0 = as many as the device's free memory asks for; K = K shards, one after the other (table_shards.hpp)
@@ -108,6 +119,11 @@ void usage(std::ostream &os) {
           "   --also-ref REF OUT  (repeatable) score the reference tree REF as well and write its annotated tree to OUT: the count\n"
           "                  table of -r is re-indexed into REF's taxon order instead of counting again. REF must hold the same\n"
           "                  taxa as -r; one GPU with the whole table (not with --gpus / --table-shards); works with --load-table\n"
+          "   --without-taxa NAMES OUT  (repeatable) score the -r tree without the taxa listed in NAMES (one label per line, as parsed and\n"
+          "                  unquoted; blank lines are skipped) as well and write the annotated pruned tree to OUT: the count table is cut\n"
+          "                  down to the kept taxa instead of pruning every tree and counting again. At least four taxa must remain; one\n"
+          "                  GPU with the whole table (not with --gpus / --table-shards); works with --load-table, --per-tree, --per-taxon\n"
+          "                  (both still the full -r tree) and beside --also-ref (whose trees are not pruned)\n"
           "   --per-tree F   write the quartet agreement of every evaluation tree with the -r tree to F (TSV, one line per tree in\n"
           "                  -e order after a header: tree taxa quartets concordant discordant eval_only ref_only unresolved\n"
           "                  concordance); computed on the device behind the counting; one GPU that counts (not with --gpus /\n"
@@ -200,6 +216,16 @@ int parse(int argc, char **argv, Args &a) {
             x.out = argv[++i];
             a.also.push_back(std::move(x));
         }
+        else if (f == "--without-taxa") {
+            if (i + 2 >= argc || argv[i + 2][0] == '-') {
+                std::cerr << "ERROR: Missing a value for this argument! for arg --without-taxa (it takes two: NAMES OUT)" << std::endl;
+                return 1;
+            }
+            WithoutTaxa x;
+            x.names = argv[++i];
+            x.out = argv[++i];
+            a.without.push_back(std::move(x));
+        }
         else if (f == "--version") { std::cout << argv[0] << "  version: 1.0.1 (" << qs_version() << ")" << std::endl; return 2; }
         else if (f == "-h" || f == "--help") { usage(std::cout); return 2; }
         else { std::cerr << "ERROR: Couldn't find match for argument for arg " << f << std::endl; return 1; }
@@ -266,6 +292,43 @@ void check_also_refs(Args &a) {
     }
 }
 
+// --without-taxa: everything that needs no GPU, before the device is touched -- every name is a taxon of -r, at least one is dropped
+// and four are kept, no OUT exists or repeats another output, and qs_score_check passes for every pruned tree with the run's flags
+void check_without_taxa(Args &a) {
+    if (a.without.empty()) return;
+    if (a.gpus > 0 || a.table_shards >= 0)
+        throw std::runtime_error("--without-taxa works on one GPU with the whole table: omit --gpus / --table-shards");
+    Tree primary;
+    {
+        const std::string text = slurp(a.ref);
+        NewickReader rr(text);
+        if (!rr.next(primary)) throw std::runtime_error("empty reference tree file");
+    }
+    const RefFlat rf = flatten_reference(primary);
+    std::set<std::string> outs{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon};
+    for (const AlsoRef &x : a.also) outs.insert(x.out);
+    for (WithoutTaxa &x : a.without) {
+        const std::string what = "--without-taxa " + x.names + ": ";
+        if (!outs.insert(x.out).second) throw std::runtime_error(what + "the output file " + x.out + " is given twice");
+        if (std::ifstream(x.out).good()) throw std::runtime_error(what + "the output file " + x.out + " already exists");
+        std::istringstream lines(slurp(x.names));
+        for (std::string line; std::getline(lines, line);) {
+            const size_t b = line.find_first_not_of(" \t\r"), e = line.find_last_not_of(" \t\r");
+            if (b == std::string::npos) continue;
+            const std::string name = line.substr(b, e - b + 1);
+            if (!rf.name_to_id.count(name)) throw std::runtime_error(what + "the taxon " + name + " is not in the reference tree " + a.ref);
+            x.drop.insert(name);
+        }
+        if (x.drop.empty()) throw std::runtime_error(what + "the list of taxa is empty");
+        if (rf.names.size() < x.drop.size() + 4)
+            throw std::runtime_error(what + "fewer than four taxa are left (" + std::to_string(rf.names.size() - x.drop.size()) + " of " + std::to_string(rf.names.size()) + ")");
+        prune(primary, x.drop, x.tree);
+        const RefFlat fx = flatten_reference(x.tree);
+        const qs_ref_tree rt = ref_view(fx);
+        if (qs_score_check(nullptr, &rt, score_flags(a.dev)) != QS_OK) throw std::runtime_error(what + qs_last_error(nullptr));
+    }
+}
+
 // --per-tree: refused before the device is touched where no trees are counted on one GPU, and where FILE exists or is another output
 void check_per_tree(const Args &a) {
     if (a.per_tree.empty()) return;
@@ -273,6 +336,7 @@ void check_per_tree(const Args &a) {
         throw std::runtime_error("--per-tree needs the evaluation trees counted on one GPU: omit --gpus / --table-shards / --load-table");
     std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_taxon};
     for (const AlsoRef &x : a.also) others.insert(x.out);
+    for (const WithoutTaxa &x : a.without) others.insert(x.out);
     if (others.count(a.per_tree)) throw std::runtime_error("--per-tree: " + a.per_tree + " is also another output file");
     if (std::ifstream(a.per_tree).good()) throw std::runtime_error("--per-tree: the output file " + a.per_tree + " already exists");
 }
@@ -326,6 +390,7 @@ void check_per_taxon(const Args &a) {
         throw std::runtime_error("--per-taxon needs the whole count table on one GPU: omit --gpus / --table-shards");
     std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree};
     for (const AlsoRef &x : a.also) others.insert(x.out);
+    for (const WithoutTaxa &x : a.without) others.insert(x.out);
     if (others.count(a.per_taxon)) throw std::runtime_error("--per-taxon: " + a.per_taxon + " is also another output file");
     if (std::ifstream(a.per_taxon).good()) throw std::runtime_error("--per-taxon: the output file " + a.per_taxon + " already exists");
 }
@@ -377,6 +442,33 @@ void score_also_refs(const Args &a, qs_ctx *src, const RefFlat &primary, qs_ctx 
         std::cout << "Remapped the count table in " << remap_us << " microseconds.\n";
         if (a.dev.trace) std::fprintf(stderr, "[trace] qs_table_remap for %s: %.2f ms\n", x.ref.c_str(), remap_us / 1000.0);
         const EdgeScores sc = score_table(table, ref_view(fx), score_flags(a.dev));
+        std::cout << (sc.bifurcating ? "The reference tree is bifurcating.\n" : "The reference tree is multifurcating.\n");
+        write_annotated(x.tree, x.out, sc.lq, sc.qp, sc.eqp);
+        std::cout << "Finished computing scores.\n";
+        std::cout << "It took: " << std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - begin).count()
+                  << " microseconds." << std::endl;
+    }
+}
+
+// --without-taxa, after the primary tree's output is written: per set a context of the kept taxa on `table` (allocated before the
+// counting for the largest of them), the count table cut down into it, scored and written
+void score_without_taxa(const Args &a, qs_ctx *src, const RefFlat &primary, uint32_t bits, const qs::DevBuf<char> &table) {
+    for (const WithoutTaxa &x : a.without) {
+        const auto begin = std::chrono::steady_clock::now();
+        std::cout << "Scoring the reference tree without " << x.drop.size() << " taxa (" << x.names << ") from the same count table.\n";
+        const RefFlat fx = flatten_reference(x.tree);
+        std::vector<uint16_t> src_id_of(fx.names.size());
+        for (size_t i = 0; i < fx.names.size(); ++i) src_id_of[i] = (uint16_t)primary.name_to_id.at(fx.names[i]);
+        qs_ctx *ctx = nullptr;
+        if (qs_create(&ctx, (uint32_t)fx.names.size(), bits, QS_FLAG_NONE, a.dev.device, nullptr, 0, 0) != QS_OK) throw std::runtime_error(qs_last_error(nullptr));
+        struct Guard { qs_ctx *c; ~Guard() { qs_destroy(c); } } guard{ctx};   // (waits for the context's stream; the table stays the caller's)
+        if (qs_table_attach(ctx, table.get(), table.bytes()) != QS_OK) throw std::runtime_error(qs_last_error(ctx));
+        const auto attached = std::chrono::steady_clock::now();   // the restrict alone is timed, not the set-up in front of it
+        if (qs_table_restrict(ctx, src, src_id_of.data()) != QS_OK || qs_sync(ctx) != QS_OK) throw std::runtime_error(qs_last_error(ctx));
+        const auto restrict_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - attached).count();
+        std::cout << "Restricted the count table in " << restrict_us << " microseconds.\n";
+        if (a.dev.trace) std::fprintf(stderr, "[trace] qs_table_restrict for %s: %.2f ms\n", x.names.c_str(), restrict_us / 1000.0);
+        const EdgeScores sc = score_table(ctx, ref_view(fx), score_flags(a.dev));
         std::cout << (sc.bifurcating ? "The reference tree is bifurcating.\n" : "The reference tree is multifurcating.\n");
         write_annotated(x.tree, x.out, sc.lq, sc.qp, sc.eqp);
         std::cout << "Finished computing scores.\n";
@@ -453,6 +545,22 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
         if (qs_table_alloc(also_table) != QS_OK) throw std::runtime_error(std::string("--also-ref: ") + qs_last_error(also_table));
         trace_mark(a.dev, "main: --also-ref table allocated");
     }
+    // --without-taxa: likewise one table for the largest set of kept taxa, which every set's context attaches in its turn
+    std::unique_ptr<qs::DevBuf<char>> without_holder(new qs::DevBuf<char>());
+    qs::DevBuf<char> &without_table = *without_holder;
+    if (!a.without.empty()) {
+        size_t kept = 0;
+        for (const WithoutTaxa &x : a.without) kept = std::max(kept, x.tree.leaf_count());
+        // qs_table_bytes of a context of `kept` taxa (C(kept,4) tuples of three cells; computed here because no such context exists
+        // yet) plus qs_table_alloc's 16 bytes of padding: qs_table_attach checks the size against qs_table_bytes for every set
+        const size_t need = (size_t)(c4(kept) * 3 * (bits / 8)) + 16;
+        size_t freeb = 0, total = 0;
+        hip_ok(hipSetDevice(a.dev.device), "--without-taxa: hipSetDevice");
+        hip_ok(hipMemGetInfo(&freeb, &total), "--without-taxa: hipMemGetInfo");
+        if (need + bytes + (64u << 20) > freeb || without_table.reserve(need, nullptr) != hipSuccess)   // (the -r tree's table comes on top)
+            throw std::runtime_error("--without-taxa: Insufficient memory!");
+        trace_mark(a.dev, "main: --without-taxa table allocated");
+    }
     // (without --clean-exit the computer is never destroyed: freeing a 17-34 GB table and the context is work the exiting process
     // leaves to the driver -- main ends with std::_Exit once the output is written)
     PerTree per_tree;
@@ -475,11 +583,12 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
     if (!a.raw_bin.empty()) qsc.printRawQICBinary(a.raw_bin);
     if (!a.per_tree.empty()) per_tree.write(a.per_tree);
     if (!a.per_taxon.empty()) write_per_taxon(qsc.context(), qsc.reference(), a.dev.device, a.per_taxon);
-    if (!a.also.empty()) {   // the primary tree's output first, exactly as without --also-ref
+    if (!a.also.empty() || !a.without.empty()) {   // the primary tree's output first, exactly as without --also-ref / --without-taxa
         write_annotated(referenceTree, a.out, lqic, qpic, eqpic);
         score_also_refs(a, qsc.context(), qsc.reference(), also_table);
+        score_without_taxa(a, qsc.context(), qsc.reference(), bits, without_table);
     }
-    if (!a.clean_exit) (void)holder.release();
+    if (!a.clean_exit) { (void)holder.release(); (void)without_holder.release(); }
 }
 
 } // namespace
@@ -499,6 +608,7 @@ int main(int argc, char *argv[]) {
     }
     try {
         check_also_refs(a);
+        check_without_taxa(a);
         check_per_tree(a);
         check_per_taxon(a);
     } catch (const std::exception &e) {
@@ -549,7 +659,7 @@ int main(int argc, char *argv[]) {
         else if (m < (size_t(1) << 32)) run<uint32_t>(referenceTree, a, m, lqic, qpic, eqpic);
         else throw std::runtime_error("more than 2^32 evaluation trees are not supported");
 
-        if (a.also.empty()) write_annotated(referenceTree, a.out, lqic, qpic, eqpic);   // (with --also-ref: written by run())
+        if (a.also.empty() && a.without.empty()) write_annotated(referenceTree, a.out, lqic, qpic, eqpic);   // (else: written by run())
     } catch (const std::exception &e) {
         std::cerr << "ERROR: " << e.what() << std::endl;
         if (a.savemem && std::string(e.what()).rfind("id = ", 0) == 0)

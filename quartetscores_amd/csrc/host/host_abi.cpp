@@ -9,6 +9,7 @@
 
 #include <cstring>
 #include <fstream>
+#include <set>
 #include <sstream>
 #include <string>
 
@@ -113,6 +114,28 @@ int qsh_synth_trees(uint32_t n, uint64_t m, uint64_t seed, int kind, const char 
     }
 }
 void qsh_free_text(char *p) { free(p); }
+
+// The first tree of `text` without the leaves named in names[0 .. n_names) (newick.hpp prune), as Newick text in *out_text
+// (malloc'ed, qsh_free_text); an empty string when no leaf is left. For the tests, which hold it against newick.py's prune.
+int qsh_prune_newick(const char *text, uint64_t len, const char *const *names, uint32_t n_names, char **out_text) {
+    try {
+        if (!text || !out_text || (n_names && !names)) throw std::runtime_error("qsh_prune_newick: NULL argument");
+        const std::string in(text, (size_t)len);
+        NewickReader rr(in);
+        Tree t, pruned;
+        if (!rr.next(t)) throw std::runtime_error("qsh_prune_newick: empty input");
+        const std::set<std::string> drop(names, names + n_names);
+        const std::string res = prune(t, drop, pruned) ? write_newick(pruned, nullptr) : std::string();
+        char *p = (char *)malloc(res.size() + 1);
+        if (!p) throw std::runtime_error("qsh_prune_newick: out of memory");
+        memcpy(p, res.c_str(), res.size() + 1);
+        *out_text = p;
+        return 0;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return 1;
+    }
+}
 
 uint32_t qsh_batch_n_trees(const qsh_batch *b) { return b ? b->b.n_trees : 0; }
 // which: 0 leaf_off (u32), 1 leaf_ids (u16), 2 adj_depth (u16), 3 node_off (u32), 4 rng_off (u32), 5 ranges (u16)

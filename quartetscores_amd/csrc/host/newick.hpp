@@ -7,6 +7,8 @@
 #pragma once
 
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
 #include <functional>
 #include <istream>
 #include <stdexcept>
@@ -181,6 +183,76 @@ inline std::string write_newick(const Tree &t, const std::function<std::string(s
     }
     out.push_back(';');
     return out;
+}
+
+// The branch length of an edge that replaces two edges in a row: the one that is present, their sum when both are (the shortest of
+// %.15g / %.16g / %.17g that reads back as the same double), none when neither is.
+inline std::string add_lengths(const std::string &a, const std::string &b) {
+    if (a.empty() || b.empty()) return a.empty() ? b : a;
+    const double x = std::strtod(a.c_str(), nullptr) + std::strtod(b.c_str(), nullptr);
+    char text[40];
+    for (int digits = 15; digits <= 17; ++digits) {
+        std::snprintf(text, sizeof text, "%.*g", digits, x);
+        if (std::strtod(text, nullptr) == x) break;
+    }
+    return text;
+}
+
+// `t` without the leaves named in `drop` (names the tree lacks are ignored); false when no leaf is left (`out` is empty then).
+// QuartetScores --without-taxa applies this to the reference tree; quartetscores_amd/newick.py prune is the same rule:
+//   1. the named leaves go, and, repeatedly, inner nodes left without children;
+//   2. a non-root node left with one child is spliced out: the child takes its place in the parent's child order, with the sum of the
+//      two branch lengths (add_lengths); the spliced node's label goes;
+//   3. a root left with one child is replaced by that child, whose branch length goes;
+//   4. where the tree's root had three or more children before pruning and the root that is left -- the old one, or the node that
+//      replaced it in step 3 -- has two, it takes the children of its first child that is an inner node in that child's place (whose
+//      length goes to the other child, add_lengths): an unrooted tree stays unrooted, so that the scoring does not treat it as a
+//      rooted one. Where the tree's root had two children the root is left alone: the tree was rooted;
+//   5. child order never changes, so the kept leaves keep their relative depth-first order.
+template <typename NameSet> bool prune(const Tree &t, const NameSet &drop, Tree &out) {
+    out = Tree();
+    const int32_t N = (int32_t)t.node_count();
+    std::vector<int32_t> stands(N, -1);   // what stands in the parent's child list for the node (-1: nothing)
+    std::vector<std::vector<int32_t>> kids(N);
+    std::vector<std::string> length = t.length;
+    for (int32_t v = N - 1; v >= 0; --v) {   // preorder ids: children before parents
+        if (t.is_leaf(v)) { stands[v] = drop.count(t.name[v]) ? -1 : v; continue; }
+        for (int32_t c : t.children[v]) if (stands[c] >= 0) kids[v].push_back(stands[c]);
+        if (kids[v].empty()) continue;
+        if (kids[v].size() == 1 && v != 0) {
+            stands[v] = kids[v][0];
+            length[stands[v]] = add_lengths(length[v], length[stands[v]]);
+        } else stands[v] = v;
+    }
+    if (N == 0 || stands[0] < 0) return false;
+    int32_t root = 0;
+    while (kids[root].size() == 1) root = kids[root][0];
+    length[root].clear();
+    if (t.children[0].size() >= 3 && kids[root].size() == 2)
+        for (size_t i = 0; i < 2; ++i) {
+            const int32_t c = kids[root][i];
+            if (kids[c].empty()) continue;
+            const int32_t other = kids[root][1 - i];
+            length[other] = add_lengths(length[c], length[other]);
+            std::vector<int32_t> merged = kids[c];
+            merged.insert(i == 0 ? merged.end() : merged.begin(), other);
+            kids[root] = merged;
+            break;
+        }
+    // preorder copy
+    std::vector<std::pair<int32_t, int32_t>> st{{root, -1}};   // (node of t, parent in out)
+    while (!st.empty()) {
+        const auto [v, par] = st.back();
+        st.pop_back();
+        const int32_t id = (int32_t)out.parent.size();
+        out.parent.push_back(par);
+        out.children.emplace_back();
+        out.name.push_back(t.name[v]);
+        out.length.push_back(length[v]);
+        if (par >= 0) out.children[par].push_back(id);
+        for (auto it = kids[v].rbegin(); it != kids[v].rend(); ++it) st.push_back({*it, id});
+    }
+    return true;
 }
 
 } // namespace qsh

@@ -143,7 +143,7 @@ struct qs_ctx {
     uint32_t tune_score_dedupe = 1;              // QS_TUNE_SCORE_DEDUPE: the logging pass skips a quartet that repeats its node pair's last logged triple
     uint32_t tune_score_sample = 64u | 65536u;             // QS_TUNE_SCORE_SAMPLE: pre-pass of the single-read scoring (0 = none; S | by-round bit 16)
     uint64_t tune_score_log_cap = 0;             // QS_TUNE_SCORE_LOG_CAP: records the log may hold (0 = 8 M); tests force overflows
-    DevBuf<uint16_t> remap_ids;                  // qs_table_remap: src_id_of on the device (n entries)
+    DevBuf<uint16_t> remap_ids;                  // qs_table_remap / qs_table_restrict: src_id_of on the device (n entries)
     // qs_tree_agreement: the reference tree's inner nodes (>= 3 links) as id boundaries on the device, and the tree they came from
     std::vector<int32_t> agree_parent;
     std::vector<uint32_t> agree_leaf_node;
@@ -748,24 +748,29 @@ extern "C" int qs_sum_words(qs_ctx *c, void *dst_device, const void *const *src_
     return QS_OK;   // asynchronous on the context's stream
 }
 
-// The table of `src` in the lookup-id order of another reference tree over the same taxa (qs_remap.hip), so that one count
-// serves several reference trees. The reference recounts per run: this replaces nothing there.
-extern "C" int qs_table_remap(qs_ctx *dst, const qs_ctx *src, const uint16_t *src_id_of) {
+// qs_table_remap (subset = false: a permutation of the same taxa, qs_remap.hip) and qs_table_restrict (subset = true: an injective
+// map of dst's taxa into src's, qs_restrict.hip) differ in what they ask of the taxon counts and the id map and in the kernel they launch.
+static int table_reindex(qs_ctx *dst, const qs_ctx *src, const uint16_t *src_id_of, bool subset) {
+    const std::string fn = subset ? "qs_table_restrict: " : "qs_table_remap: ";
     if (dst) dst->log_valid = false;   // (the table changes: a logged pass 1 no longer describes it)
     if (!dst) return QS_ERR_ARG;
-    if (!src || !src_id_of) return fail(dst, QS_ERR_ARG, "qs_table_remap: NULL argument");
-    if (dst == src) return fail(dst, QS_ERR_ARG, "qs_table_remap: source and destination are the same context");
+    if (!src || !src_id_of) return fail(dst, QS_ERR_ARG, fn + "NULL argument");
+    if (dst == src) return fail(dst, QS_ERR_ARG, fn + "source and destination are the same context");
     if (dst->d_lo != 0 || dst->d_hi != dst->n || src->d_lo != 0 || src->d_hi != src->n)
-        return fail(dst, QS_ERR_UNSUPPORTED, "qs_table_remap: whole-table contexts only (no table shards)");
-    if (dst->n != src->n) return fail(dst, QS_ERR_ARG, "qs_table_remap: the contexts have different numbers of taxa");
-    if (dst->device != src->device) return fail(dst, QS_ERR_ARG, "qs_table_remap: the contexts are on different devices");
-    if (!dst->table || !src->table) return fail(dst, QS_ERR_STATE, std::string("qs_table_remap: the ") + (src->table ? "destination" : "source") + " has no table");
-    if (dst->table == src->table) return fail(dst, QS_ERR_ARG, "qs_table_remap: source and destination share their table");
-    if (dst->count_bits < src->count_bits) return fail(dst, QS_ERR_ARG, "qs_table_remap: 32-bit cells cannot be narrowed to 16 bits");
-    std::vector<uint8_t> seen(dst->n, 0);
+        return fail(dst, QS_ERR_UNSUPPORTED, fn + "whole-table contexts only (no table shards)");
+    if (subset ? dst->n > src->n : dst->n != src->n)
+        return fail(dst, QS_ERR_ARG, fn + (subset ? "the destination has more taxa than the source" : "the contexts have different numbers of taxa"));
+    if (dst->device != src->device) return fail(dst, QS_ERR_ARG, fn + "the contexts are on different devices");
+    if (!dst->table || !src->table) return fail(dst, QS_ERR_STATE, fn + "the " + (src->table ? "destination" : "source") + " has no table");
+    if (dst->table == src->table) return fail(dst, QS_ERR_ARG, fn + "source and destination share their table");
+    if (dst->count_bits < src->count_bits) return fail(dst, QS_ERR_ARG, fn + "32-bit cells cannot be narrowed to 16 bits");
+    std::vector<uint8_t> seen(src->n, 0);
+    bool monotone = true;   // strictly increasing: the source ids of a destination 4-set are sorted as they come
     for (uint32_t i = 0; i < dst->n; ++i) {
-        if (src_id_of[i] >= dst->n || seen[src_id_of[i]]) return fail(dst, QS_ERR_ARG, "qs_table_remap: src_id_of is not a permutation of [0, n_taxa)");
+        if (src_id_of[i] >= src->n || seen[src_id_of[i]])
+            return fail(dst, QS_ERR_ARG, fn + (subset ? "src_id_of is not injective into [0, n_taxa of the source)" : "src_id_of is not a permutation of [0, n_taxa)"));
         seen[src_id_of[i]] = 1;
+        if (i && src_id_of[i] < src_id_of[i - 1]) monotone = false;
     }
     QS_HIP(dst, hipSetDevice(dst->device));
     QS_HIP(dst, dst->remap_ids.reserve(4096 * sizeof(uint16_t), nullptr));
@@ -778,10 +783,23 @@ extern "C" int qs_table_remap(qs_ctx *dst, const qs_ctx *src, const uint16_t *sr
         QS_HIP(dst, e);
     }
     QS_HIP(dst, hipMemcpyAsync(dst->remap_ids.get(), src_id_of, dst->n * sizeof(uint16_t), hipMemcpyHostToDevice, dst->stream));
-    QS_HIP(dst, launch_table_remap(dst->stream, src->table, (int)src->count_bits, dst->table, (int)dst->count_bits, dst->remap_ids.get(), dst->n, dst->n_tuples));
+    if (subset)
+        QS_HIP(dst, launch_table_restrict(dst->stream, src->table, (int)src->count_bits, dst->table, (int)dst->count_bits, dst->remap_ids.get(), dst->n, dst->n_tuples, monotone));
+    else
+        QS_HIP(dst, launch_table_remap(dst->stream, src->table, (int)src->count_bits, dst->table, (int)dst->count_bits, dst->remap_ids.get(), dst->n, dst->n_tuples));
     dst->trees_counted = src->trees_counted;   // sizes the log table and the 16-bit overflow guard of later counts
     return QS_OK;   // asynchronous on dst's stream
 }
+
+// The table of `src` in the lookup-id order of another reference tree over the same taxa (qs_remap.hip), so that one count
+// serves several reference trees. The reference recounts per run: this replaces nothing there.
+extern "C" int qs_table_remap(qs_ctx *dst, const qs_ctx *src, const uint16_t *src_id_of) { return table_reindex(dst, src, src_id_of, false); }
+
+// The table of `src` over a subset of its taxa, in any id order (qs_restrict.hip): the table of the problem without the other taxa,
+// because what a tree displays for a 4-set does not depend on its other taxa (a tree pruned below four taxa still counts towards
+// trees-counted; scores never depend on it). The reference rejects a leaf it does not know and recounts per run: this replaces
+// nothing there.
+extern "C" int qs_table_restrict(qs_ctx *dst, const qs_ctx *src, const uint16_t *src_id_of) { return table_reindex(dst, src, src_id_of, true); }
 
 // Per-tree quartet agreement of a batch with the reference tree (qs_agree.hip). The reference's links come from its depth-first id
 // order: the children of an inner node split its id interval, ordered by their first id, and its parent link holds the other ids.

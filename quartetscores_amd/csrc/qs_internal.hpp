@@ -138,6 +138,10 @@ hipError_t launch_lookup(hipStream_t s, uint32_t n, uint32_t d_lo, uint32_t d_hi
 // qs_remap.hip: dst (ids B) <- src (ids A); src_id_of_dev[i] = A-id of B-id i (a permutation of [0, n)); cell widths 32/32, 16/16 or 16 -> 32
 hipError_t launch_table_remap(hipStream_t s, const void *src, int src_bits, void *dst, int dst_bits, const uint16_t *src_id_of_dev,
                               uint32_t n, uint64_t n_tuples);
+// qs_restrict.hip: dst (n_dst taxa) <- the sub-table of src over the taxa src_id_of_dev[0 .. n_dst) (injective into src's ids); monotone:
+// the map is strictly increasing (no sort, slots are the identity); cell widths as above
+hipError_t launch_table_restrict(hipStream_t s, const void *src, int src_bits, void *dst, int dst_bits, const uint16_t *src_id_of_dev,
+                                 uint32_t n_dst, uint64_t n_tuples, bool monotone);
 // qs_agree.hip: per-tree quartet agreement with the reference (qs_tree_agreement); the reference's inner nodes with >= 3
 // links as id boundaries (ref_off / ref_bnd, ref_par = has a parent link); dst = 4 words per tree of the batch
 hipError_t launch_tree_agree(hipStream_t s, const DeviceBatch &b, uint32_t n, uint32_t max_tree_nodes, const uint32_t *ref_off,

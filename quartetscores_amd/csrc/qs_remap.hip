@@ -10,40 +10,12 @@
 // decode_near. For destination ids t0 < t1 < t2 < t3 with source ids u_i = src_id_of[t_i]: the source tuple sits at
 // rank4(sorted u), and destination slot k (t0 paired with t_{k+1}) is the source slot of the pairing
 // {u0, u_{k+1}} | {the other two} (slot_of_pairing). src_id_of lives in LDS. The source tuple is read with ONE load
-// (dwordx3 for 32-bit cells, the two dwords around the 6 bytes for 16-bit cells): a read that leaves the source row is
-// one scattered cache line per lane.
+// (qs_tuple_io.hpp).
 #include "qs_common.hpp"
 #include "qs_internal.hpp"
+#include "qs_tuple_io.hpp"
 
 namespace qs {
-
-constexpr int kRemapThreads = 256;
-constexpr uint32_t kRemapSteps = 32;   // destination ranks per lane (64 apart)
-
-struct alignas(4) Cells3 { uint32_t x, y, z; };
-struct alignas(4) Words2 { uint32_t x, y; };
-
-__device__ __forceinline__ void load_tuple(const uint32_t *__restrict__ t, uint64_t r, uint32_t v[3]) {
-    const Cells3 q = *reinterpret_cast<const Cells3 *>(t + 3 * r);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z;
-}
-// 6 bytes at 2-byte alignment: the two dwords that hold them. They end at most 2 bytes behind the tuple, which the
-// table's allocation (16 bytes of padding) and an attached table (bytes rounded up to a multiple of 4) both cover.
-__device__ __forceinline__ void load_tuple(const uint16_t *__restrict__ t, uint64_t r, uint32_t v[3]) {
-    const uint64_t byte = 6 * r;
-    const Words2 q = *reinterpret_cast<const Words2 *>(reinterpret_cast<const char *>(t) + (byte & ~3ull));
-    const uint64_t w = ((uint64_t)q.y << 32 | q.x) >> ((byte & 2) * 8);
-    v[0] = (uint32_t)w & 0xFFFFu; v[1] = (uint32_t)(w >> 16) & 0xFFFFu; v[2] = (uint32_t)(w >> 32) & 0xFFFFu;
-}
-
-__device__ __forceinline__ void store_tuple(uint32_t *__restrict__ t, uint64_t r, uint32_t a, uint32_t b, uint32_t c) {
-    *reinterpret_cast<Cells3 *>(t + 3 * r) = Cells3{a, b, c};
-}
-__device__ __forceinline__ void store_tuple(uint16_t *__restrict__ t, uint64_t r, uint32_t a, uint32_t b, uint32_t c) {
-    t[3 * r] = (uint16_t)a; t[3 * r + 1] = (uint16_t)b; t[3 * r + 2] = (uint16_t)c;
-}
-
-__device__ __forceinline__ uint32_t pick3(const uint32_t v[3], int k) { return k == 0 ? v[0] : k == 1 ? v[1] : v[2]; }
 
 template <typename ST, typename DT>
 __global__ __launch_bounds__(kRemapThreads) void table_remap_kernel(const ST *__restrict__ src, DT *__restrict__ dst,
@@ -77,10 +49,8 @@ hipError_t launch_table_remap(hipStream_t s, const void *src, int src_bits, void
                               uint32_t n, uint64_t n_tuples) {
     if (n_tuples == 0) return hipSuccess;
     if (n > 4096) return hipErrorInvalidValue;
-    const uint64_t per_block = (uint64_t)kRemapThreads * kRemapSteps;
-    const uint64_t blocks = (n_tuples + per_block - 1) / per_block;
-    if (blocks >= (1ull << 31)) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)blocks), block(kRemapThreads);
+    dim3 grid, block;
+    if (!reindex_grid(n_tuples, grid, block)) return hipErrorInvalidValue;
     if (src_bits == 32 && dst_bits == 32)
         hipLaunchKernelGGL((table_remap_kernel<uint32_t, uint32_t>), grid, block, 0, s, (const uint32_t *)src, (uint32_t *)dst, src_id_of_dev, n, n_tuples);
     else if (src_bits == 16 && dst_bits == 16)

@@ -191,6 +191,15 @@ class Context:
             raise ValueError(f"table_remap: src_id_of needs {self.n} entries, got {perm.shape}")
         self._chk(self.L.qs_table_remap(self.h, src.h, perm.ctypes.data_as(C.c_void_p)))
 
+    def table_restrict(self, src: "Context", src_id_of):
+        """qs_table_restrict: this context's table := `src`'s table over a subset of its taxa. src_id_of[i] = id in src's order
+        of the taxon whose id here is i (flatten.taxon_restriction(ref_here, ref_src)); any injective map, strictly increasing
+        for a pruned reference tree. Asynchronous on this context's stream."""
+        ids = np.ascontiguousarray(src_id_of, dtype=np.uint16)
+        if ids.shape != (self.n,):
+            raise ValueError(f"table_restrict: src_id_of needs {self.n} entries, got {ids.shape}")
+        self._chk(self.L.qs_table_restrict(self.h, src.h, ids.ctypes.data_as(C.c_void_p)))
+
     def tree_agreement(self, ref: flatten.RefTree, hb) -> np.ndarray:
         """qs_tree_agreement: per tree of the uploaded batch `hb` (uploaded with its node ranges) its quartet agreement with `ref`
         -> uint64 (n_trees, 4) in AGREEMENT_FIELDS order (agreement_columns derives the rest). Allocates the device buffer,

@@ -70,6 +70,18 @@ def taxon_permutation(ref_dst: RefTree, ref_src: RefTree) -> np.ndarray:
     return np.array([ref_src.name_to_id[nm] for nm in ref_dst.names], dtype=np.uint16)
 
 
+def taxon_restriction(ref_dst: RefTree, ref_src: RefTree) -> np.ndarray:
+    """uint16[n_dst]: entry i = lookup id under ref_src of the taxon whose lookup id under ref_dst is i -- the src_id_of of
+    qs_table_restrict. Like taxon_permutation, but ref_dst's taxa may be a subset of ref_src's; strictly increasing when
+    ref_dst is ref_src pruned (newick.prune keeps the leaf order). Raises ValueError naming the taxa of ref_dst that
+    ref_src lacks."""
+    extra = sorted(set(ref_dst.names) - set(ref_src.names))
+    if extra:
+        raise ValueError("the reference trees hold different taxa: missing none; extra " + ", ".join(extra) +
+                         " (taxa of ref_dst that ref_src lacks; ref_dst may hold fewer taxa, not others)")
+    return np.array([ref_src.name_to_id[nm] for nm in ref_dst.names], dtype=np.uint16)
+
+
 @dataclass
 class TreeBatch:
     n_trees: int

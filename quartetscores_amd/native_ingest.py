@@ -41,6 +41,8 @@ def _lib():
         L.qsh_synth_trees.argtypes = [C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_char_p, C.c_double, C.c_uint,
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.qsh_free_text.argtypes = [C.c_void_p]
+        L.qsh_prune_newick.restype = C.c_int
+        L.qsh_prune_newick.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_void_p)]
         L.qsh_batch_n_trees.restype = C.c_uint32
         L.qsh_batch_n_trees.argtypes = [C.c_void_p]
         L.qsh_batch_array.restype = C.c_void_p
@@ -96,6 +98,22 @@ def synth_trees(n: int, m: int, seed: int, kind: str = "random", ref_text: str =
         raise IngestError(L.qsh_last_error().decode())
     try:
         return C.string_at(p, ln.value)
+    finally:
+        L.qsh_free_text(p)
+
+
+def prune_newick(text: str, drop_names) -> str:
+    """The C++ host's pruner (csrc/host/newick.hpp prune, what QuartetScores --without-taxa applies to the reference tree) on
+    the first tree of `text`: Newick text without the named leaves, "" when no leaf is left. newick.prune is the same rule."""
+    L = _lib()
+    names = [nm.encode() for nm in drop_names]
+    arr = (C.c_char_p * max(1, len(names)))(*names)
+    p = C.c_void_p()
+    tb = text.encode()
+    if L.qsh_prune_newick(tb, len(tb), arr, len(names), C.byref(p)) != 0:
+        raise IngestError(L.qsh_last_error().decode())
+    try:
+        return C.string_at(p).decode()
     finally:
         L.qsh_free_text(p)
 

@@ -192,3 +192,66 @@ def write(root: Node, comment=None) -> str:
             if cm:
                 parts.append("[" + cm + "]")
     return "".join(parts) + ";"
+
+
+def add_lengths(a: Optional[str], b: Optional[str]) -> Optional[str]:
+    """The branch length of an edge that replaces two edges in a row: the one that is present, their sum when both are
+    (the shortest of %.15g / %.16g / %.17g that reads back as the same double; csrc/host/newick.hpp add_lengths writes
+    the same text), None when neither is."""
+    if not a or not b:
+        return a or b or None
+    x = float(a) + float(b)
+    for digits in (15, 16, 17):
+        text = "%.*g" % (digits, x)
+        if float(text) == x:
+            break
+    return text
+
+
+def prune(root: Node, drop_names) -> Optional[Node]:
+    """A copy of the tree without the leaves named in drop_names (names the tree lacks are ignored); None when no leaf is left.
+    The rule of csrc/host/newick.hpp prune, which QuartetScores --without-taxa applies to the reference tree:
+      1. the named leaves go, and, repeatedly, inner nodes left without children;
+      2. a non-root node left with one child is spliced out: the child takes its place in the parent's child order, with
+         the sum of the two branch lengths (add_lengths); the spliced node's label goes;
+      3. a root left with one child is replaced by that child, whose branch length goes;
+      4. where the tree's root had three or more children before pruning and the root that is left -- the old one, or the node
+         that replaced it in step 3 -- has two, it takes the children of its first child that is an inner node in that
+         child's place (whose length goes to the other child, add_lengths): an unrooted tree stays unrooted. Where the
+         tree's root had two children the root is left alone: the tree was rooted;
+      5. child order never changes, so the kept leaves keep their relative depth-first order."""
+    drop = set(drop_names)
+    nodes = preorder(root)
+    copy = {}      # id(node) -> what stands in its parent's child list for it (None: nothing)
+    for x in reversed(nodes):                      # children before parents
+        if x.is_leaf:
+            copy[id(x)] = None if x.name in drop else Node(x.name, x.length)
+            continue
+        kids = [k for k in (copy[id(c)] for c in x.children) if k is not None]
+        if not kids:
+            copy[id(x)] = None
+        elif len(kids) == 1 and x is not root:
+            kids[0].length = add_lengths(x.length, kids[0].length)
+            copy[id(x)] = kids[0]
+        else:
+            y = Node(x.name, x.length, kids)
+            for k in kids:
+                k.parent = y
+            copy[id(x)] = y
+    new = copy[id(root)]
+    if new is None:
+        return None
+    while len(new.children) == 1:
+        new = new.children[0]
+    new.parent = None
+    new.length = None
+    if len(root.children) >= 3 and len(new.children) == 2:
+        for i, c in enumerate(new.children):
+            if c.children:
+                other = new.children[1 - i]
+                other.length = add_lengths(c.length, other.length)
+                new.children[i:i + 1] = c.children
+                for k in c.children:
+                    k.parent = new
+                break
+    return new
