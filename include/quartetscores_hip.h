@@ -20,6 +20,8 @@
  *   qs_tree_agreement             replaces nothing in the reference (it reports no per-tree agreement)
  *   qs_taxon_support              replaces nothing in the reference (the nearest is printRawQICScores, :612-680: one text
  *                                 line per quartet, which a user would reduce per taxon on the host)
+ *   qs_taxon_placement /          replace nothing in the reference (it never asks where the evaluation trees would put a taxon; the
+ *   qs_placement_scores           nearest route is one more reference tree and one more run per candidate position)
  *   qs_score                      QuartetScoreComputer: processNodePair /
  *                                 computeQuartetScoresBifurcating / ...Multifurcating
  *                                 (QuartetScoreComputer.hpp:379-593) + getLQIC/QPIC/EQPICScores (:106-125)
@@ -365,6 +367,30 @@ int qs_tree_agreement(qs_ctx *ctx, const qs_ref_tree *ref, const qs_device_batch
  * QS_TUNE_TABLE_TREES -- if known, else the largest count a cell holds) exceeds 63 bits; QS_ERR_UNSUPPORTED = more than 3413 taxa
  * (table-shard contexts only; a whole table ends at 2259). Asynchronous on the context's stream. */
 int qs_taxon_support(qs_ctx *ctx, const qs_ref_tree *ref, int64_t *dst_device);
+
+/* Quartet placement of taxa on the reference tree from the count table: where would the evaluation trees put taxon x? With x attached
+ * on an edge e of the reference tree T without x, the placement score of e is the sum, over the 4-sets {x,p,q,r}, of the count of the
+ * topology that tree displays -- what a quartet-based placement maximises, and at x's own pendant edge the `concordant` word of
+ * qs_taxon_support. All edges come out of 2 * n_nodes LINK SUMS W_x: link v (v not the root) is the edge from parent[v] into v, link
+ * n_nodes + m the edge from m to its parent. For three other taxa p < q < r with median node m in T, n(xp|qr), n(xq|pr) and n(xr|pq)
+ * of the 4-set's tuple are added to the links of m that lead towards p, q and r; qs_placement_scores turns a row of
+ * link sums into scores. The sum of W_x over all links is concordant + discordant + eval_only of qs_taxon_support.
+ * taxa = host array of n_list distinct lookup ids (lent for the call), or NULL = all taxa in id order (n_list must be n_taxa then).
+ * dst_device (caller-owned device memory, 8-byte aligned, n_list x 2 * n_nodes words) is OVERWRITTEN, one row per list entry in list
+ * order. Exact integers, independent of grid and order. One gather over the C(n_taxa-1,3) tuples that hold each listed taxon; changes
+ * neither the table nor trees-counted nor a pending score log; a scoring view is not looked at. The reference tree is checked and
+ * uploaded as by qs_score, its link lookups beside it (cached per context, dropped with it).
+ * Errors: QS_ERR_STATE = no table; QS_ERR_ARG = NULL / misaligned dst, an id >= n_taxa or listed twice, n_list = 0 or > n_taxa, malformed
+ * reference, n_taxa differs from the context's, ids not in depth-first order; QS_ERR_OVERFLOW = the bound of qs_taxon_support;
+ * QS_ERR_UNSUPPORTED = a table-shard context (whole tables only), or more than 10240 nodes. Asynchronous on the context's stream.
+ * The reference has no such output: this replaces nothing there. */
+int qs_taxon_placement(qs_ctx *ctx, const qs_ref_tree *ref, const uint16_t *taxa, uint32_t n_list, int64_t *dst_device);
+/* Host-only (no device, no context; the message of a failure comes from qs_last_error(NULL)): one row W_x of qs_taxon_placement ->
+ * scores_host[v], v < n_nodes = the placement score of the edge above node v (the root's entry is 0), by the preorder recurrence
+ * S(v) = S(parent v) - W[n_nodes + parent v] + W[v], started with the sum of W over all parent links at the root. Edges that induce
+ * the same bipartition of the other taxa get equal scores (x's pendant edge and the two other edges at a degree-3 parent; the two
+ * edges at a degree-2 root). QS_ERR_ARG = NULL argument or malformed tree. Replaces nothing in the reference. */
+int qs_placement_scores(const qs_ref_tree *ref, const int64_t *links_host, int64_t *scores_host);
 
 /* ---- scoring (QuartetScoreComputer) ----------------------------------------------------- */
 

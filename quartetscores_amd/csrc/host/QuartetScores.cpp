@@ -14,6 +14,8 @@
 // re-indexed into REF's lookup-id order (qs_table_remap) instead of being counted again.
 // --without-taxa NAMES OUT (repeatable) scores the -r tree without the taxa listed in NAMES from the same count table: the tree is
 // pruned (newick.hpp prune) and the table cut down to the kept taxa (qs_table_restrict) instead of pruning every tree and recounting.
+// --place-taxa FILE [--place-only NAMES] writes where the evaluation trees would put every (listed) taxon of the -r tree: the quartet
+// score of each edge as a position of the taxon, from the same count table (qs_taxon_placement, qs_placement_scores).
 #include "QuartetScoreComputer.hpp"
 #include "multi_gpu.hpp"
 #include "table_shards.hpp"
@@ -66,6 +68,9 @@ struct Args {
     std::string ref, eval, out, raw, raw_bin;
     std::string per_tree;   // --per-tree FILE: quartet agreement of every evaluation tree with -r (TSV)
     std::string per_taxon;  // --per-taxon FILE: quartet support per taxon of -r from the count table (TSV)
+    std::string place_taxa; // --place-taxa FILE: quartet placement of the taxa of -r from the count table (TSV)
+    std::string place_only; // --place-only NAMES: a file of the taxon labels to place (default: all)
+    std::vector<uint16_t> place_ids;   // the lookup ids to place, ascending (check_place_taxa)
     std::vector<AlsoRef> also;
     std::vector<WithoutTaxa> without;
     size_t threads = 0;
@@ -132,7 +137,17 @@ void usage(std::ostream &os) {
           "                  taxon in lookup-id order after a header: taxon name quartets ref_resolved concordant discordant eval_only\n"
           "                  outvoted uninformed concordance concordance_without); one more read of the table on the device; a taxon\n"
           "                  whose concordance_without lies clearly above the others' is a rogue taxon; one GPU with the whole table\n"
-          "                  (not with --gpus / --table-shards); works with --load-table, --also-ref (still the -r tree) and --per-tree\n";
+          "                  (not with --gpus / --table-shards); works with --load-table, --also-ref (still the -r tree) and --per-tree\n"
+          "   --place-taxa F write, per taxon of the -r tree, where the evaluation trees would put it to F (TSV, one line per taxon in\n"
+          "                  lookup-id order after a header: taxon name current best gain n_best best_node best_lo best_hi distance).\n"
+          "                  The score of a position = the sum, over the quartets that hold the taxon, of the count of the topology the\n"
+          "                  -r tree shows with the taxon attached there; current = at its own edge, best = the largest over all edges,\n"
+          "                  n_best = positions that attain it (one clearly better position: a misplaced taxon; none: an unstable one),\n"
+          "                  best_node / [best_lo, best_hi) = node index and lookup ids below the edge of the reported position,\n"
+          "                  distance = nodes between the two positions (0 = where it is, 1 = an NNI away). One gather over the table per\n"
+          "                  taxon; one GPU with the whole table (not with --gpus / --table-shards); works with --load-table, --per-taxon,\n"
+          "                  --per-tree, --also-ref and --without-taxa (always the full -r tree)\n"
+          "   --place-only NAMES  with --place-taxa: place only the taxa listed in NAMES (one label per line, as for --without-taxa)\n";
 }
 
 // returns 0 ok, 1 error (message printed like the reference prints TCLAP::ArgException), 2 exit quietly
@@ -205,6 +220,8 @@ int parse(int argc, char **argv, Args &a) {
         else if (f == "--qic-binary") { if (!(v = need(i, "--qic-binary"))) return 1; a.raw_bin = v; }
         else if (f == "--per-tree") { if (!(v = need(i, "--per-tree"))) return 1; a.per_tree = v; }
         else if (f == "--per-taxon") { if (!(v = need(i, "--per-taxon"))) return 1; a.per_taxon = v; }
+        else if (f == "--place-taxa") { if (!(v = need(i, "--place-taxa"))) return 1; a.place_taxa = v; }
+        else if (f == "--place-only") { if (!(v = need(i, "--place-only"))) return 1; a.place_only = v; }
         else if (f == "--load-table") { if (!(v = need(i, "--load-table"))) return 1; a.dev.load_table = v; }
         else if (f == "--also-ref") {
             if (i + 2 >= argc || argv[i + 2][0] == '-') {
@@ -292,6 +309,22 @@ void check_also_refs(Args &a) {
     }
 }
 
+// A NAMES file (--without-taxa, --place-only): one label per line, as parsed and unquoted; surrounding blanks go, blank lines are skipped,
+// a repeated label counts once. Returns the labels; `what` prefixes the message for a label the -r tree lacks.
+std::set<std::string> read_taxon_names(const std::string &path, const RefFlat &rf, const std::string &ref_path, const std::string &what) {
+    std::set<std::string> names;
+    std::istringstream lines(slurp(path));
+    for (std::string line; std::getline(lines, line);) {
+        const size_t b = line.find_first_not_of(" \t\r"), e = line.find_last_not_of(" \t\r");
+        if (b == std::string::npos) continue;
+        const std::string name = line.substr(b, e - b + 1);
+        if (!rf.name_to_id.count(name)) throw std::runtime_error(what + "the taxon " + name + " is not in the reference tree " + ref_path);
+        names.insert(name);
+    }
+    if (names.empty()) throw std::runtime_error(what + "the list of taxa is empty");
+    return names;
+}
+
 // --without-taxa: everything that needs no GPU, before the device is touched -- every name is a taxon of -r, at least one is dropped
 // and four are kept, no OUT exists or repeats another output, and qs_score_check passes for every pruned tree with the run's flags
 void check_without_taxa(Args &a) {
@@ -311,15 +344,7 @@ void check_without_taxa(Args &a) {
         const std::string what = "--without-taxa " + x.names + ": ";
         if (!outs.insert(x.out).second) throw std::runtime_error(what + "the output file " + x.out + " is given twice");
         if (std::ifstream(x.out).good()) throw std::runtime_error(what + "the output file " + x.out + " already exists");
-        std::istringstream lines(slurp(x.names));
-        for (std::string line; std::getline(lines, line);) {
-            const size_t b = line.find_first_not_of(" \t\r"), e = line.find_last_not_of(" \t\r");
-            if (b == std::string::npos) continue;
-            const std::string name = line.substr(b, e - b + 1);
-            if (!rf.name_to_id.count(name)) throw std::runtime_error(what + "the taxon " + name + " is not in the reference tree " + a.ref);
-            x.drop.insert(name);
-        }
-        if (x.drop.empty()) throw std::runtime_error(what + "the list of taxa is empty");
+        x.drop = read_taxon_names(x.names, rf, a.ref, what);
         if (rf.names.size() < x.drop.size() + 4)
             throw std::runtime_error(what + "fewer than four taxa are left (" + std::to_string(rf.names.size() - x.drop.size()) + " of " + std::to_string(rf.names.size()) + ")");
         prune(primary, x.drop, x.tree);
@@ -423,6 +448,107 @@ void write_per_taxon(qs_ctx *ctx, const RefFlat &ref, int device, const std::str
         f << x << '\t' << ref.names[x] << '\t' << quartets;
         for (int k = 0; k < 6; ++k) f << '\t' << v[k];
         f << '\t' << own << '\t' << without << '\n';
+    }
+    if (!f) throw std::runtime_error("cannot write " + path);
+}
+
+// --place-taxa: refused before the device is touched where the whole table is not on one GPU, where FILE exists or is another output,
+// and where --place-only names a label the -r tree lacks; leaves the lookup ids to place in a.place_ids
+void check_place_taxa(Args &a) {
+    if (a.place_taxa.empty()) {
+        if (!a.place_only.empty()) throw std::runtime_error("--place-only needs --place-taxa FILE");
+        return;
+    }
+    if (a.gpus > 0 || a.table_shards >= 0)
+        throw std::runtime_error("--place-taxa needs the whole count table on one GPU: omit --gpus / --table-shards");
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon};
+    for (const AlsoRef &x : a.also) others.insert(x.out);
+    for (const WithoutTaxa &x : a.without) others.insert(x.out);
+    if (others.count(a.place_taxa)) throw std::runtime_error("--place-taxa: " + a.place_taxa + " is also another output file");
+    if (std::ifstream(a.place_taxa).good()) throw std::runtime_error("--place-taxa: the output file " + a.place_taxa + " already exists");
+    Tree primary;
+    {
+        const std::string text = slurp(a.ref);
+        NewickReader rr(text);
+        if (!rr.next(primary)) throw std::runtime_error("empty reference tree file");
+    }
+    const RefFlat rf = flatten_reference(primary);
+    std::set<uint16_t> ids;
+    if (a.place_only.empty()) {
+        for (size_t i = 0; i < rf.names.size(); ++i) ids.insert((uint16_t)i);
+    } else {
+        for (const std::string &name : read_taxon_names(a.place_only, rf, a.ref, "--place-only " + a.place_only + ": "))
+            ids.insert((uint16_t)rf.name_to_id.at(name));
+    }
+    a.place_ids.assign(ids.begin(), ids.end());
+}
+
+// --place-taxa: one qs_taxon_placement over the counted (or loaded) table for the listed taxa, their link sums downloaded, per taxon
+// qs_placement_scores and the columns (tests/placement_model.py defines them): a position = the edges that induce the same
+// bipartition of the other taxa
+void write_place_taxa(qs_ctx *ctx, const RefFlat &ref, int device, const std::string &path, const std::vector<uint16_t> &ids) {
+    const size_t n = ref.names.size(), N = ref.parent.size(), L = ids.size();
+    const qs_ref_tree rt = ref_view(ref);
+    qs::DevBuf<int64_t> dev;
+    if (hipSetDevice(device) != hipSuccess || dev.reserve(L * 2 * N * 8, nullptr) != hipSuccess) throw std::runtime_error("--place-taxa: Insufficient memory!");
+    if (qs_taxon_placement(ctx, &rt, ids.data(), (uint32_t)L, dev.get()) != QS_OK || qs_sync(ctx) != QS_OK)
+        throw std::runtime_error(std::string("--place-taxa: ") + qs_last_error(ctx));
+    std::vector<int64_t> w(L * 2 * N);
+    if (hipMemcpy(w.data(), dev.get(), w.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("--place-taxa: download failed");
+    // the tree's shape: nodes are numbered in preorder (parents first)
+    size_t root = 0;
+    std::vector<uint32_t> depth(N, 0), links(N, 0);
+    std::vector<int64_t> lo(N, (int64_t)n), hi(N, 0);
+    for (size_t v = 0; v < N; ++v) {
+        const int32_t p = ref.parent[v];
+        if (p < 0) { root = v; continue; }
+        if ((size_t)p >= v) throw std::runtime_error("--place-taxa: the reference tree is not numbered in preorder");
+        depth[v] = depth[p] + 1; links[v] += 1; links[p] += 1;
+    }
+    for (size_t i = 0; i < n; ++i) { lo[ref.leaf_node[i]] = (int64_t)i; hi[ref.leaf_node[i]] = (int64_t)i + 1; }
+    for (size_t v = N; v-- > 0;)
+        if (ref.parent[v] >= 0) { const size_t p = (size_t)ref.parent[v]; lo[p] = std::min(lo[p], lo[v]); hi[p] = std::max(hi[p], hi[v]); }
+    auto walk = [&](size_t a, size_t b) {   // nodes on the path from a to b, both inclusive
+        std::vector<size_t> left{a}, right{b};
+        while (left.back() != right.back()) {
+            if (depth[left.back()] >= depth[right.back()]) left.push_back((size_t)ref.parent[left.back()]);
+            else right.push_back((size_t)ref.parent[right.back()]);
+        }
+        left.insert(left.end(), right.rbegin() + 1, right.rend());
+        return left;
+    };
+    std::ofstream f(path);
+    if (!f) throw std::runtime_error("cannot write " + path);
+    f << "taxon\tname\tcurrent\tbest\tgain\tn_best\tbest_node\tbest_lo\tbest_hi\tdistance\n";
+    std::vector<int64_t> score(N), key(N);
+    for (size_t k = 0; k < L; ++k) {
+        const int64_t x = ids[k];
+        if (qs_placement_scores(&rt, &w[k * 2 * N], score.data()) != QS_OK) throw std::runtime_error(std::string("--place-taxa: ") + qs_last_error(nullptr));
+        // the position of the edge above v: the id interval, in the others' numbering, of the side without the smallest other taxon
+        for (size_t v = 0; v < N; ++v) {
+            int64_t a = lo[v] - (lo[v] > x), b = hi[v] - (hi[v] > x);
+            if (a == 0 && b > 0) { a = b; b = (int64_t)n - 1; }
+            key[v] = b > a ? a * (int64_t)n + b : 0;
+        }
+        const size_t own = ref.leaf_node[x], u = (size_t)ref.parent[own];
+        if (links[u] == 3)   // the taxon's pendant edge and the two other edges at its parent are one position
+            for (size_t v = 0; v < N; ++v) if (v != own && ref.parent[v] == (int32_t)u) { key[own] = key[v]; break; }
+        int64_t best = INT64_MIN;
+        for (size_t v = 0; v < N; ++v) if (v != root) best = std::max(best, score[v]);
+        std::set<int64_t> top;
+        int64_t first_top = -1;
+        for (size_t v = 0; v < N; ++v) if (v != root && score[v] == best) { if (top.empty()) first_top = key[v]; top.insert(key[v]); }
+        const int64_t current = score[own];
+        const int64_t pick = current == best ? key[own] : first_top;
+        size_t node = 0;
+        for (size_t v = 0; v < N; ++v) if (v != root && key[v] == pick) { node = v; break; }
+        size_t dist = 0;
+        if (pick != key[own]) {
+            const std::vector<size_t> to_child = walk(u, node), to_parent = walk(u, (size_t)ref.parent[node]);
+            for (size_t v : to_parent.size() < to_child.size() ? to_parent : to_child) dist += links[v] - (v == u) >= 3;
+        }
+        f << x << '\t' << ref.names[x] << '\t' << current << '\t' << best << '\t' << (best - current) << '\t' << top.size() << '\t' << node << '\t'
+          << lo[node] << '\t' << hi[node] << '\t' << dist << '\n';
     }
     if (!f) throw std::runtime_error("cannot write " + path);
 }
@@ -583,6 +709,7 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
     if (!a.raw_bin.empty()) qsc.printRawQICBinary(a.raw_bin);
     if (!a.per_tree.empty()) per_tree.write(a.per_tree);
     if (!a.per_taxon.empty()) write_per_taxon(qsc.context(), qsc.reference(), a.dev.device, a.per_taxon);
+    if (!a.place_taxa.empty()) write_place_taxa(qsc.context(), qsc.reference(), a.dev.device, a.place_taxa, a.place_ids);
     if (!a.also.empty() || !a.without.empty()) {   // the primary tree's output first, exactly as without --also-ref / --without-taxa
         write_annotated(referenceTree, a.out, lqic, qpic, eqpic);
         score_also_refs(a, qsc.context(), qsc.reference(), also_table);
@@ -611,6 +738,7 @@ int main(int argc, char *argv[]) {
         check_without_taxa(a);
         check_per_tree(a);
         check_per_taxon(a);
+        check_place_taxa(a);
     } catch (const std::exception &e) {
         std::cerr << "ERROR: " << e.what() << std::endl;
         return 1;

@@ -151,6 +151,12 @@ struct qs_ctx {
     DevBuf<uint16_t> agree_bnd;
     DevBuf<uint8_t> agree_par;
     uint32_t agree_n_u = 0;
+    // qs_taxon_placement: the cached reference tree's link lookups (dropped with ref_lca_dev), the walks of an n-taxon table and
+    // the list of the last call; the host copies stay until the uploads on `stream` have read them
+    std::vector<uint16_t> place_child, place_next, place_taxa;
+    std::vector<uint32_t> place_tasks;
+    DevBuf<uint16_t> place_child_dev, place_next_dev, place_taxa_dev;
+    DevBuf<uint32_t> place_node_dev, place_tasks_dev;
 };
 
 static thread_local std::string g_create_err;   // per thread: qs_create of several contexts may run concurrently (multi_gpu.hpp)
@@ -1992,6 +1998,7 @@ static int get_ref(qs_ctx *c, const qs_ref_tree *ref, bool want_dev, const RefHo
         if (rc != QS_OK) return rc;
         fresh->leaf_node_in.assign(ref->leaf_node, ref->leaf_node + ref->n_taxa);
         if (c->ref_lca_dev) { (void)hipStreamSynchronize(c->stream); c->ref_lca_dev.reset(); c->ref_next_dev.reset(); c->root_pairs_dev.reset(); }
+        if (c->place_child_dev) { (void)hipStreamSynchronize(c->stream); c->place_child_dev.reset(); c->place_next_dev.reset(); c->place_node_dev.reset(); }
         c->ref_cache = std::move(fresh);
         R = c->ref_cache.get();
         c->log_valid = false;
@@ -2111,6 +2118,121 @@ extern "C" int qs_taxon_support(qs_ctx *c, const qs_ref_tree *ref, int64_t *dst_
     const bool wide = max_count >= (1ull << 32) / 192;   // 64 lanes x 3 counts in a 32-bit partial sum
     QS_HIP(c, launch_taxon_support(c->stream, sd, wide, c->n_cu, reinterpret_cast<unsigned long long *>(dst_device)));
     return QS_OK;   // asynchronous on the context's stream
+}
+
+// qs_taxon_placement: the link lookups of the cached reference tree on the device, beside its LCA matrix
+static int ensure_place_ref(qs_ctx *c, const RefHost &R) {
+    if (c->place_child_dev) return QS_OK;
+    const uint32_t n = R.n;
+    uint32_t max_depth = 0;
+    for (uint32_t d : R.depth) max_depth = std::max(max_depth, d);
+    // child[i][j] = the child of lca(i,j) that holds leaf j: j's ancestor one level below the LCA
+    c->place_child.assign((size_t)n * n, 0);
+    std::vector<uint32_t> at_depth(max_depth + 2, 0);
+    for (uint32_t j = 0; j < n; ++j) {
+        for (uint32_t v = R.leaf_node_in[j];; v = (uint32_t)R.parent[v]) { at_depth[R.depth[v]] = v; if (R.parent[v] < 0) break; }
+        for (uint32_t i = 0; i < n; ++i)
+            if (i != j) c->place_child[(size_t)i * n + j] = (uint16_t)at_depth[(R.lca[(size_t)i * n + j] >> 16) + 1];
+    }
+    // next[q][p], p < q: the end of the run of p over which lca(p,q) AND the child of it that holds p stay the same
+    c->place_next.assign((size_t)n * n, 0);
+    for (uint32_t q = 1; q < n; ++q) {
+        const size_t o = (size_t)q * n;
+        c->place_next[o + q - 1] = (uint16_t)q;
+        for (uint32_t p = q - 1; p-- > 0;)
+            c->place_next[o + p] = (R.lca[o + p] != R.lca[o + p + 1] || c->place_child[o + p] != c->place_child[o + p + 1]) ? (uint16_t)(p + 1) : c->place_next[o + p + 1];
+    }
+    DevBuf<uint16_t> child, next; DevBuf<uint32_t> node;
+    QS_HIP(c, child.reserve(c->place_child.size() * 2, nullptr));
+    QS_HIP(c, next.reserve(c->place_next.size() * 2, nullptr));
+    QS_HIP(c, node.reserve(std::max<size_t>(R.inner_node.size(), 1) * 4, nullptr));
+    QS_HIP(c, hipMemcpyAsync(child.get(), c->place_child.data(), c->place_child.size() * 2, hipMemcpyHostToDevice, c->stream));
+    QS_HIP(c, hipMemcpyAsync(next.get(), c->place_next.data(), c->place_next.size() * 2, hipMemcpyHostToDevice, c->stream));
+    QS_HIP(c, hipMemcpyAsync(node.get(), R.inner_node.data(), R.inner_node.size() * 4, hipMemcpyHostToDevice, c->stream));
+    c->place_child_dev = std::move(child); c->place_next_dev = std::move(next); c->place_node_dev = std::move(node);
+    return QS_OK;
+}
+
+// Link sums of the quartet placement of the listed taxa (qs_place.hip). The reference never asks where the evaluation trees would
+// put a taxon: this replaces nothing there.
+extern "C" int qs_taxon_placement(qs_ctx *c, const qs_ref_tree *ref, const uint16_t *taxa, uint32_t n_list, int64_t *dst_device) {
+    if (!c) return QS_ERR_ARG;
+    if (!dst_device) return fail(c, QS_ERR_ARG, "qs_taxon_placement: NULL argument");
+    if (reinterpret_cast<uintptr_t>(dst_device) % 8) return fail(c, QS_ERR_ARG, "qs_taxon_placement: dst_device is not 8-byte aligned");
+    if (!c->table) return fail(c, QS_ERR_STATE, "qs_taxon_placement: no table");
+    // every sum is at most C(n-1,3) x (largest count): the trees behind the table if known, else what a cell can hold (as qs_taxon_support)
+    const uint64_t cell_max = c->count_bits == 16 ? 0xFFFFull : 0xFFFFFFFFull;
+    const uint64_t trees = std::max(c->trees_counted, c->table_trees_hint);
+    const uint64_t max_count = trees ? std::min(trees, cell_max) : cell_max;
+    const uint64_t per_taxon = c->n >= 4 ? (uint64_t)(c->n - 1) * (c->n - 2) / 2 * (c->n - 3) / 3 : 0;
+    if (per_taxon && max_count > (uint64_t)INT64_MAX / per_taxon)
+        return fail(c, QS_ERR_OVERFLOW, "qs_taxon_placement: C(n-1,3) x the largest possible count exceeds 63 bits");
+    if (c->d_lo != 0 || c->d_hi != c->n) return fail(c, QS_ERR_UNSUPPORTED, "qs_taxon_placement: a table-shard context (the walks of a taxon cross every shard: use a whole-table one)");
+    if (taxa ? n_list == 0 || n_list > c->n : n_list != c->n) return fail(c, QS_ERR_ARG, taxa ? "qs_taxon_placement: the list needs 1 .. n_taxa entries" : "qs_taxon_placement: n_list must be n_taxa when taxa is NULL");
+    std::vector<uint16_t> list(n_list);
+    {
+        std::vector<uint8_t> seen(c->n, 0);
+        for (uint32_t i = 0; i < n_list; ++i) {
+            const uint32_t x = taxa ? taxa[i] : i;
+            if (x >= c->n) return fail(c, QS_ERR_ARG, "qs_taxon_placement: taxon id out of range");
+            if (seen[x]) return fail(c, QS_ERR_ARG, "qs_taxon_placement: taxon id " + std::to_string(x) + " is listed twice");
+            seen[x] = 1; list[i] = (uint16_t)x;
+        }
+    }
+    QS_HIP(c, hipSetDevice(c->device));
+    const RefHost *Rp = nullptr;
+    if (int rc = get_ref(c, ref, true, &Rp)) return rc;
+    if (place_lds_bytes(Rp->n_nodes) > 160u * 1024u)
+        return fail(c, QS_ERR_UNSUPPORTED, "qs_taxon_placement: more than 10240 nodes (the link sums of a workgroup live in LDS)");
+    if (int rc = ensure_place_ref(c, *Rp)) return rc;
+    if (c->n_cu == 0) { int v = 0; QS_HIP(c, hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device)); c->n_cu = std::max(1, v); }
+    if (!c->place_tasks_dev) {
+        // a walk = (middle id q, 64 consecutive largest ids): q steps; the long ones first
+        c->place_tasks.clear();
+        for (uint32_t q = c->n - 2; q >= 1; --q)
+            for (uint32_t g = 0; q + 1 + g * kWave < c->n; ++g) c->place_tasks.push_back(q | g << 16);
+        QS_HIP(c, c->place_tasks_dev.reserve(c->place_tasks.size() * 4, nullptr));
+        QS_HIP(c, hipMemcpyAsync(c->place_tasks_dev.get(), c->place_tasks.data(), c->place_tasks.size() * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    if (list != c->place_taxa || !c->place_taxa_dev) {
+        QS_HIP(c, hipStreamSynchronize(c->stream));   // (an earlier call's kernel and upload may still read the old list)
+        c->place_taxa = list;
+        QS_HIP(c, c->place_taxa_dev.reserve((size_t)c->n * 2, nullptr));
+        QS_HIP(c, hipMemcpyAsync(c->place_taxa_dev.get(), c->place_taxa.data(), (size_t)n_list * 2, hipMemcpyHostToDevice, c->stream));
+    }
+    PlaceDevice pd;
+    pd.ref_lca = c->ref_lca_dev.get(); pd.inner_node = c->place_node_dev.get(); pd.tasks = c->place_tasks_dev.get();
+    pd.child = c->place_child_dev.get(); pd.next = c->place_next_dev.get(); pd.taxa = c->place_taxa_dev.get();
+    pd.n = c->n; pd.n_nodes = Rp->n_nodes; pd.n_tasks = (uint32_t)c->place_tasks.size();
+    pd.table = c->table; pd.count_bits = (int)c->count_bits;   // the context's own table, not a scoring view
+    QS_HIP(c, hipMemsetAsync(dst_device, 0, (size_t)n_list * 2 * Rp->n_nodes * 8, c->stream));
+    // 32-bit partial sums: a walk has q < n_taxa steps, so 4096 x (largest count) < 2^32 suffices only while n_taxa <= 4096
+    // (qs_create's cap today; the LDS limit alone would allow more)
+    const bool wide = max_count >= (1ull << 32) / 4096 || c->n > 4096;
+    QS_HIP(c, launch_taxon_placement(c->stream, pd, n_list, wide, c->n_cu, reinterpret_cast<unsigned long long *>(dst_device)));
+    return QS_OK;   // asynchronous on the context's stream
+}
+
+// Host-only: the link sums of one taxon -> the placement score of every edge, by the preorder recurrence S(v) = S(parent v) -
+// W[N + parent v] + W[v] with S(root) = the sum of W over all parent links. No device, no context.
+extern "C" int qs_placement_scores(const qs_ref_tree *ref, const int64_t *links_host, int64_t *scores_host) {
+    if (!links_host || !scores_host) return fail(nullptr, QS_ERR_ARG, "qs_placement_scores: NULL argument");
+    RefHost R;
+    if (int rc = build_ref_shape(nullptr, ref, R)) return rc;
+    const uint32_t N = R.n_nodes;
+    std::vector<uint32_t> order(N);
+    for (uint32_t v = 0; v < N; ++v) order[v] = v;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return R.depth[a] < R.depth[b]; });   // parents first
+    int64_t tot_up = 0;
+    for (uint32_t v = 0; v < N; ++v) tot_up += links_host[N + v];
+    scores_host[R.root] = tot_up;
+    for (uint32_t v : order) {
+        if (v == R.root) continue;
+        const uint32_t p = (uint32_t)R.parent[v];
+        scores_host[v] = scores_host[p] - links_host[N + p] + links_host[v];
+    }
+    scores_host[R.root] = 0;
+    return QS_OK;
 }
 
 extern "C" int qs_score_plan(uint32_t n_taxa, uint64_t rank_lo, uint64_t n_tuples, uint32_t *first_pair, uint32_t *n_pairs, uint64_t parts[4]) {

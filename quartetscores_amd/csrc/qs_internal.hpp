@@ -152,6 +152,20 @@ struct ScoreDevice;
 constexpr int kTaxonWaves = 12;   // waves per workgroup = consecutive b per round (the logging pass 1's count, qs_score.hip)
 size_t taxon_lds_bytes(uint32_t n);
 hipError_t launch_taxon_support(hipStream_t s, const ScoreDevice &sd, bool wide, int n_cu, unsigned long long *dst);
+// qs_place.hip: link sums of the quartet placement of the taxa pd.taxa[0 .. n_list) (qs_taxon_placement); whole tables only. child[i][j] =
+// node of the child of lca(i,j) that holds leaf j; next[q][p], p < q = the first p' > p at which lca(p',q) or child[q][p'] differs (q if
+// none); inner_node = node index of a compact inner id of ref_lca; tasks = q | group of 64 largest ids << 16, longest walks first;
+// dst = n_list rows of 2 x n_nodes words, zeroed beforehand; wide: counts may reach 2^32 / 4096
+struct PlaceDevice {
+    const uint32_t *ref_lca, *inner_node, *tasks;
+    const uint16_t *child, *next, *taxa;
+    uint32_t n, n_nodes, n_tasks;
+    const void *table;
+    int count_bits;
+};
+constexpr int kPlaceWaves = 4;
+size_t place_lds_bytes(uint32_t n_nodes);
+hipError_t launch_taxon_placement(hipStream_t s, const PlaceDevice &pd, uint32_t n_list, bool wide, int n_cu, unsigned long long *dst);
 size_t gather_lds_bytes(uint32_t d_hi);
 uint32_t gather_tiles_for_c(uint32_t c); // workgroups of the gather kernel per (d-block, c)
 

@@ -81,6 +81,83 @@ def taxon_columns(counts) -> dict:
     return out
 
 
+PLACEMENT_COLUMNS = ("taxon", "name", "current", "best", "gain", "n_best", "best_node", "best_lo", "best_hi", "distance")
+
+
+def placement_scores(ref: flatten.RefTree, links) -> np.ndarray:
+    """qs_placement_scores (host-only, no device): rows of link sums (n_list, 2 * n_nodes) of Context.taxon_placement -> int64
+    (n_list, n_nodes), the placement score of the edge above every node; the root's entry is 0."""
+    L = _lib.load()
+    W = np.ascontiguousarray(links, dtype=np.int64).reshape(-1, 2 * ref.n_nodes)
+    out = np.zeros((len(W), ref.n_nodes), dtype=np.int64)
+    s, keep = Context._ref_struct(ref)
+    for row, dst in zip(W, out):
+        rc = L.qs_placement_scores(C.byref(s), row.ctypes.data_as(C.c_void_p), dst.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise QSError(rc, L.qs_last_error(None).decode())
+    del keep
+    return out
+
+
+def placement_columns(ref: flatten.RefTree, taxa, scores) -> dict:
+    """The columns of QuartetScores --place-taxa (PLACEMENT_COLUMNS) for the listed taxa (lookup ids) and their rows of
+    placement_scores. A position = the edges that induce the same bipartition of the OTHER taxa (the taxon's own pendant edge
+    belongs to the position of the two other edges at a parent with three links). current = the score at the taxon's own edge,
+    best = the largest score, n_best = positions that attain it; the reported position is the current one if it attains best,
+    else the one that holds the smallest node index; best_node = its smallest node index, [best_lo, best_hi) the lookup ids
+    below that node; distance = 0 for the current position, else the nodes on the path from the taxon's parent to the nearer end
+    of the edge above best_node that keep three links without the taxon (1 = an NNI neighbour)."""
+    parent = np.asarray(ref.parent, dtype=np.int64)
+    N, n = len(parent), ref.n_taxa
+    root = int(np.nonzero(parent < 0)[0][0])
+    order = newick.preorder(ref.root)
+    depth = np.zeros(N, dtype=np.int64)
+    for x in order[1:]:
+        depth[x.index] = depth[x.parent.index] + 1
+    lo, hi = np.full(N, n, dtype=np.int64), np.zeros(N, dtype=np.int64)
+    leaf_node = np.asarray(ref.leaf_node, dtype=np.int64)
+    lo[leaf_node], hi[leaf_node] = np.arange(n), np.arange(n) + 1
+    for x in reversed(order[1:]):                      # children before parents
+        p = x.parent.index
+        lo[p], hi[p] = min(lo[p], lo[x.index]), max(hi[p], hi[x.index])
+    links = np.bincount(parent[parent >= 0], minlength=N) + (parent >= 0)
+    edges = np.arange(N) != root
+    sc = np.asarray(scores, dtype=np.int64).reshape(len(taxa), N)
+
+    def walk(a, b):
+        left, right = [a], [b]
+        while left[-1] != right[-1]:
+            if depth[left[-1]] >= depth[right[-1]]:
+                left.append(int(parent[left[-1]]))
+            else:
+                right.append(int(parent[right[-1]]))
+        return left + right[-2::-1]
+
+    out = {name: [] for name in PLACEMENT_COLUMNS}
+    for row, x in zip(sc, taxa):
+        x = int(x)
+        a, b = lo - (lo > x), hi - (hi > x)            # the interval below every node in the others' numbering
+        flip = (a == 0) & (b > 0)
+        a, b = np.where(flip, b, a), np.where(flip, n - 1, b)
+        key = np.where(b > a, a * n + b, 0)            # the side without the smallest other taxon; 0 = all others on one side
+        own = int(leaf_node[x])
+        u = int(parent[own])
+        if links[u] == 3:
+            key[own] = key[[w for w in np.nonzero(parent == u)[0] if w != own][0]]
+        current, best = int(row[own]), int(row[edges].max())
+        top = edges & (row == best)
+        pick = key[own] if current == best else key[np.nonzero(top)[0][0]]
+        node = int(np.nonzero(edges & (key == pick))[0][0])
+        dist = 0
+        if pick != key[own]:
+            near = min((walk(u, node), walk(u, int(parent[node]))), key=len)
+            dist = sum(1 for w in near if links[w] - (w == u) >= 3)
+        vals = (x, ref.names[x], current, best, best - current, len(np.unique(key[top])), node, int(lo[node]), int(hi[node]), dist)
+        for name, val in zip(PLACEMENT_COLUMNS, vals):
+            out[name].append(val)
+    return {k: (v if k == "name" else np.array(v, dtype=np.int64)) for k, v in out.items()}
+
+
 class Context:
     """Thin RAII wrapper of qs_ctx."""
 
@@ -224,6 +301,28 @@ class Context:
         self.sync()
         del keep
         return buf.cpu().numpy().reshape(self.n, 6)
+
+    def taxon_placement(self, ref: flatten.RefTree, taxa=None) -> np.ndarray:
+        """qs_taxon_placement: per listed taxon (lookup ids; None = all, in id order) the 2 * n_nodes link sums W_x of its
+        quartet placement on `ref` from this context's whole table -> int64 (n_list, 2 * n_nodes); placement_scores turns them
+        into the score of every edge, placement_columns into the CLI's columns. Allocates the device buffer, waits for the
+        result and downloads it."""
+        import torch
+        ids = None
+        if taxa is not None:
+            wide = np.asarray(taxa, dtype=np.int64).reshape(-1)
+            if ((wide < 0) | (wide >= self.n)).any():     # (before the cast to the ABI's 16-bit ids, which would wrap)
+                raise QSError(_lib.QS_ERR_ARG, "taxon_placement: taxon id out of range")
+            ids = np.ascontiguousarray(wide, dtype=np.uint16)
+        n_list = self.n if ids is None else len(ids)
+        width = 2 * ref.n_nodes
+        buf = torch.empty(max(1, n_list * width), dtype=torch.int64, device=f"cuda:{self.device}")
+        s, keep = self._ref_struct(ref)
+        self._chk(self.L.qs_taxon_placement(self.h, C.byref(s), None if ids is None else ids.ctypes.data_as(C.c_void_p), n_list,
+                                            C.c_void_p(buf.data_ptr())))
+        self.sync()
+        del keep
+        return buf[: n_list * width].cpu().numpy().reshape(n_list, width)
 
     def table_clear(self):
         self._chk(self.L.qs_table_clear(self.h))

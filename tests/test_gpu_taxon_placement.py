@@ -1,0 +1,195 @@
+"""qs_taxon_placement / Context.taxon_placement: the link sums of every taxon's quartet placement, bit for bit against the numpy
+model of the downloaded table (tests/placement_model.py), on the reference shapes that break runs, for lists, at 512 taxa through
+the two identities with qs_taxon_support, with counts near 2^32, repeatable, without side effects, and every error code."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import placement_model as P
+from helpers import binom
+from quartetscores_amd import _lib, flatten, synth
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def eng():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a device"
+    from quartetscores_amd import engine
+    return engine
+
+
+def mixed_trees(n, seed):
+    """dropout, collapsed edges and rooted trees in one batch (as tests/test_gpu_taxon_support.py)"""
+    return (synth.tree_set(n, 12, seed, dropout=0.2) + synth.tree_set(n, 12, seed + 1, collapse=0.3) +
+            synth.tree_set(n, 12, seed + 2, rooted=True) + synth.tree_set(n, 6, seed + 3))
+
+
+def reference(n, kind, seed):
+    rng = np.random.default_rng(seed)
+    kw = {"binary": {}, "multifurcating": {"collapse": 0.4}, "rooted": {"rooted": True}}[kind]
+    return flatten.flatten_reference(synth.random_tree(n, rng, **kw))
+
+
+def counted(eng, ref, trees, bits):
+    ctx = eng.Context(ref.n_taxa, bits)
+    ctx.table_alloc()
+    ctx.count_trees(flatten.flatten_eval_trees(trees, ref.name_to_id))
+    return ctx
+
+
+@pytest.mark.parametrize("kind", ["binary", "multifurcating", "rooted"])
+@pytest.mark.parametrize("bits", [16, 32])
+@pytest.mark.parametrize("n", [4, 5, 7, 9, 17, 33, 65, 130])
+def test_equals_model_of_the_downloaded_table(eng, n, bits, kind):
+    ref = reference(n, kind, 1000 + n)
+    ctx = counted(eng, ref, mixed_trees(n, 300 + n), bits)
+    got = ctx.taxon_placement(ref)
+    assert got.dtype == np.int64 and got.shape == (n, 2 * ref.n_nodes)
+    want = P.link_sums(ctx.table_download(), ref)
+    assert (got == want).all()
+    assert want.sum() > 0
+
+
+def caterpillar(names):
+    return names[0] if len(names) == 1 else "(" + names[0] + "," + caterpillar(names[1:]) + ")"
+
+
+def special_reference(shape, n):
+    names = [f"t{i}" for i in np.random.default_rng(5).permutation(n)]
+    if shape == "ladder":            # every run of lca(p,q) has length 1
+        return caterpillar(names) + ";"
+    if shape == "star":
+        return "(" + ",".join(names) + ");"
+    # a node with six children, every child a small clade: the child that holds p changes inside one run of lca(p,q)
+    clades = ["(" + ",".join(names[i:i + 4]) + ")" for i in range(0, 24, 4)]
+    return "((" + ",".join(clades) + ")," + caterpillar(names[24:]) + ");"
+
+
+@pytest.mark.parametrize("bits", [16, 32])
+@pytest.mark.parametrize("shape", ["ladder", "star", "wide_node"])
+def test_special_reference_shapes(eng, shape, bits):
+    n = 40
+    ref = flatten.flatten_reference(special_reference(shape, n))
+    if shape == "wide_node":
+        assert np.bincount(ref.parent[ref.parent >= 0]).max() >= 5
+    ctx = counted(eng, ref, mixed_trees(n, 77), bits)
+    got = ctx.taxon_placement(ref)
+    assert (got == P.link_sums(ctx.table_download(), ref)).all()
+
+
+def test_a_list_gives_the_rows_of_the_all_taxa_call(eng):
+    n = 37
+    ref = reference(n, "multifurcating", 21)
+    ctx = counted(eng, ref, mixed_trees(n, 22), 16)
+    every = ctx.taxon_placement(ref)
+    for taxa in ([30, 2, 17, 36, 0, 9], [11], [0], [n - 1], list(range(n))[::-1]):
+        got = ctx.taxon_placement(ref, taxa)
+        assert got.shape == (len(taxa), 2 * ref.n_nodes)
+        assert (got == every[taxa]).all(), taxa
+
+
+def test_identities_at_512_taxa(eng):
+    # no model at this size: the two identities with qs_taxon_support, from a small count into 16-bit cells
+    n = 512
+    ref = reference(n, "multifurcating", 2512)
+    ctx = counted(eng, ref, mixed_trees(n, 912), 16)
+    links = ctx.taxon_placement(ref)
+    support = ctx.taxon_support(ref)
+    sc = eng.placement_scores(ref, links)
+    own = sc[np.arange(n), ref.leaf_node.astype(np.int64)]
+    assert (own == support[:, 1]).all()                              # current = concordant
+    assert (links.sum(axis=1) == support[:, 1:4].sum(axis=1)).all()  # every triple has a median
+    assert support[:, 1].min() > 0 and support[:, 3].sum() > 0 and (links >= 0).all()
+
+
+def test_large_counts_take_the_wide_sums(eng):
+    # counts close to 2^32 behind an uploaded 32-bit table (trees unknown): 64-bit partial sums
+    n = 40
+    ref = reference(n, "multifurcating", 10)
+    ctx = eng.Context(n, 32)
+    ctx.table_alloc()
+    rng = np.random.default_rng(11)
+    table = rng.integers(0, 1 << 32, size=(int(binom(n, 4)), 3), dtype=np.uint64).astype(np.uint32)
+    table[rng.random(len(table)) < 0.2] = 0
+    ctx.table_upload(table)
+    want = P.link_sums(table, ref)                                   # (exact int64 sums: the model switches at 2^52)
+    assert want.max() > 1 << 40
+    assert (ctx.taxon_placement(ref) == want).all()
+    # the same table, said to hold few trees (every count masked below the hint): the 32-bit partial sums
+    small = (table & 0xFFF).astype(np.uint32)
+    ctx.table_upload(small)
+    ctx.set_tuning(_lib.QS_TUNE_TABLE_TREES, 0xFFF)
+    assert (ctx.taxon_placement(ref) == P.link_sums(small, ref)).all()
+
+
+def test_repeatable_and_without_side_effects(eng):
+    n = 48
+    ref = reference(n, "binary", 12)
+    trees = mixed_trees(n, 13)
+    ctx = counted(eng, ref, trees, 32)
+    before = ctx.table_download()
+    score_before = [np.asarray(x, dtype=np.float64).view(np.int64) for x in ctx.score(ref)[:3]]
+    first = ctx.taxon_placement(ref)
+    assert (ctx.taxon_placement(ref) == first).all()
+    assert (ctx.taxon_placement(ref, [5, 40]) == first[[5, 40]]).all()
+    assert (ctx.taxon_placement(ref) == first).all()
+    assert (ctx.table_download() == before).all() and ctx.trees_counted == len(trees)
+    for x, y in zip(score_before, [np.asarray(x, dtype=np.float64).view(np.int64) for x in ctx.score(ref)[:3]]):
+        assert (x == y).all()
+    # another reference tree over the same table, then the first one again: the cached link lookups follow the tree
+    other = reference(n, "multifurcating", 99)
+    perm = flatten.taxon_permutation(other, ref)
+    moved = eng.Context(n, 32)
+    moved.table_alloc()
+    moved.table_remap(ctx, perm)
+    assert (moved.taxon_placement(other) == P.link_sums(moved.table_download(), other)).all()
+    assert (ctx.taxon_placement(ref) == first).all()
+
+
+def test_error_codes(eng):
+    import torch
+    n = 12
+    ref = reference(n, "binary", 14)
+    ctx = counted(eng, ref, mixed_trees(n, 15), 32)
+    want = ctx.taxon_placement(ref)
+
+    def code(f):
+        with pytest.raises(eng.QSError) as ei:
+            f()
+        return ei.value.code
+
+    assert code(lambda: eng.Context(n, 32).taxon_placement(ref)) == _lib.QS_ERR_STATE            # no table
+    assert code(lambda: ctx.taxon_placement(reference(n + 1, "binary", 14))) == _lib.QS_ERR_ARG    # n_taxa differs
+    bad = reference(n, "binary", 14)
+    bad.leaf_node = bad.leaf_node.copy()
+    bad.leaf_node[[0, n - 1]] = bad.leaf_node[[n - 1, 0]]   # ids 0 and n-1 swapped: not depth-first any more
+    assert code(lambda: ctx.taxon_placement(bad)) == _lib.QS_ERR_ARG
+    malformed = reference(n, "binary", 14)
+    malformed.parent = np.full_like(malformed.parent, -1)
+    assert code(lambda: ctx.taxon_placement(malformed)) == _lib.QS_ERR_ARG
+    assert code(lambda: ctx.taxon_placement(ref, [3, n])) == _lib.QS_ERR_ARG                        # an id >= n
+    assert code(lambda: ctx.taxon_placement(ref, [3, 5, 3])) == _lib.QS_ERR_ARG                     # repeated
+    assert code(lambda: ctx.taxon_placement(ref, [65536 + 3])) == _lib.QS_ERR_ARG                   # (not wrapped into a 16-bit id)
+    ids = np.array([3, n], dtype=np.uint16)
+    out = torch.zeros(2 * 2 * ref.n_nodes, dtype=torch.int64, device="cuda")
+    s_, keep_ = ctx._ref_struct(ref)
+    assert ctx.L.qs_taxon_placement(ctx.h, C.byref(s_), ids.ctypes.data_as(C.c_void_p), 2, C.c_void_p(out.data_ptr())) == _lib.QS_ERR_ARG   # the library's own check
+    buf = torch.zeros(n * 2 * ref.n_nodes + 1, dtype=torch.int64, device="cuda")
+    s, keep = ctx._ref_struct(ref)
+    assert ctx.L.qs_taxon_placement(ctx.h, C.byref(s), None, n, C.c_void_p(buf.data_ptr() + 4)) == _lib.QS_ERR_ARG   # misaligned
+    assert ctx.L.qs_taxon_placement(ctx.h, C.byref(s), None, n, None) == _lib.QS_ERR_ARG
+    assert ctx.L.qs_taxon_placement(ctx.h, C.byref(s), None, n - 1, C.c_void_p(buf.data_ptr())) == _lib.QS_ERR_ARG   # NULL list: all taxa
+    shard = eng.Context(n, 32, d_lo=4, d_hi=8)
+    shard.table_alloc()
+    assert code(lambda: shard.taxon_placement(ref)) == _lib.QS_ERR_UNSUPPORTED                      # a table shard
+    # C(2999,3) x (2^32 - 1) does not fit 63 bits (only a shard of such a table can exist: the bound is looked at first)
+    big_ref = reference(3000, "binary", 16)
+    big = eng.Context(3000, 32, d_lo=4, d_hi=6)
+    big.table_alloc()
+    assert code(lambda: big.taxon_placement(big_ref, [0])) == _lib.QS_ERR_OVERFLOW
+    big.set_tuning(_lib.QS_TUNE_TABLE_TREES, 1000)
+    assert code(lambda: big.taxon_placement(big_ref, [0])) == _lib.QS_ERR_UNSUPPORTED
+    assert (ctx.taxon_placement(ref) == want).all()            # and the context still works after the refusals
