@@ -22,6 +22,7 @@
  *                                 line per quartet, which a user would reduce per taxon on the host)
  *   qs_taxon_placement /          replace nothing in the reference (it never asks where the evaluation trees would put a taxon; the
  *   qs_placement_scores           nearest route is one more reference tree and one more run per candidate position)
+ *   qs_clade_placement            replaces nothing in the reference (it never asks where the evaluation trees would put a subtree)
  *   qs_score                      QuartetScoreComputer: processNodePair /
  *                                 computeQuartetScoresBifurcating / ...Multifurcating
  *                                 (QuartetScoreComputer.hpp:379-593) + getLQIC/QPIC/EQPICScores (:106-125)
@@ -391,6 +392,25 @@ int qs_taxon_placement(qs_ctx *ctx, const qs_ref_tree *ref, const uint16_t *taxa
  * the same bipartition of the other taxa get equal scores (x's pendant edge and the two other edges at a degree-3 parent; the two
  * edges at a degree-2 root). QS_ERR_ARG = NULL argument or malformed tree. Replaces nothing in the reference. */
 int qs_placement_scores(const qs_ref_tree *ref, const int64_t *links_host, int64_t *scores_host);
+/* Quartet placement of clades on the reference tree from the count table: where would the evaluation trees put the subtree C below a
+ * non-root node c of the reference tree T? Prune C and regraft it, unchanged inside, on an edge e of T without C (one SPR move). Only
+ * the 4-sets with exactly one taxon x of C depend on e, and as in qs_taxon_placement: with p < q < r outside C, n(xp|qr), n(xq|pr) and
+ * n(xr|pq) belong to the links of the median node of p, q, r that lead towards p, q and r. Row i of dst_device is the sum W_C of these
+ * over x in C and all triples outside C for c = nodes[i]; qs_placement_scores, unchanged, turns it into the score of
+ * every edge OUTSIDE C: that part of the total quartet score which depends on where C hangs (the rest is the same at every position).
+ * In a row of scores the entries of the nodes strictly inside C are not positions (all links into and out of C's nodes are 0); the
+ * entry of c itself is the score of C's current position -- equal to the scores of the two other edges at parent[c] when that node
+ * has three links, the score "at the node" under a multifurcation.
+ * nodes = host array of n_list distinct non-root node indices (lent for the call); a leaf is allowed, its row is that taxon's row of
+ * qs_taxon_placement. Every listed node needs at least three taxa outside it. dst_device (caller-owned device memory, 8-byte aligned,
+ * n_list x 2 * n_nodes words) is OVERWRITTEN, one row per list entry in list order. Link indexing, exactness, caching (the link lookups
+ * of the reference are shared with qs_taxon_placement), stream order and side effects (none) as for qs_taxon_placement.
+ * Errors: QS_ERR_STATE = no table; QS_ERR_ARG = NULL / misaligned dst, NULL list or n_list = 0, a node index >= n_nodes, the root, a
+ * repeated node, fewer than three taxa outside a node, malformed reference, n_taxa differs from the context's, ids not in depth-first
+ * order; QS_ERR_OVERFLOW = |C| x C(n_taxa-|C|,3) x (the trees behind the table if known, else the largest count a cell holds) exceeds
+ * 63 bits for a listed clade; QS_ERR_UNSUPPORTED = a table-shard context (whole tables only), or more than 10240 nodes. Asynchronous
+ * on the context's stream. The reference has no such output: this replaces nothing there. */
+int qs_clade_placement(qs_ctx *ctx, const qs_ref_tree *ref, const uint32_t *nodes, uint32_t n_list, int64_t *dst_device);
 
 /* ---- scoring (QuartetScoreComputer) ----------------------------------------------------- */
 

@@ -37,7 +37,7 @@ EXPORTS = [
     "qs_set_tuning", "qs_last_count_launches", "qs_batch_flags", "qs_score_overflow", "qs_free_host", "qs_raw_qic_lex",
     "qs_score_plan", "qs_last_score_ms", "qs_prepare", "qs_table_pack32x2", "qs_unpack32x2", "qs_last_score_log", "qs_last_score_estimate", "qs_score_prepare",
     "qs_sum_words", "qs_issue_probe", "qs_last_count_fix_ms", "qs_batch_clamp_info", "qs_depth_clamp_plan", "qs_score_check", "qs_last_count_events", "qs_class_plan", "qs_shard_bounds",
-    "qs_table_remap", "qs_tree_agreement", "qs_taxon_support", "qs_table_restrict", "qs_taxon_placement", "qs_placement_scores",
+    "qs_table_remap", "qs_tree_agreement", "qs_taxon_support", "qs_table_restrict", "qs_taxon_placement", "qs_placement_scores", "qs_clade_placement",
 ]
 
 
@@ -117,6 +117,8 @@ def load():
     L.qs_taxon_placement.argtypes = [vp, vp, vp, u32, vp]
     L.qs_placement_scores.restype = i32
     L.qs_placement_scores.argtypes = [vp, vp, vp]
+    L.qs_clade_placement.restype = i32
+    L.qs_clade_placement.argtypes = [vp, vp, vp, u32, vp]
     L.qs_sum_words.restype = i32
     L.qs_sum_words.argtypes = [vp, vp, vp, u32, u64]
     L.qs_table_device_ptr.restype = vp

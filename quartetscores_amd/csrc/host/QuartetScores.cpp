@@ -16,11 +16,14 @@
 // pruned (newick.hpp prune) and the table cut down to the kept taxa (qs_table_restrict) instead of pruning every tree and recounting.
 // --place-taxa FILE [--place-only NAMES] writes where the evaluation trees would put every (listed) taxon of the -r tree: the quartet
 // score of each edge as a position of the taxon, from the same count table (qs_taxon_placement, qs_placement_scores).
+// --place-clades FILE [--place-clades-only SPEC] does the same for whole clades of the -r tree, pruned and regrafted unchanged inside
+// (qs_clade_placement, qs_placement_scores).
 #include "QuartetScoreComputer.hpp"
 #include "multi_gpu.hpp"
 #include "table_shards.hpp"
 
 #include <cerrno>
+#include <map>
 #include <set>
 #include <sstream>
 #include <cstdlib>
@@ -71,6 +74,9 @@ struct Args {
     std::string place_taxa; // --place-taxa FILE: quartet placement of the taxa of -r from the count table (TSV)
     std::string place_only; // --place-only NAMES: a file of the taxon labels to place (default: all)
     std::vector<uint16_t> place_ids;   // the lookup ids to place, ascending (check_place_taxa)
+    std::string place_clades;      // --place-clades FILE: quartet placement of the clades of -r from the count table (TSV)
+    std::string place_clades_only; // --place-clades-only SPEC: a file of the clades to place, one per line (default: every eligible inner clade)
+    std::vector<uint32_t> place_nodes; // the nodes to place, in output order (check_place_clades)
     std::vector<AlsoRef> also;
     std::vector<WithoutTaxa> without;
     size_t threads = 0;
@@ -147,7 +153,19 @@ void usage(std::ostream &os) {
           "                  distance = nodes between the two positions (0 = where it is, 1 = an NNI away). One gather over the table per\n"
           "                  taxon; one GPU with the whole table (not with --gpus / --table-shards); works with --load-table, --per-taxon,\n"
           "                  --per-tree, --also-ref and --without-taxa (always the full -r tree)\n"
-          "   --place-only NAMES  with --place-taxa: place only the taxa listed in NAMES (one label per line, as for --without-taxa)\n";
+          "   --place-only NAMES  with --place-taxa: place only the taxa listed in NAMES (one label per line, as for --without-taxa)\n"
+          "   --place-clades F  write, per inner clade of the -r tree, where the evaluation trees would put the whole clade to F (TSV, one\n"
+          "                  line per clade in node order after a header: clade node lo hi size current best gain n_best best_node best_lo\n"
+          "                  best_hi distance). The clade (the subtree below `node`, lookup ids [lo, hi)) is pruned and regrafted, unchanged\n"
+          "                  inside, on every edge outside it: one subtree-prune-and-regraft move per position. The score of a position =\n"
+          "                  the sum, over the quartets with exactly one taxon of the clade, of the count of the topology the -r tree shows\n"
+          "                  with the clade there (the other quartets do not see the move); the columns as for --place-taxa with the clade\n"
+          "                  in the taxon's place (distance 1 = an NNI of the clade). Every inner clade with at least three taxa outside it\n"
+          "                  is placed; one GPU with the whole table (not with --gpus / --table-shards); works with --load-table and\n"
+          "                  beside the other outputs (always the full -r tree)\n"
+          "   --place-clades-only SPEC  with --place-clades: place only the clades of SPEC, in its order: one clade per line, given as one\n"
+          "                  or more labels separated by tabs = the smallest subtree of the -r tree, as rooted in its file, that holds\n"
+          "                  them all (one label: that leaf)\n";
 }
 
 // returns 0 ok, 1 error (message printed like the reference prints TCLAP::ArgException), 2 exit quietly
@@ -222,6 +240,8 @@ int parse(int argc, char **argv, Args &a) {
         else if (f == "--per-taxon") { if (!(v = need(i, "--per-taxon"))) return 1; a.per_taxon = v; }
         else if (f == "--place-taxa") { if (!(v = need(i, "--place-taxa"))) return 1; a.place_taxa = v; }
         else if (f == "--place-only") { if (!(v = need(i, "--place-only"))) return 1; a.place_only = v; }
+        else if (f == "--place-clades") { if (!(v = need(i, "--place-clades"))) return 1; a.place_clades = v; }
+        else if (f == "--place-clades-only") { if (!(v = need(i, "--place-clades-only"))) return 1; a.place_clades_only = v; }
         else if (f == "--load-table") { if (!(v = need(i, "--load-table"))) return 1; a.dev.load_table = v; }
         else if (f == "--also-ref") {
             if (i + 2 >= argc || argv[i + 2][0] == '-') {
@@ -452,6 +472,26 @@ void write_per_taxon(qs_ctx *ctx, const RefFlat &ref, int device, const std::str
     if (!f) throw std::runtime_error("cannot write " + path);
 }
 
+// The shape of a flattened reference tree that the placement outputs need: nodes are numbered in preorder (parents first)
+struct PlaceShape {
+    size_t root = 0;
+    std::vector<uint32_t> depth, links;
+    std::vector<int64_t> lo, hi;   // the lookup ids below a node: [lo, hi)
+    PlaceShape(const RefFlat &ref, const char *flag) {
+        const size_t n = ref.names.size(), N = ref.parent.size();
+        depth.assign(N, 0); links.assign(N, 0); lo.assign(N, (int64_t)n); hi.assign(N, 0);
+        for (size_t v = 0; v < N; ++v) {
+            const int32_t p = ref.parent[v];
+            if (p < 0) { root = v; continue; }
+            if ((size_t)p >= v) throw std::runtime_error(std::string(flag) + ": the reference tree is not numbered in preorder");
+            depth[v] = depth[p] + 1; links[v] += 1; links[p] += 1;
+        }
+        for (size_t i = 0; i < n; ++i) { lo[ref.leaf_node[i]] = (int64_t)i; hi[ref.leaf_node[i]] = (int64_t)i + 1; }
+        for (size_t v = N; v-- > 0;)
+            if (ref.parent[v] >= 0) { const size_t p = (size_t)ref.parent[v]; lo[p] = std::min(lo[p], lo[v]); hi[p] = std::max(hi[p], hi[v]); }
+    }
+};
+
 // --place-taxa: refused before the device is touched where the whole table is not on one GPU, where FILE exists or is another output,
 // and where --place-only names a label the -r tree lacks; leaves the lookup ids to place in a.place_ids
 void check_place_taxa(Args &a) {
@@ -495,19 +535,10 @@ void write_place_taxa(qs_ctx *ctx, const RefFlat &ref, int device, const std::st
         throw std::runtime_error(std::string("--place-taxa: ") + qs_last_error(ctx));
     std::vector<int64_t> w(L * 2 * N);
     if (hipMemcpy(w.data(), dev.get(), w.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("--place-taxa: download failed");
-    // the tree's shape: nodes are numbered in preorder (parents first)
-    size_t root = 0;
-    std::vector<uint32_t> depth(N, 0), links(N, 0);
-    std::vector<int64_t> lo(N, (int64_t)n), hi(N, 0);
-    for (size_t v = 0; v < N; ++v) {
-        const int32_t p = ref.parent[v];
-        if (p < 0) { root = v; continue; }
-        if ((size_t)p >= v) throw std::runtime_error("--place-taxa: the reference tree is not numbered in preorder");
-        depth[v] = depth[p] + 1; links[v] += 1; links[p] += 1;
-    }
-    for (size_t i = 0; i < n; ++i) { lo[ref.leaf_node[i]] = (int64_t)i; hi[ref.leaf_node[i]] = (int64_t)i + 1; }
-    for (size_t v = N; v-- > 0;)
-        if (ref.parent[v] >= 0) { const size_t p = (size_t)ref.parent[v]; lo[p] = std::min(lo[p], lo[v]); hi[p] = std::max(hi[p], hi[v]); }
+    const PlaceShape S(ref, "--place-taxa");
+    const size_t root = S.root;
+    const std::vector<uint32_t> &depth = S.depth, &links = S.links;
+    const std::vector<int64_t> &lo = S.lo, &hi = S.hi;
     auto walk = [&](size_t a, size_t b) {   // nodes on the path from a to b, both inclusive
         std::vector<size_t> left{a}, right{b};
         while (left.back() != right.back()) {
@@ -549,6 +580,130 @@ void write_place_taxa(qs_ctx *ctx, const RefFlat &ref, int device, const std::st
         }
         f << x << '\t' << ref.names[x] << '\t' << current << '\t' << best << '\t' << (best - current) << '\t' << top.size() << '\t' << node << '\t'
           << lo[node] << '\t' << hi[node] << '\t' << dist << '\n';
+    }
+    if (!f) throw std::runtime_error("cannot write " + path);
+}
+
+// --place-clades: refused before the device is touched where the whole table is not on one GPU, where FILE exists or is another output,
+// and where a line of --place-clades-only names a label the -r tree lacks, the whole tree, a clade with fewer than three taxa outside it
+// or a clade an earlier line names; leaves the nodes to place in a.place_nodes
+void check_place_clades(Args &a) {
+    if (a.place_clades.empty()) {
+        if (!a.place_clades_only.empty()) throw std::runtime_error("--place-clades-only needs --place-clades FILE");
+        return;
+    }
+    if (a.gpus > 0 || a.table_shards >= 0)
+        throw std::runtime_error("--place-clades needs the whole count table on one GPU: omit --gpus / --table-shards");
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa};
+    for (const AlsoRef &x : a.also) others.insert(x.out);
+    for (const WithoutTaxa &x : a.without) others.insert(x.out);
+    if (others.count(a.place_clades)) throw std::runtime_error("--place-clades: " + a.place_clades + " is also another output file");
+    if (std::ifstream(a.place_clades).good()) throw std::runtime_error("--place-clades: the output file " + a.place_clades + " already exists");
+    Tree primary;
+    {
+        const std::string text = slurp(a.ref);
+        NewickReader rr(text);
+        if (!rr.next(primary)) throw std::runtime_error("empty reference tree file");
+    }
+    const RefFlat rf = flatten_reference(primary);
+    const PlaceShape S(rf, "--place-clades");
+    const size_t n = rf.names.size(), N = rf.parent.size();
+    std::vector<uint32_t> nchild(N, 0);
+    for (size_t v = 0; v < N; ++v) if (rf.parent[v] >= 0) nchild[rf.parent[v]]++;
+    if (a.place_clades_only.empty()) {
+        for (size_t v = 0; v < N; ++v)
+            if (v != S.root && nchild[v] && n - (size_t)(S.hi[v] - S.lo[v]) >= 3) a.place_nodes.push_back((uint32_t)v);
+        if (a.place_nodes.empty()) throw std::runtime_error("--place-clades: the reference tree " + a.ref + " has no inner clade with at least three taxa outside it");
+        return;
+    }
+    std::map<uint32_t, size_t> line_of;
+    std::istringstream lines(slurp(a.place_clades_only));
+    size_t line_no = 0;
+    for (std::string line; std::getline(lines, line);) {
+        ++line_no;
+        const std::string what = "--place-clades-only " + a.place_clades_only + " line " + std::to_string(line_no) + ": ";
+        if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+        int64_t first = (int64_t)n, last = -1;
+        std::istringstream fields(line);
+        for (std::string field; std::getline(fields, field, '\t');) {
+            const size_t b = field.find_first_not_of(" \r"), e = field.find_last_not_of(" \r");
+            if (b == std::string::npos) continue;
+            const std::string name = field.substr(b, e - b + 1);
+            const auto it = rf.name_to_id.find(name);
+            if (it == rf.name_to_id.end()) throw std::runtime_error(what + "the taxon " + name + " is not in the reference tree " + a.ref);
+            first = std::min(first, (int64_t)it->second); last = std::max(last, (int64_t)it->second);
+        }
+        // the smallest subtree that holds all labels: from the first label's leaf upwards until the last label is below as well
+        size_t v = rf.leaf_node[(size_t)first];
+        while (!(S.lo[v] <= first && last < S.hi[v])) v = (size_t)rf.parent[v];
+        if (v == S.root) throw std::runtime_error(what + "the smallest subtree that holds these labels is the whole reference tree");
+        if (n - (size_t)(S.hi[v] - S.lo[v]) < 3)
+            throw std::runtime_error(what + "the clade leaves fewer than three taxa outside it (" + std::to_string(n - (size_t)(S.hi[v] - S.lo[v])) + ")");
+        const auto ins = line_of.emplace((uint32_t)v, line_no);
+        if (!ins.second) throw std::runtime_error(what + "the same clade as line " + std::to_string(ins.first->second));
+        a.place_nodes.push_back((uint32_t)v);
+    }
+    if (a.place_nodes.empty()) throw std::runtime_error("--place-clades-only " + a.place_clades_only + ": the list of clades is empty");
+}
+
+// --place-clades: one qs_clade_placement over the counted (or loaded) table for the listed nodes, their link sums downloaded, per clade
+// qs_placement_scores and the columns (tests/clade_placement_model.py defines them): a position = the edges outside the clade that
+// induce the same bipartition of the taxa outside it
+void write_place_clades(qs_ctx *ctx, const RefFlat &ref, int device, const std::string &path, const std::vector<uint32_t> &nodes) {
+    const size_t n = ref.names.size(), N = ref.parent.size(), L = nodes.size();
+    const qs_ref_tree rt = ref_view(ref);
+    qs::DevBuf<int64_t> dev;
+    if (hipSetDevice(device) != hipSuccess || dev.reserve(L * 2 * N * 8, nullptr) != hipSuccess) throw std::runtime_error("--place-clades: Insufficient memory!");
+    if (qs_clade_placement(ctx, &rt, nodes.data(), (uint32_t)L, dev.get()) != QS_OK || qs_sync(ctx) != QS_OK)
+        throw std::runtime_error(std::string("--place-clades: ") + qs_last_error(ctx));
+    std::vector<int64_t> w(L * 2 * N);
+    if (hipMemcpy(w.data(), dev.get(), w.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("--place-clades: download failed");
+    const PlaceShape S(ref, "--place-clades");
+    auto walk = [&](size_t a, size_t b) {   // nodes on the path from a to b, both inclusive
+        std::vector<size_t> left{a}, right{b};
+        while (left.back() != right.back()) {
+            if (S.depth[left.back()] >= S.depth[right.back()]) left.push_back((size_t)ref.parent[left.back()]);
+            else right.push_back((size_t)ref.parent[right.back()]);
+        }
+        left.insert(left.end(), right.rbegin() + 1, right.rend());
+        return left;
+    };
+    std::ofstream f(path);
+    if (!f) throw std::runtime_error("cannot write " + path);
+    f << "clade\tnode\tlo\thi\tsize\tcurrent\tbest\tgain\tn_best\tbest_node\tbest_lo\tbest_hi\tdistance\n";
+    std::vector<int64_t> score(N), key(N);
+    std::vector<uint8_t> edge(N);
+    for (size_t k = 0; k < L; ++k) {
+        const size_t c = nodes[k];
+        const int64_t cl = S.lo[c], ch = S.hi[c], size = ch - cl;
+        if (qs_placement_scores(&rt, &w[k * 2 * N], score.data()) != QS_OK) throw std::runtime_error(std::string("--place-clades: ") + qs_last_error(nullptr));
+        // the edges outside the clade and its own; the position of the edge above v: the id interval, in the numbering of the taxa
+        // outside the clade, of the side without the smallest of them
+        for (size_t v = 0; v < N; ++v) {
+            edge[v] = v != S.root && !(v != c && S.lo[v] >= cl && S.hi[v] <= ch);
+            int64_t a = S.lo[v] - (S.lo[v] >= ch ? size : 0), b = S.hi[v] - (S.hi[v] >= ch ? size : 0);
+            if (a == 0 && b > 0) { a = b; b = (int64_t)n - size; }
+            key[v] = b > a ? a * (int64_t)n + b : 0;
+        }
+        const size_t u = (size_t)ref.parent[c];
+        if (S.links[u] == 3)   // the clade's own edge and the two other edges at its parent are one position
+            for (size_t v = 0; v < N; ++v) if (v != c && ref.parent[v] == (int32_t)u) { key[c] = key[v]; break; }
+        int64_t best = INT64_MIN;
+        for (size_t v = 0; v < N; ++v) if (edge[v]) best = std::max(best, score[v]);
+        std::set<int64_t> top;
+        int64_t first_top = -1;
+        for (size_t v = 0; v < N; ++v) if (edge[v] && score[v] == best) { if (top.empty()) first_top = key[v]; top.insert(key[v]); }
+        const int64_t current = score[c];
+        const int64_t pick = current == best ? key[c] : first_top;
+        size_t node = 0;
+        for (size_t v = 0; v < N; ++v) if (edge[v] && key[v] == pick) { node = v; break; }
+        size_t dist = 0;
+        if (pick != key[c]) {
+            const std::vector<size_t> to_child = walk(u, node), to_parent = walk(u, (size_t)ref.parent[node]);
+            for (size_t v : to_parent.size() < to_child.size() ? to_parent : to_child) dist += S.links[v] - (v == u) >= 3;
+        }
+        f << k << '\t' << c << '\t' << cl << '\t' << ch << '\t' << size << '\t' << current << '\t' << best << '\t' << (best - current) << '\t' << top.size()
+          << '\t' << node << '\t' << S.lo[node] << '\t' << S.hi[node] << '\t' << dist << '\n';
     }
     if (!f) throw std::runtime_error("cannot write " + path);
 }
@@ -710,6 +865,7 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
     if (!a.per_tree.empty()) per_tree.write(a.per_tree);
     if (!a.per_taxon.empty()) write_per_taxon(qsc.context(), qsc.reference(), a.dev.device, a.per_taxon);
     if (!a.place_taxa.empty()) write_place_taxa(qsc.context(), qsc.reference(), a.dev.device, a.place_taxa, a.place_ids);
+    if (!a.place_clades.empty()) write_place_clades(qsc.context(), qsc.reference(), a.dev.device, a.place_clades, a.place_nodes);
     if (!a.also.empty() || !a.without.empty()) {   // the primary tree's output first, exactly as without --also-ref / --without-taxa
         write_annotated(referenceTree, a.out, lqic, qpic, eqpic);
         score_also_refs(a, qsc.context(), qsc.reference(), also_table);
@@ -739,6 +895,7 @@ int main(int argc, char *argv[]) {
         check_per_tree(a);
         check_per_taxon(a);
         check_place_taxa(a);
+        check_place_clades(a);
     } catch (const std::exception &e) {
         std::cerr << "ERROR: " << e.what() << std::endl;
         return 1;

@@ -157,6 +157,10 @@ struct qs_ctx {
     std::vector<uint32_t> place_tasks;
     DevBuf<uint16_t> place_child_dev, place_next_dev, place_taxa_dev;
     DevBuf<uint32_t> place_node_dev, place_tasks_dev;
+    // qs_clade_placement: the walks in the numbering of the ids outside a clade (one list for every clade size) and the last call's
+    // clades and workgroups, kept like the lists above
+    std::vector<uint32_t> clade_tasks, clade_list;
+    DevBuf<uint32_t> clade_tasks_dev, clade_list_dev;
 };
 
 static thread_local std::string g_create_err;   // per thread: qs_create of several contexts may run concurrently (multi_gpu.hpp)
@@ -2210,6 +2214,103 @@ extern "C" int qs_taxon_placement(qs_ctx *c, const qs_ref_tree *ref, const uint1
     // (qs_create's cap today; the LDS limit alone would allow more)
     const bool wide = max_count >= (1ull << 32) / 4096 || c->n > 4096;
     QS_HIP(c, launch_taxon_placement(c->stream, pd, n_list, wide, c->n_cu, reinterpret_cast<unsigned long long *>(dst_device)));
+    return QS_OK;   // asynchronous on the context's stream
+}
+
+// Link sums of the quartet placement of the listed clades (qs_place_clade.hip): the clade below a node is pruned and regrafted, unchanged
+// inside, on every edge outside it. The reference never asks where the evaluation trees would put a subtree: this replaces nothing there.
+extern "C" int qs_clade_placement(qs_ctx *c, const qs_ref_tree *ref, const uint32_t *nodes, uint32_t n_list, int64_t *dst_device) {
+    if (!c) return QS_ERR_ARG;
+    if (!dst_device) return fail(c, QS_ERR_ARG, "qs_clade_placement: NULL argument");
+    if (reinterpret_cast<uintptr_t>(dst_device) % 8) return fail(c, QS_ERR_ARG, "qs_clade_placement: dst_device is not 8-byte aligned");
+    if (!c->table) return fail(c, QS_ERR_STATE, "qs_clade_placement: no table");
+    if (!nodes || n_list == 0) return fail(c, QS_ERR_ARG, "qs_clade_placement: the list needs at least one node");
+    // the list against the tree's shape, before anything touches the device
+    const uint32_t n = c->n;
+    std::vector<uint32_t> lo(n_list), hi(n_list);
+    {
+        RefHost S;
+        if (int rc = build_ref_shape(c, ref, S)) return rc;
+        std::vector<uint8_t> seen(S.n_nodes, 0);
+        for (uint32_t i = 0; i < n_list; ++i) {
+            const uint32_t v = nodes[i];
+            if (v >= S.n_nodes) return fail(c, QS_ERR_ARG, "qs_clade_placement: node index out of range");
+            if (v == S.root) return fail(c, QS_ERR_ARG, "qs_clade_placement: the root is not a clade to move");
+            if (seen[v]) return fail(c, QS_ERR_ARG, "qs_clade_placement: node " + std::to_string(v) + " is listed twice");
+            seen[v] = 1;
+            lo[i] = S.leaf_lo[v]; hi[i] = lo[i] + S.leaf_cnt[v];
+            if (n - S.leaf_cnt[v] < 3) return fail(c, QS_ERR_ARG, "qs_clade_placement: node " + std::to_string(v) + " leaves fewer than three taxa outside it");
+        }
+    }
+    // every sum is at most |C| x C(n-|C|,3) x (largest count): the trees behind the table if known, else what a cell can hold (as qs_taxon_support)
+    const uint64_t cell_max = c->count_bits == 16 ? 0xFFFFull : 0xFFFFFFFFull;
+    const uint64_t trees = std::max(c->trees_counted, c->table_trees_hint);
+    const uint64_t max_count = trees ? std::min(trees, cell_max) : cell_max;
+    std::vector<uint64_t> cost(n_list);
+    for (uint32_t i = 0; i < n_list; ++i) {
+        const uint64_t s = hi[i] - lo[i], o = n - s;
+        cost[i] = s * (o * (o - 1) / 2 * (o - 2) / 3);        // (n <= 65535: below 2^62)
+        if (max_count > (uint64_t)INT64_MAX / cost[i])
+            return fail(c, QS_ERR_OVERFLOW, "qs_clade_placement: |C| x C(n-|C|,3) x the largest possible count exceeds 63 bits for node " + std::to_string(nodes[i]));
+    }
+    if (c->d_lo != 0 || c->d_hi != c->n) return fail(c, QS_ERR_UNSUPPORTED, "qs_clade_placement: a table-shard context (the walks of a clade cross every shard: use a whole-table one)");
+    if (place_lds_bytes(ref->n_nodes) > 160u * 1024u)
+        return fail(c, QS_ERR_UNSUPPORTED, "qs_clade_placement: more than 10240 nodes (the link sums of a workgroup live in LDS)");
+    QS_HIP(c, hipSetDevice(c->device));
+    const RefHost *Rp = nullptr;
+    if (int rc = get_ref(c, ref, true, &Rp)) return rc;
+    if (int rc = ensure_place_ref(c, *Rp)) return rc;
+    if (c->n_cu == 0) { int v = 0; QS_HIP(c, hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device)); c->n_cu = std::max(1, v); }
+    if (!c->clade_tasks_dev) {
+        // a walk = (middle id, 64 consecutive largest ids) among the ids outside a clade, named by d = the outside ids above the middle
+        // one: a clade with `o` taxa outside owns the entries with d <= o - 2, and the smallest d are its longest walks
+        c->clade_tasks.clear();
+        for (uint32_t d = 1; d + 2 <= n; ++d)
+            for (uint32_t g = 0; g * kWave < d; ++g) c->clade_tasks.push_back(d | g << 16);
+        QS_HIP(c, c->clade_tasks_dev.reserve(std::max<size_t>(c->clade_tasks.size(), 1) * 4, nullptr));
+        QS_HIP(c, hipMemcpyAsync(c->clade_tasks_dev.get(), c->clade_tasks.data(), c->clade_tasks.size() * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    // per clade: its x-slices and its share of about eight workgroups per CU, in proportion to its tuples
+    // 32-bit register sums: a walk has at most n - |C| - 2 steps of `slice` tuples each, so (n - |C|) x slice x (largest count) < 2^32
+    // keeps them exact; slices are shortened to stay below, and the 64-bit instance takes over where that would cut a clade
+    // into slices of fewer than 16 taxa
+    bool wide = false;
+    for (uint32_t i = 0; i < n_list && !wide; ++i) {
+        const uint64_t s = hi[i] - lo[i], cap = 0xFFFFFFFFull / (max_count * (n - s));
+        wide = cap < std::min<uint64_t>(s, 16);
+    }
+    long double total_cost = 0;
+    for (uint64_t v : cost) total_cost += (long double)v;
+    const uint32_t budget = (uint32_t)c->n_cu * 8u;
+    std::vector<uint32_t> list((size_t)n_list * 4), groups;
+    for (uint32_t i = 0; i < n_list; ++i) {
+        const uint32_t s = hi[i] - lo[i], o = n - s;
+        uint64_t walks = 0;
+        for (uint32_t d = 1; d + 2 <= o; ++d) walks += (d + kWave - 1) / kWave;
+        uint32_t share = (uint32_t)std::min<long double>(65535.0L, std::max<long double>(1.0L, (long double)budget * (long double)cost[i] / total_cost + 0.5L));
+        // about four items per wave of the share, from slices of at least 16 taxa
+        uint64_t n_slices = std::max<uint64_t>(1, std::min<uint64_t>(s / 16, ((uint64_t)share * kPlaceWaves * 4 + walks - 1) / walks));
+        uint32_t slice = (uint32_t)((s + n_slices - 1) / n_slices);
+        if (!wide) slice = (uint32_t)std::min<uint64_t>(slice, 0xFFFFFFFFull / (max_count * o));
+        n_slices = (s + slice - 1) / slice;
+        share = (uint32_t)std::min<uint64_t>(share, (walks * n_slices + kPlaceWaves - 1) / kPlaceWaves);
+        list[4 * (size_t)i] = lo[i]; list[4 * (size_t)i + 1] = hi[i]; list[4 * (size_t)i + 2] = slice; list[4 * (size_t)i + 3] = (uint32_t)walks;
+        for (uint32_t k = 0; k < share; ++k) { groups.push_back(i); groups.push_back(k | share << 16); }
+    }
+    const uint32_t n_groups = (uint32_t)(groups.size() / 2);
+    list.insert(list.end(), groups.begin(), groups.end());
+    QS_HIP(c, hipStreamSynchronize(c->stream));   // (an earlier call's kernel and upload may still read the old lists)
+    c->clade_list = std::move(list);
+    QS_HIP(c, c->clade_list_dev.reserve(c->clade_list.size() * 4, nullptr));
+    QS_HIP(c, hipMemcpyAsync(c->clade_list_dev.get(), c->clade_list.data(), c->clade_list.size() * 4, hipMemcpyHostToDevice, c->stream));
+    CladeDevice cd;
+    cd.ref_lca = c->ref_lca_dev.get(); cd.inner_node = c->place_node_dev.get(); cd.tasks = c->clade_tasks_dev.get();
+    cd.clades = c->clade_list_dev.get(); cd.groups = cd.clades + (size_t)n_list * 4;
+    cd.child = c->place_child_dev.get(); cd.next = c->place_next_dev.get();
+    cd.n = c->n; cd.n_nodes = Rp->n_nodes;
+    cd.table = c->table; cd.count_bits = (int)c->count_bits;   // the context's own table, not a scoring view
+    QS_HIP(c, hipMemsetAsync(dst_device, 0, (size_t)n_list * 2 * Rp->n_nodes * 8, c->stream));
+    QS_HIP(c, launch_clade_placement(c->stream, cd, n_groups, wide, reinterpret_cast<unsigned long long *>(dst_device)));
     return QS_OK;   // asynchronous on the context's stream
 }
 

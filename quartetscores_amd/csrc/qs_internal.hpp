@@ -166,6 +166,20 @@ struct PlaceDevice {
 constexpr int kPlaceWaves = 4;
 size_t place_lds_bytes(uint32_t n_nodes);
 hipError_t launch_taxon_placement(hipStream_t s, const PlaceDevice &pd, uint32_t n_list, bool wide, int n_cu, unsigned long long *dst);
+// qs_place_clade.hip: link sums of the quartet placement of listed clades (qs_clade_placement); whole tables only. ref_lca, inner_node,
+// child, next as in PlaceDevice. tasks = d | group of 64 largest ids << 16 by d ascending, in the numbering of the ids OUTSIDE a clade:
+// the walk of the middle id n_outside - 1 - d (d = 1 ..: the longest walks first), so that the first clades[4 i + 3] entries are the walks
+// of clade i whatever its size. clades = per listed clade lo, hi, x-slice length, walks. groups = per workgroup the clade's list index
+// and (its number among the clade's workgroups | their count << 16). dst = one row of 2 x n_nodes words per clade, zeroed beforehand;
+// wide: (n - |C|) x slice x (largest count) may reach 2^32
+struct CladeDevice {
+    const uint32_t *ref_lca, *inner_node, *tasks, *clades, *groups;
+    const uint16_t *child, *next;
+    uint32_t n, n_nodes;
+    const void *table;
+    int count_bits;
+};
+hipError_t launch_clade_placement(hipStream_t s, const CladeDevice &cd, uint32_t n_groups, bool wide, unsigned long long *dst);
 size_t gather_lds_bytes(uint32_t d_hi);
 uint32_t gather_tiles_for_c(uint32_t c); // workgroups of the gather kernel per (d-block, c)
 

@@ -99,14 +99,8 @@ def placement_scores(ref: flatten.RefTree, links) -> np.ndarray:
     return out
 
 
-def placement_columns(ref: flatten.RefTree, taxa, scores) -> dict:
-    """The columns of QuartetScores --place-taxa (PLACEMENT_COLUMNS) for the listed taxa (lookup ids) and their rows of
-    placement_scores. A position = the edges that induce the same bipartition of the OTHER taxa (the taxon's own pendant edge
-    belongs to the position of the two other edges at a parent with three links). current = the score at the taxon's own edge,
-    best = the largest score, n_best = positions that attain it; the reported position is the current one if it attains best,
-    else the one that holds the smallest node index; best_node = its smallest node index, [best_lo, best_hi) the lookup ids
-    below that node; distance = 0 for the current position, else the nodes on the path from the taxon's parent to the nearer end
-    of the edge above best_node that keep three links without the taxon (1 = an NNI neighbour)."""
+def _tree_arrays(ref: flatten.RefTree):
+    """parent, depth, leaf interval [lo, hi) and links (children + parent edge) of every node; the root's index"""
     parent = np.asarray(ref.parent, dtype=np.int64)
     N, n = len(parent), ref.n_taxa
     root = int(np.nonzero(parent < 0)[0][0])
@@ -121,6 +115,20 @@ def placement_columns(ref: flatten.RefTree, taxa, scores) -> dict:
         p = x.parent.index
         lo[p], hi[p] = min(lo[p], lo[x.index]), max(hi[p], hi[x.index])
     links = np.bincount(parent[parent >= 0], minlength=N) + (parent >= 0)
+    return parent, depth, lo, hi, links, root
+
+
+def placement_columns(ref: flatten.RefTree, taxa, scores) -> dict:
+    """The columns of QuartetScores --place-taxa (PLACEMENT_COLUMNS) for the listed taxa (lookup ids) and their rows of
+    placement_scores. A position = the edges that induce the same bipartition of the OTHER taxa (the taxon's own pendant edge
+    belongs to the position of the two other edges at a parent with three links). current = the score at the taxon's own edge,
+    best = the largest score, n_best = positions that attain it; the reported position is the current one if it attains best,
+    else the one that holds the smallest node index; best_node = its smallest node index, [best_lo, best_hi) the lookup ids
+    below that node; distance = 0 for the current position, else the nodes on the path from the taxon's parent to the nearer end
+    of the edge above best_node that keep three links without the taxon (1 = an NNI neighbour)."""
+    parent, depth, lo, hi, links, root = _tree_arrays(ref)
+    N, n = len(parent), ref.n_taxa
+    leaf_node = np.asarray(ref.leaf_node, dtype=np.int64)
     edges = np.arange(N) != root
     sc = np.asarray(scores, dtype=np.int64).reshape(len(taxa), N)
 
@@ -156,6 +164,65 @@ def placement_columns(ref: flatten.RefTree, taxa, scores) -> dict:
         for name, val in zip(PLACEMENT_COLUMNS, vals):
             out[name].append(val)
     return {k: (v if k == "name" else np.array(v, dtype=np.int64)) for k, v in out.items()}
+
+
+CLADE_PLACEMENT_COLUMNS = ("clade", "node", "lo", "hi", "size", "current", "best", "gain", "n_best", "best_node", "best_lo", "best_hi", "distance")
+
+
+def eligible_clades(ref: flatten.RefTree) -> np.ndarray:
+    """The default list of Context.clade_placement and --place-clades: the inner non-root nodes of `ref` with at least three
+    taxa outside them, in node order."""
+    parent, _, lo, hi, links, root = _tree_arrays(ref)
+    inner = np.bincount(parent[parent >= 0], minlength=len(parent)) > 0
+    return np.nonzero(inner & (np.arange(len(parent)) != root) & (ref.n_taxa - (hi - lo) >= 3))[0].astype(np.int64)
+
+
+def clade_placement_columns(ref: flatten.RefTree, nodes, scores) -> dict:
+    """The columns of QuartetScores --place-clades (CLADE_PLACEMENT_COLUMNS) for the listed nodes and their rows of
+    placement_scores over Context.clade_placement. clade = the list index, [lo, hi) the clade's lookup ids. A position = the
+    edges OUTSIDE the clade that induce the same bipartition of the taxa outside it; the clade's own edge belongs to the position
+    of the two other edges at a parent with three links (under a multifurcation it is a position of its own: the score at the
+    node). The remaining columns as placement_columns defines them with the clade in the taxon's place: distance = 0 for the
+    current position, else the nodes on the path from the clade's parent to the nearer end of the edge above best_node that keep
+    three links without the clade (1 = an NNI of the clade)."""
+    parent, depth, lo, hi, links, root = _tree_arrays(ref)
+    N, n = len(parent), ref.n_taxa
+    sc = np.asarray(scores, dtype=np.int64).reshape(len(nodes), N)
+
+    def walk(a, b):
+        left, right = [a], [b]
+        while left[-1] != right[-1]:
+            if depth[left[-1]] >= depth[right[-1]]:
+                left.append(int(parent[left[-1]]))
+            else:
+                right.append(int(parent[right[-1]]))
+        return left + right[-2::-1]
+
+    out = {name: [] for name in CLADE_PLACEMENT_COLUMNS}
+    for k, (row, c) in enumerate(zip(sc, nodes)):
+        c = int(c)
+        cl, ch = int(lo[c]), int(hi[c])
+        size = ch - cl
+        edges = (np.arange(N) != root) & ~((lo >= cl) & (hi <= ch) & (np.arange(N) != c))   # outside the clade, and its own edge
+        a, b = lo - np.where(lo >= ch, size, 0), hi - np.where(hi >= ch, size, 0)            # in the numbering of the taxa outside
+        flip = (a == 0) & (b > 0)
+        a, b = np.where(flip, b, a), np.where(flip, n - size, b)
+        key = np.where(b > a, a * n + b, 0)            # the side without the smallest outside taxon; 0 = all of them on one side
+        u = int(parent[c])                             # (the clade's own edge has key 0 so far: nothing outside below it)
+        if links[u] == 3:
+            key[c] = key[[w for w in np.nonzero(parent == u)[0] if w != c][0]]
+        current, best = int(row[c]), int(row[edges].max())
+        top = edges & (row == best)
+        pick = key[c] if current == best else key[np.nonzero(top)[0][0]]
+        node = int(np.nonzero(edges & (key == pick))[0][0])
+        dist = 0
+        if pick != key[c]:
+            near = min((walk(u, node), walk(u, int(parent[node]))), key=len)
+            dist = sum(1 for w in near if links[w] - (w == u) >= 3)
+        vals = (k, c, cl, ch, size, current, best, best - current, len(np.unique(key[top])), node, int(lo[node]), int(hi[node]), dist)
+        for name, val in zip(CLADE_PLACEMENT_COLUMNS, vals):
+            out[name].append(val)
+    return {k: np.array(v, dtype=np.int64) for k, v in out.items()}
 
 
 class Context:
@@ -323,6 +390,26 @@ class Context:
         self.sync()
         del keep
         return buf[: n_list * width].cpu().numpy().reshape(n_list, width)
+
+    def clade_placement(self, ref: flatten.RefTree, nodes=None) -> np.ndarray:
+        """qs_clade_placement: per listed non-root node of `ref` (None = eligible_clades(ref)) the 2 * n_nodes link sums W_C of the
+        quartet placement of the clade below it, pruned and regrafted unchanged inside, from this context's whole table -> int64
+        (n_list, 2 * n_nodes); placement_scores turns a row into the score of every edge outside the clade (the entries of the
+        nodes strictly inside it are not positions, the node's own entry is the current position's score),
+        clade_placement_columns into the CLI's columns. Allocates the device buffer, waits for the result and downloads it."""
+        import torch
+        wide = np.asarray(eligible_clades(ref) if nodes is None else nodes, dtype=np.int64).reshape(-1)
+        if ((wide < 0) | (wide >= ref.n_nodes)).any():    # (before the cast to the ABI's unsigned indices, which would wrap)
+            raise QSError(_lib.QS_ERR_ARG, "clade_placement: node index out of range")
+        ids = np.ascontiguousarray(wide, dtype=np.uint32)
+        width = 2 * ref.n_nodes
+        buf = torch.empty(max(1, len(ids) * width), dtype=torch.int64, device=f"cuda:{self.device}")
+        s, keep = self._ref_struct(ref)
+        self._chk(self.L.qs_clade_placement(self.h, C.byref(s), ids.ctypes.data_as(C.c_void_p) if len(ids) else None, len(ids),
+                                            C.c_void_p(buf.data_ptr())))
+        self.sync()
+        del keep
+        return buf[: len(ids) * width].cpu().numpy().reshape(len(ids), width)
 
     def table_clear(self):
         self._chk(self.L.qs_table_clear(self.h))
