@@ -212,6 +212,13 @@ const char *qs_last_error(const qs_ctx *ctx); /* ctx may be NULL: message of the
                                        * kernel -- one pass over the table whatever the mix of tree shapes, like the reference's shape-independent loop
                                        * (QuartetCounterLookup.hpp:65-106,166-188); no mode joins a dearer one any more. 0: one launch per class (round 5).
                                        * Read by qs_batch_upload (class plan) and qs_count_batch (launches). */
+#define QS_TUNE_FIX_OVERLAP 19u       /* 1 (default): a slice of the count step whose trees carry depth-clamp corrections is counted in TWO launches, split at
+                                       * a largest id d_mid (qs_fix_overlap_plan): the corrections of [d_mid, d_hi) run on a second stream beside the count
+                                       * launch of [d_lo, d_mid), which is a few per cent of the work. 0: one count launch, then the corrections. Same table. */
+#define QS_TUNE_FIX_SPLIT_AT 20u      /* tests: the d_mid of every split slice, d_lo < value < d_hi (no plan, no minimum size); 0 (default) = planned.
+                                       * The forced value also bypasses the planner's word alignment for 16-bit cells: the last cell of the lower
+                                       * range and the first of the upper may then share a 32-bit word, which a halfword store and an atomic on the
+                                       * other half reach at the same time (distinct cells; both are resolved in the L2). Not for production use. */
 #define QS_TUNE_CLASS_MIN_TREES 16u   /* ... and the absolute floor of a class (default 1024 trees; tests lower it to split small batches) */
 #define QS_TUNE_SCORE_LOAD 14u        /* bundle score kernel, shape of the table loads: 0 (default) = every lane loads its own row in 16-byte pieces;
                                        * 2 = ... and requests the next chunk before it processes the current one; 1 = eight lanes load the
@@ -510,8 +517,21 @@ int qs_last_count_launches(const qs_ctx *ctx);
 /* ... and the share of [1] spent in the depth-clamp correction kernels (QS_TUNE_DEPTH_CLAMP; 0 without clamped trees). */
 float qs_last_count_fix_ms(qs_ctx *ctx);
 /* ... and every kernel of that call in launch order: ms[k] = its duration, kind[k] = 0 panel build, 1 count kernel, 2 depth-clamp
- * corrections; returns the number of kernels written (at most cap). */
+ * corrections (those of a split slice's upper range are timed from the end of the upper count launch on their own stream, its lower count
+ * launch from the same point: the two overlap; the set-up of a new split -- two filter kernels and two small copies, once per context
+ * and d_mid -- and the wait for the correction stream are no kernels of the step and are left out here and in qs_last_count_ms [0], [1]); returns the number of kernels written (at most cap). */
 int qs_last_count_events(qs_ctx *ctx, float *ms, uint8_t *kind, int cap);
+/* Largest id at which the last slice with corrections of the most recent qs_count_batch was split (QS_TUNE_FIX_OVERLAP; its variant
+ * string ends in /overlap:<d_mid> then), 0 = every slice was one count launch; n_slices (may be NULL) = how many slices were split. */
+int qs_last_count_split(const qs_ctx *ctx, uint32_t *n_slices);
+/* Host-only: the split QS_TUNE_FIX_OVERLAP makes for a slice of n_groups 32-tree groups of a class (kernel mode, depth bits) with
+ * `corrections` (tree, quartet) corrections over all C(n_taxa,4) tuples, on the shard [d_lo, d_hi) with count_bits cells: the smallest
+ * d_mid, d-blocks of 8 aligned to d_hi (16-bit cells: moved up by 4 where the upper range would not start at a 32-bit word), whose
+ * lower count launch is modelled to outlast the upper range's corrections by half. keep = a d_mid already in use, which stays if it
+ * still fits (0 = none). Returns d_mid, 0 = one launch (no corrections, a short range, a lower launch below one wave population of
+ * tiles or above 40 % of the count), < 0 = QS_ERR_ARG. model_ms (may be NULL): [0] lower count launch, [1] upper corrections. */
+int qs_fix_overlap_plan(uint32_t n_taxa, uint32_t d_lo, uint32_t d_hi, uint32_t count_bits, uint32_t mode, uint32_t depth_bits,
+                        uint32_t n_groups, uint64_t corrections, uint32_t keep, double *model_ms);
 /* Depth clamp of an uploaded batch: out[0] = trees counted in a class below their own depth bits, out[1] = the (tree, quartet)
  * corrections they cost, out[2] = workgroups of the correction kernel. */
 int qs_batch_clamp_info(const qs_device_batch *batch, uint64_t out[3]);

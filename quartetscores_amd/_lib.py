@@ -24,6 +24,7 @@ QS_TUNE_PANEL_SLICE_BYTES, QS_TUNE_GATHER_IMPL, QS_TUNE_PANEL_KERNEL, QS_TUNE_TI
 QS_TUNE_SCORE_CAND_SLOTS, QS_TUNE_SCORE_TOL_EXP, QS_TUNE_SCORE_KERNEL, QS_TUNE_TABLE_TREES, QS_TUNE_COOP, QS_TUNE_SCORE_PASSES, QS_TUNE_SCORE_LOG_CAP, QS_TUNE_SCORE_SAMPLE, QS_TUNE_SCORE_DEDUPE, QS_TUNE_SCORE_LOAD, QS_TUNE_CLASS_PCT, QS_TUNE_CLASS_MIN_TREES = 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16
 QS_TUNE_DEPTH_CLAMP = 17
 QS_TUNE_FUSE_CLASSES = 18
+QS_TUNE_FIX_OVERLAP, QS_TUNE_FIX_SPLIT_AT = 19, 20
 QS_CLASS_PLAN_FUSED = 0x100
 QS_IMPL_AUTO, QS_IMPL_SWAR, QS_IMPL_BITSLICE = 0, 1, 2
 QS_SHARDS_BY_TUPLES, QS_SHARDS_BY_COST = 0, 1
@@ -38,6 +39,7 @@ EXPORTS = [
     "qs_score_plan", "qs_last_score_ms", "qs_prepare", "qs_table_pack32x2", "qs_unpack32x2", "qs_last_score_log", "qs_last_score_estimate", "qs_score_prepare",
     "qs_sum_words", "qs_issue_probe", "qs_last_count_fix_ms", "qs_batch_clamp_info", "qs_depth_clamp_plan", "qs_score_check", "qs_last_count_events", "qs_class_plan", "qs_shard_bounds",
     "qs_table_remap", "qs_tree_agreement", "qs_taxon_support", "qs_table_restrict", "qs_taxon_placement", "qs_placement_scores", "qs_clade_placement",
+    "qs_last_count_split", "qs_fix_overlap_plan",
 ]
 
 
@@ -199,5 +201,9 @@ def load():
     L.qs_score_check.argtypes = [vp, C.POINTER(RefTreeC), u32]
     L.qs_depth_clamp_plan.restype = i32
     L.qs_depth_clamp_plan.argtypes = [u32, C.POINTER(TreeBatchC), u32, vp, vp, vp]
+    L.qs_last_count_split.restype = i32
+    L.qs_last_count_split.argtypes = [vp, vp]
+    L.qs_fix_overlap_plan.restype = i32
+    L.qs_fix_overlap_plan.argtypes = [u32, u32, u32, u32, u32, u32, u32, u64, u32, vp]
     _lib = L
     return L

@@ -29,6 +29,7 @@ struct EarlyPerm { std::vector<uint32_t> perm; uint32_t chunk = 0, cblock_in = 0
 struct qs_device_batch {
     DeviceBatch d;
     std::vector<uint32_t> fix_slot;   // depth clamp: slot (in the class-ordered batch) of the tree behind every correction unit, ascending
+    std::vector<uint64_t> fix_work;   // n_fix + 1 prefix sums: triples x fourth leaves of every unit (what the split of a slice is planned from)
 };
 
 // the reference tree, flattened and indexed for scoring (build_ref)
@@ -83,9 +84,27 @@ struct qs_ctx {
     DevBuf<void> panel;
     DevBuf<uint32_t> dev_flags; // [0] counter overflow, [1] score flags, [3] two-cell wire format: tuple sum mismatch
     std::vector<hipEvent_t> evs;   // QS_COUNT_TIMED: evs[0] = start, then one event after every kernel launch
-    std::vector<uint8_t> ev_kind;  // per event after evs[0]: 0 = panel build, 1 = count kernel, 2 = depth-clamp corrections (clamp_fix_kernel)
+    std::vector<uint8_t> ev_kind;  // per event after evs[0]: 0 = panel build, 1 = count kernel, 2 = depth-clamp corrections (clamp_fix_kernel),
+                                   // 3 = no kernel of the step (the wait for the correction stream, the set-up of a new split), 4 = second count launch of a split slice
+    std::vector<uint32_t> ev_from; // ... and the event its interval starts at (the one before it, unless a split slice says otherwise)
     uint32_t ev_used = 0;
     bool last_timed = false;
+    // Split slices (run_launch): the corrections of the upper d-range run on fix_stream beside the count launch of the lower one.
+    // split = the tilings of the two ranges for the d_mid they were last built for (launch orders: built with the first split launch).
+    DevStream fix_stream;
+    DevEvent fix_go, fix_done;     // fix_go: the upper range is stored (main stream); fix_done: its corrections are in (correction stream)
+    struct Split {
+        uint32_t d_mid = 0;                  // 0 = none built
+        const uint32_t *perm_of = nullptr;   // the full launch order the two below were cut from (NULL: identity order, none needed)
+        uint32_t n_dblk_hi = 0, tiles_hi = 0, n_dblk_lo = 0, tiles_lo = 0;
+        DevBuf<uint32_t> dprefix_lo, perm_hi, perm_lo, filter_scratch;
+        std::vector<uint32_t> h_dp_lo, h_perm_lo;
+        DevEvent copied;                     // behind the copies out of the two host lists
+        bool copied_valid = false;
+    } split;
+    uint32_t tune_fix_overlap = 1;           // QS_TUNE_FIX_OVERLAP
+    uint32_t tune_fix_split_at = 0;          // QS_TUNE_FIX_SPLIT_AT (tests): d_mid of every split, 0 = planned
+    uint32_t last_split = 0, last_splits = 0; // qs_last_count_split: d_mid of the last split slice of the last count, and how many there were
     // qs_set_tuning
     uint64_t tune_slice_bytes = 0; // 0 = automatic
     uint32_t tune_gather_impl = 0; // QS_IMPL_*
@@ -199,15 +218,19 @@ static uint32_t slice_groups(const qs_ctx *c, size_t group_bytes, uint32_t n_tot
 }
 
 // QS_COUNT_TIMED: an event after every kernel launch of the call (created on demand, re-used by later calls)
-static hipError_t mark(qs_ctx *c, int kind) {
+// The event goes onto the stream its kernel ran on (`on`; NULL pointer = the context's stream). Its interval starts at event
+// `from` (index into evs), by default the event recorded before it.
+constexpr uint32_t kEvPrev = ~0u;
+static hipError_t mark(qs_ctx *c, int kind, const hipStream_t *on = nullptr, uint32_t from = kEvPrev) {
     if (c->ev_used == c->evs.size()) {
         hipEvent_t e;
         hipError_t rc = hipEventCreate(&e);
         if (rc != hipSuccess) return rc;
-        c->evs.push_back(e); c->ev_kind.push_back(0);
+        c->evs.push_back(e); c->ev_kind.push_back(0); c->ev_from.push_back(0);
     }
     c->ev_kind[c->ev_used] = (uint8_t)kind;
-    return hipEventRecord(c->evs[c->ev_used++], c->stream);
+    c->ev_from[c->ev_used] = from != kEvPrev ? from : (c->ev_used ? c->ev_used - 1 : 0);
+    return hipEventRecord(c->evs[c->ev_used++], on ? *on : c->stream);
 }
 
 static int fail(qs_ctx *c, int code, const std::string &msg) {
@@ -395,6 +418,7 @@ static int drop_tile_order(qs_ctx *c) {
     QS_HIP(c, hipStreamSynchronize(c->stream));
     c->perm.reset(); c->perm_coop.reset(); c->perm_rest.reset();
     c->perm_built = false; c->n_coop = c->n_rest = 0;
+    c->split.d_mid = 0;   // (cut from the order just dropped)
     return QS_OK;
 }
 
@@ -425,6 +449,10 @@ extern "C" int qs_set_tuning(qs_ctx *c, uint32_t key, uint64_t value) {
         case QS_TUNE_CLASS_MIN_TREES: c->tune_class_min = (uint32_t)std::min<uint64_t>(value, 0xFFFFFFFFull); return QS_OK;
         case QS_TUNE_DEPTH_CLAMP: c->tune_clamp_ppm = (uint32_t)std::min<uint64_t>(value, 1000000ull); return QS_OK;
         case QS_TUNE_FUSE_CLASSES: c->tune_fuse = value ? 1u : 0u; return QS_OK;
+        case QS_TUNE_FIX_OVERLAP: c->tune_fix_overlap = value ? 1u : 0u; return QS_OK;
+        case QS_TUNE_FIX_SPLIT_AT:
+            if (value > c->n) return fail(c, QS_ERR_ARG, "qs_set_tuning: QS_TUNE_FIX_SPLIT_AT takes 0 (planned) or a largest id up to n_taxa");
+            c->tune_fix_split_at = (uint32_t)value; return QS_OK;
         case QS_TUNE_CLASS_PCT: if (value > 100) return fail(c, QS_ERR_ARG, "qs_set_tuning: QS_TUNE_CLASS_PCT takes 0 .. 100"); c->tune_class_pct = (uint32_t)value; return QS_OK;
         case QS_TUNE_SCORE_LOAD:
             if (value > 3) return fail(c, QS_ERR_ARG, "qs_set_tuning: QS_TUNE_SCORE_LOAD takes 0 .. 3");
@@ -609,6 +637,14 @@ static int prepare_staging(qs_ctx *c, uint64_t n_trees_hint) {
         }
         (void)hipGetLastError();
     }
+    // the correction stream of split slices (QS_TUNE_FIX_OVERLAP) with its hardware queue, which the runtime opens with the stream's
+    // first work: here instead of inside the first count
+    if (c->tune_fix_overlap && c->fix_stream.ensure() == hipSuccess) {
+        DevBuf<char> word;
+        if (word.reserve(64, nullptr) == hipSuccess && hipMemsetAsync(word.get(), 0, 64, c->fix_stream.get()) == hipSuccess)
+            (void)hipStreamSynchronize(c->fix_stream.get());
+    }
+    (void)hipGetLastError();
     return QS_OK;
 }
 
@@ -1263,6 +1299,79 @@ extern "C" int qs_class_plan(uint32_t n_taxa, const qs_tree_batch *hb, uint32_t 
  *        d slots): fitted to the per-shard timings of profiles/r06_scaling_model.json within 2 %. The largest shard is minimal
  *        over all contiguous cuts (bisection on the bound, greedy from the top). */
 constexpr double kShardTileOverhead = 4.0;
+// count-kernel cost of the d-range [d_lo, d_hi) on n taxa in those units
+struct TileCost {
+    std::vector<double> T0, T1;   // T0[c] = sum of tiles(c') over c' < c, T1[c] = sum of tiles(c') * c'
+    explicit TileCost(uint32_t n) : T0(n + 2, 0.0), T1(n + 2, 0.0) {
+        for (uint32_t c = 0; c <= n; ++c) {
+            const double t = c >= 2 ? (double)bitslice3_tiles_for_c(c) : 0.0;
+            T0[c + 1] = T0[c] + t; T1[c + 1] = T1[c] + t * c;
+        }
+    }
+    double operator()(uint32_t d_lo, uint32_t d_hi) const {
+        d_lo = std::max(d_lo, 3u);
+        double tot = 0.0;
+        for (uint32_t d1 = d_hi; d1 > d_lo;) {
+            const uint32_t d0 = d1 > d_lo + kDB ? d1 - kDB : d_lo, p = d1 - d0;
+            // third ids below the block see all p slots; c inside the block sees the slots above it: d1 - 1 - c
+            tot += (kShardTileOverhead + p) * T0[d0] + (kShardTileOverhead + (double)(d1 - 1)) * (T0[d1 - 1] - T0[d0]) - (T1[d1 - 1] - T1[d0]);
+            d1 = d0;
+        }
+        return tot;
+    }
+    double tiles(uint32_t d_lo, uint32_t d_hi) const {   // wave tiles of the range (d-blocks counted down from d_hi)
+        d_lo = std::max(d_lo, 3u);
+        double t = 0.0;
+        for (uint32_t d1 = d_hi; d1 > d_lo; d1 = d1 > d_lo + kDB ? d1 - kDB : d_lo) t += T0[d1 - 1];
+        return t;
+    }
+};
+
+/* Host-only: where a slice of the count step is split so that the depth-clamp corrections of the upper d-range run beside the count
+ * launch of the lower one (run_launch). The count launch of [d_lo, d_mid) is priced with the tile cost model above, the corrections
+ * of [d_mid, d_hi) as their share of the table's tuples; the answer is the SMALLEST d_mid (d-blocks aligned to d_hi) whose lower
+ * count launch is modelled to last kFixCover times the upper corrections -- the upper launch keeps nearly all of the work.
+ * Rates (MI355X, 512 taxa x 10000 binary trees, profiles/r06_cfg2_kernel_stats.csv): 284.8 ms for 3.67e7 cost units x 313 groups at
+ * 4 depth bits (a chain of 2(B+1)+2 instructions; half as much again with the third comparison of the general modes), 1.9e10
+ * corrections per second.
+ * 16-bit cells: two tuples may share a 32-bit word, which the corrections' atomics work on; d_mid is then moved up by half a d-block
+ * where needed, so that the upper range starts at a word boundary.
+ * `keep`: a d_mid whose launch orders exist already; it is kept if it still covers the corrections and the lower launch stays below
+ * the cap. Returns 0 = do not split: no corrections, a range too short, fewer than a wave population of tiles (kSplitMinTiles) in
+ * the lower launch, or a lower launch of more than kSplitMaxShare of the count. model_ms (may be NULL) = modelled ms of the lower
+ * count launch and of the upper corrections. */
+constexpr double kCountMsPerUnitGroup = 284.8 / (36697698.0 * 313.0), kFixPerMs = 1.9e7, kFixCover = 1.5, kFixLaunchMs = 0.05, kSplitMaxShare = 0.4;
+constexpr double kSplitMinTiles = 4096.0;   // 256 CUs x 4 SIMDs x 4 waves
+extern "C" int qs_fix_overlap_plan(uint32_t n_taxa, uint32_t d_lo, uint32_t d_hi, uint32_t count_bits, uint32_t mode, uint32_t depth_bits,
+                                   uint32_t n_groups, uint64_t corrections, uint32_t keep, double *model_ms) {
+    if (n_taxa < 4 || n_taxa > 65535 || d_hi > n_taxa || d_lo >= d_hi || (count_bits != 16 && count_bits != 32) || mode > 3) return QS_ERR_ARG;
+    if (model_ms) model_ms[0] = model_ms[1] = 0.0;
+    const uint32_t d_start = std::max(d_lo, 3u);
+    if (corrections == 0 || n_groups == 0 || d_hi < d_start + 2 * kDB) return 0;
+    const TileCost cost(n_taxa);
+    const bool gen = mode == MODE_GENERAL_FULL || mode == MODE_PARTIAL;
+    const double B = (double)std::min(std::max(depth_bits, 4u), 10u);
+    const double ms_per_unit = kCountMsPerUnitGroup * n_groups * (2.0 * (B + 1.0) + 2.0) / 12.0 * (gen ? 1.5 : 1.0);
+    const double all = cost(d_start, d_hi) * ms_per_unit, tuples = (double)binom4(n_taxa);
+    auto fix_ms = [&](uint32_t d_mid) { return (double)corrections * ((double)(binom4(d_hi) - binom4(d_mid)) / tuples) / kFixPerMs + kFixLaunchMs; };
+    auto aligned = [&](uint32_t d_mid) { return count_bits == 32 || ((binom4(d_mid) - binom4(d_lo)) & 1ull) == 0; };
+    auto fits = [&](uint32_t d_mid) {
+        const double lo_ms = cost(d_start, d_mid) * ms_per_unit;
+        return lo_ms >= kFixCover * fix_ms(d_mid) && lo_ms <= kSplitMaxShare * all && cost.tiles(d_start, d_mid) >= kSplitMinTiles;
+    };
+    uint32_t pick = 0;
+    if (keep > d_start && keep < d_hi && aligned(keep) && fits(keep)) pick = keep;
+    for (uint32_t j = (d_hi - d_start - 1) / kDB; !pick && j >= 1; --j) {
+        uint32_t d_mid = d_hi - j * kDB;
+        if (cost(d_start, d_mid) * ms_per_unit < kFixCover * fix_ms(d_mid)) continue;
+        if (!aligned(d_mid)) d_mid += kDB / 2;   // (C(d,4) is even for d mod 8 in 0..3 and odd above: half a block changes the parity)
+        if (!aligned(d_mid) || !fits(d_mid)) return 0;   // the smallest cover is too small or too large a launch: larger ones are no better
+        pick = d_mid;
+    }
+    if (pick && model_ms) { model_ms[0] = cost(d_start, pick) * ms_per_unit; model_ms[1] = fix_ms(pick); }
+    return (int)pick;
+}
+
 extern "C" int qs_shard_bounds(uint32_t n_taxa, uint32_t n_shards, uint32_t by, uint32_t *bounds) {
     if (!bounds || n_shards == 0 || n_taxa < 4 || n_taxa > 65535) return QS_ERR_ARG;
     const uint32_t n = n_taxa, K = n_shards;
@@ -1279,23 +1388,7 @@ extern "C" int qs_shard_bounds(uint32_t n_taxa, uint32_t n_shards, uint32_t by, 
         return QS_OK;
     }
     if (by != QS_SHARDS_BY_COST) return QS_ERR_ARG;
-    // T0[c] = sum of tiles(c') over c' < c, T1[c] = sum of tiles(c') * c'
-    std::vector<double> T0(n + 2, 0.0), T1(n + 2, 0.0);
-    for (uint32_t c = 0; c <= n; ++c) {
-        const double t = c >= 2 ? (double)bitslice3_tiles_for_c(c) : 0.0;
-        T0[c + 1] = T0[c] + t; T1[c + 1] = T1[c] + t * c;
-    }
-    auto cost = [&](uint32_t d_lo, uint32_t d_hi) {   // count-kernel cost of the shard [d_lo, d_hi)
-        d_lo = std::max(d_lo, 3u);
-        double tot = 0.0;
-        for (uint32_t d1 = d_hi; d1 > d_lo;) {
-            const uint32_t d0 = d1 > d_lo + kDB ? d1 - kDB : d_lo, p = d1 - d0;
-            // third ids below the block see all p slots; c inside the block sees the slots above it: d1 - 1 - c
-            tot += (kShardTileOverhead + p) * T0[d0] + (kShardTileOverhead + (double)(d1 - 1)) * (T0[d1 - 1] - T0[d0]) - (T1[d1 - 1] - T1[d0]);
-            d1 = d0;
-        }
-        return tot;
-    };
+    const TileCost cost(n);
     auto cut = [&](double bound, uint32_t *out) {     // greedy from the top; true if K shards suffice (shards left over stay empty: [0, 0))
         uint32_t hi = n;
         if (out) out[K] = n;
@@ -1418,6 +1511,8 @@ extern "C" int qs_batch_upload(qs_ctx *c, const qs_tree_batch *hb, qs_device_bat
                     for (uint32_t t0 = 0; t0 < triples; t0 += per_unit) {
                         fix_units.push_back(FixUnit{t, r.first | (r.second << 16), t0, std::min(triples, t0 + per_unit)});
                         b->fix_slot.push_back(slot);
+                        if (b->fix_work.empty()) b->fix_work.push_back(0);
+                        b->fix_work.push_back(b->fix_work.back() + (uint64_t)(std::min(triples, t0 + per_unit) - t0) * (L > 3 ? L - 3 : 0));
                     }
                 }
             };
@@ -1482,12 +1577,19 @@ extern "C" uint32_t qs_batch_flags(const qs_device_batch *b) {
     return (b->d.all_full ? QS_BATCH_ALL_TAXA : 0u) | (b->d.all_binary ? QS_BATCH_BINARY : 0u);
 }
 
-// corrections of the depth clamp for the trees in slots [slot_lo, slot_hi) of the batch, after their count kernel
-static hipError_t clamp_fix_slots(qs_ctx *c, const qs_device_batch *b, uint32_t slot_lo, uint32_t slot_hi, int mode, uint32_t *wire) {
+// corrections of the depth clamp for the trees in slots [slot_lo, slot_hi) of the batch whose largest id lies in [d_a, d_b), on
+// stream s: after the count kernel that stored that range
+static hipError_t clamp_fix_slots(qs_ctx *c, hipStream_t s, const qs_device_batch *b, uint32_t slot_lo, uint32_t slot_hi, uint32_t d_a, uint32_t d_b,
+                                  int mode, uint32_t *wire) {
     const auto lo = std::lower_bound(b->fix_slot.begin(), b->fix_slot.end(), slot_lo), hi = std::lower_bound(lo, b->fix_slot.end(), slot_hi);
-    if (lo == hi) return hipSuccess;
-    return launch_clamp_fix(c->stream, b->d, b->d.fix_units + (lo - b->fix_slot.begin()), (uint32_t)(hi - lo), std::max(c->d_lo, 3u), c->d_hi,
+    if (lo == hi || d_a >= d_b) return hipSuccess;
+    return launch_clamp_fix(s, b->d, b->d.fix_units + (lo - b->fix_slot.begin()), (uint32_t)(hi - lo), d_a, d_b,
                             c->rank_lo, c->table, (int)c->count_bits, mode, wire, c->dev_flags.get());
+}
+// ... and what they are modelled to cost: (tree, quartet) corrections over the whole table (an upper bound, see qs_batch_upload)
+static uint64_t clamp_fix_work(const qs_device_batch *b, uint32_t slot_lo, uint32_t slot_hi) {
+    const auto lo = std::lower_bound(b->fix_slot.begin(), b->fix_slot.end(), slot_lo), hi = std::lower_bound(lo, b->fix_slot.end(), slot_hi);
+    return b->fix_work.empty() ? 0 : b->fix_work[hi - b->fix_slot.begin()] - b->fix_work[lo - b->fix_slot.begin()];
 }
 
 // the pair-depth panel holds `need` bytes (growing it waits for the launches that read the old one)
@@ -1508,6 +1610,55 @@ static int count_geometry(qs_ctx *c, bool tiles16x8, bool coop, CountGeometry &g
     const int rc = tile_order(c, &g.perm);
     if (rc == QS_OK && coop) { g.perm_coop = c->perm_coop.get(); g.n_coop = c->n_coop; g.perm_rest = c->perm_rest.get(); g.n_rest = c->n_rest; }
     return rc;
+}
+
+// The 16x8 tiling `g` of the shard cut at d_mid into the tilings of [d_mid, d_hi) (hi: the leading d-blocks of g, so g's prefix
+// array serves) and [d_lo, d_mid) (lo: d-blocks counted down from d_mid, a prefix array of its own), each with its launch order in
+// the nesting of g's. Kept in the context for the d_mid they were built for.
+static int split_geometry(qs_ctx *c, uint32_t d_mid, const CountGeometry &g, CountGeometry &hi, CountGeometry &lo, bool *rebuilt) {
+    *rebuilt = false;
+    qs_ctx::Split &S = c->split;
+    const uint32_t d_start = g.d_lo;
+    if (S.d_mid != d_mid || S.perm_of != g.perm) {
+        // Everything goes onto the context's stream, behind the launches that may still read the old lists. The host waits only
+        // where it rewrites what the device may still use: for the copies out of the host lists of an earlier split (the runtime may
+        // read pageable memory after the call returns), and for the stream where a buffer has to grow. The first split of a context
+        // finds neither.
+        S.d_mid = 0;
+        if (S.copied_valid) QS_HIP(c, hipEventSynchronize(S.copied.get()));
+        S.copied_valid = false;
+        S.n_dblk_hi = (g.d_hi - std::max(d_mid, d_start) + kDB - 1) / kDB;
+        S.tiles_hi = c->h_dp3[S.n_dblk_hi];
+        S.n_dblk_lo = d_mid > d_start ? (d_mid - d_start + kDB - 1) / kDB : 0;
+        S.h_dp_lo.assign(S.n_dblk_lo + 1, 0);   // (host copies stay in the context: the asynchronous copies read them)
+        for (uint32_t k = 0; k < S.n_dblk_lo; ++k) S.h_dp_lo[k + 1] = S.h_dp_lo[k] + c->h_cp3[d_mid - k * kDB - 1];
+        S.tiles_lo = S.h_dp_lo[S.n_dblk_lo];
+        if (S.dprefix_lo.reserve(S.h_dp_lo.size() * 4, &c->stream) != hipSuccess) return fail(c, QS_ERR_OOM, "hipMalloc split tiling");
+        QS_HIP(c, hipMemcpyAsync(S.dprefix_lo.get(), S.h_dp_lo.data(), S.h_dp_lo.size() * 4, hipMemcpyHostToDevice, c->stream));
+        if (g.perm) {
+            // upper range: the shard's launch order without the tiles of the lower d-blocks -- its tiles are the ids below tiles_hi and
+            // the nesting stays --, filtered on the device (12 M entries at 512 taxa: two short kernels instead of 25 ms of host work)
+            if (S.perm_hi.reserve(std::max<size_t>(S.tiles_hi, 1) * 4, &c->stream) != hipSuccess ||
+                S.filter_scratch.reserve(perm_filter_scratch_bytes(g.total_tiles), &c->stream) != hipSuccess)
+                return fail(c, QS_ERR_OOM, "hipMalloc split tile order");
+            QS_HIP(c, launch_perm_filter(c->stream, g.perm, g.total_tiles, S.tiles_hi, S.perm_hi.get(), S.tiles_hi, S.filter_scratch.get()));
+            // lower range: a tiling of its own (d-blocks counted down from d_mid), a few per cent of the tiles: enumerated on the host
+            std::string perr;
+            const TilePermParams P_lo{c->tile_chunk, c->tile_cblock, c->tile_cgroup, d_mid, S.n_dblk_lo, S.tiles_lo};
+            if (!build_tile_perm(P_lo, c->h_cp3, S.h_dp_lo, S.h_perm_lo, perr)) return fail(c, QS_ERR_STATE, perr);
+            if (S.perm_lo.reserve(std::max<size_t>(S.h_perm_lo.size(), 1) * 4, &c->stream) != hipSuccess) return fail(c, QS_ERR_OOM, "hipMalloc split tile order");
+            if (!S.h_perm_lo.empty()) QS_HIP(c, hipMemcpyAsync(S.perm_lo.get(), S.h_perm_lo.data(), S.h_perm_lo.size() * 4, hipMemcpyHostToDevice, c->stream));
+        }
+        QS_HIP(c, S.copied.ensure());
+        QS_HIP(c, hipEventRecord(S.copied.get(), c->stream));
+        S.copied_valid = true;
+        S.perm_of = g.perm; S.d_mid = d_mid;
+        *rebuilt = true;
+    }
+    hi = g; lo = g;
+    hi.d_lo = std::max(d_mid, d_start); hi.n_dblk = S.n_dblk_hi; hi.total_tiles = S.tiles_hi; hi.perm = g.perm ? S.perm_hi.get() : nullptr;
+    lo.d_hi = std::max(d_mid, d_start); lo.n_dblk = S.n_dblk_lo; lo.total_tiles = S.tiles_lo; lo.dprefix = S.dprefix_lo.get(); lo.perm = g.perm ? S.perm_lo.get() : nullptr;
+    return QS_OK;
 }
 
 // One launch of a count kernel = 1..4 segments; a segment = one class's share of it: the slots [slot0, slot0 + trees) of the
@@ -1563,6 +1714,32 @@ static int run_launch(qs_ctx *c, const qs_device_batch *b, const Launch &L, uint
     // byte more would make the CLI's first count wait for the stream, free that panel and allocate another.
     rc = ensure_panel(c, (size_t)per_slice * group_bytes + 256 * (L.segs.size() - 1));
     if (rc != QS_OK) return rc;
+    // Split slices (QS_TUNE_FIX_OVERLAP): one d_mid for the launch, planned for a slice's groups and its share of the launch's
+    // corrections. Not with the byte-SWAR kernel (no corrections), the cooperative lists, or where the plan says a split does not pay.
+    uint32_t d_mid = 0;
+    CountGeometry g_hi = g, g_lo = g;
+    if (bitsliced && d.n_fix && c->tune_fix_overlap && !g.perm_coop) {
+        uint64_t work = 0;
+        for (const Seg &sg : L.segs) work += clamp_fix_work(b, sg.slot0, sg.slot0 + sg.trees);
+        const uint32_t grp = std::min(per_slice, g_total), n_slices = (g_total + per_slice - 1) / per_slice;
+        work = (work + n_slices - 1) / std::max(n_slices, 1u);
+        if (c->tune_fix_split_at) d_mid = (work && c->tune_fix_split_at > c->d_lo && c->tune_fix_split_at < c->d_hi) ? c->tune_fix_split_at : 0;
+        else {
+            int gen = 0;
+            for (const Seg &sg : L.segs) gen = gen || sg.mode == MODE_GENERAL_FULL || sg.mode == MODE_PARTIAL;
+            const int pick = qs_fix_overlap_plan(c->n, c->d_lo, c->d_hi, c->count_bits, gen ? MODE_GENERAL_FULL : MODE_BINARY_FULL, (uint32_t)L.bits, grp, work, c->split.d_mid, nullptr);
+            d_mid = pick > 0 ? (uint32_t)pick : 0;
+        }
+        if (d_mid) {
+            QS_HIP(c, c->fix_stream.ensure());
+            QS_HIP(c, c->fix_go.ensure());
+            QS_HIP(c, c->fix_done.ensure());
+            bool rebuilt = false;
+            rc = split_geometry(c, d_mid, g, g_hi, g_lo, &rebuilt);
+            if (rc != QS_OK) return rc;
+            if (timed && rebuilt) QS_HIP(c, mark(c, 3));   // (the filter kernels and copies of a new split: not the next panel build's time)
+        }
+    }
     for (uint32_t g0 = 0; g0 < g_total; g0 += per_slice) {
         const uint32_t g1 = std::min(g_total, g0 + per_slice);
         // per CountMode, as the fused kernel takes them (a mode without trees in this slice: 0 groups)
@@ -1587,18 +1764,66 @@ static int run_launch(qs_ctx *c, const qs_device_batch *b, const Launch &L, uint
         }
         if (timed) QS_HIP(c, mark(c, 0));
         const bool ow = overwrite && first;
-        if (L.kernel == KERNEL_FUSED)
-            QS_HIP(c, launch_count_bitslice3_fused(c->stream, g, seg_panel, seg_groups, seg_trees, L.bits, c->table, (int)c->count_bits, c->dev_flags.get(), ow));
-        else if (L.kernel == KERNEL_BITSLICE3)
-            QS_HIP(c, launch_count_bitslice3(c->stream, g, seg_panel[mode0], L.bits, mode0, seg_groups[mode0], seg_trees[mode0], wire ? nullptr : c->table,
-                                             wire ? 32 : (int)c->count_bits, c->dev_flags.get(), ow, wire));
-        else QS_HIP(c, launch_count_gather(c->stream, g, seg_panel[mode0], L.bits, mode0, seg_groups[mode0], seg_trees[mode0], c->table, (int)c->count_bits, c->dev_flags.get(), ow));
+        // a count launch over the tiling gg (the whole shard, or one d-range of a split slice)
+        auto count_range = [&](const CountGeometry &gg) -> hipError_t {
+            if (L.kernel == KERNEL_FUSED)
+                return launch_count_bitslice3_fused(c->stream, gg, seg_panel, seg_groups, seg_trees, L.bits, c->table, (int)c->count_bits, c->dev_flags.get(), ow);
+            if (L.kernel == KERNEL_BITSLICE3)
+                return launch_count_bitslice3(c->stream, gg, seg_panel[mode0], L.bits, mode0, seg_groups[mode0], seg_trees[mode0], wire ? nullptr : c->table,
+                                              wire ? 32 : (int)c->count_bits, c->dev_flags.get(), ow, wire);
+            return launch_count_gather(c->stream, gg, seg_panel[mode0], L.bits, mode0, seg_groups[mode0], seg_trees[mode0], c->table, (int)c->count_bits, c->dev_flags.get(), ow);
+        };
+        // the corrections of the slice's trees in the d-range [d_a, d_b), on stream s
+        auto fix_range = [&](hipStream_t s, uint32_t d_a, uint32_t d_b) -> hipError_t {
+            for (int mo = 0; mo < 4; ++mo) {   // (the rule of the correction depends on the mode: a tied quartet sits in the third cell of a binary tree)
+                const hipError_t e = seg_groups[mo] ? clamp_fix_slots(c, s, b, seg_slot[mo], seg_slot[mo] + seg_trees[mo], d_a, d_b, mo, wire) : hipSuccess;
+                if (e != hipSuccess) return e;
+            }
+            return hipSuccess;
+        };
+        bool has_fix = false;   // (never the byte-SWAR kernel: its panel holds the trees' own depths)
+        for (int mo = 0; mo < 4 && bitsliced && d.n_fix; ++mo) has_fix = has_fix || (seg_groups[mo] && clamp_fix_work(b, seg_slot[mo], seg_slot[mo] + seg_trees[mo]) > 0);
+        // (with the first overwriting launch enqueued the old contents are gone: a later refusal must not leave their count behind)
+        auto overwritten = [&] { if (ow) { if (wire) c->wire_trees = 0; else c->trees_counted = 0; } };
         first = false;
-        if (timed) QS_HIP(c, mark(c, 1));
-        if (bitsliced && d.n_fix) {   // (never the byte-SWAR kernel: its panel holds the trees' own depths)
-            for (int mo = 0; mo < 4; ++mo)   // (the rule of the correction depends on the mode: a tied quartet sits in the third cell of a binary tree)
-                if (seg_groups[mo]) QS_HIP(c, clamp_fix_slots(c, b, seg_slot[mo], seg_slot[mo] + seg_trees[mo], mo, wire));
-            if (timed) QS_HIP(c, mark(c, 2));
+        if (has_fix && d_mid) {
+            // THE ORDERING RULE of a split slice. A correction must land after the store of the cell it corrects, and a cell belongs to
+            // exactly one of the two d-ranges (a d-range is one contiguous piece of the table), so:
+            //   main stream:        count [d_mid, d_hi) -> fix_go -> count [d_lo, d_mid) -> corrections of [d_lo, d_mid) -> wait for fix_done
+            //   correction stream:  wait for fix_go -> corrections of [d_mid, d_hi) -> fix_done
+            // Kernels in flight together (the lower count launch and the upper corrections) work on disjoint ranges; everything later on
+            // the main stream -- the next slice, the next class, whoever reads the table -- comes after both. Whatever fails once the
+            // correction stream has work, the main stream still waits for it before the error is returned.
+            const hipStream_t fs = c->fix_stream.get();
+            QS_HIP(c, count_range(g_hi));
+            overwritten();
+            const uint32_t ev_hi = c->ev_used;
+            if (timed) QS_HIP(c, mark(c, 1));
+            QS_HIP(c, hipEventRecord(c->fix_go.get(), c->stream));
+            QS_HIP(c, hipStreamWaitEvent(fs, c->fix_go.get(), 0));
+            hipError_t e = fix_range(fs, g_hi.d_lo, g_hi.d_hi);
+            if (e == hipSuccess && timed) e = mark(c, 2, &fs, ev_hi);
+            const hipError_t e_done = hipEventRecord(c->fix_done.get(), fs);
+            uint32_t ev_lo = 0;
+            if (e == hipSuccess) e = count_range(g_lo);
+            if (e == hipSuccess) { ev_lo = c->ev_used; if (timed) e = mark(c, 4, nullptr, ev_hi); }
+            if (e == hipSuccess) e = fix_range(c->stream, g_lo.d_lo, g_lo.d_hi);
+            if (e == hipSuccess && timed) e = mark(c, 2, nullptr, ev_lo);
+            // the join: behind fix_done, or -- if that event could not be recorded -- once the correction stream has drained
+            const hipError_t e_join = e_done == hipSuccess ? hipStreamWaitEvent(c->stream, c->fix_done.get(), 0) : hipStreamSynchronize(fs);
+            QS_HIP(c, e);
+            QS_HIP(c, e_done);
+            QS_HIP(c, e_join);
+            if (timed) QS_HIP(c, mark(c, 3));
+            c->last_split = d_mid; ++c->last_splits;
+        } else {
+            QS_HIP(c, count_range(g));
+            overwritten();
+            if (timed) QS_HIP(c, mark(c, 1));
+            if (has_fix) {
+                QS_HIP(c, fix_range(c->stream, g.d_lo, g.d_hi));
+                if (timed) QS_HIP(c, mark(c, 2));
+            }
         }
     }
     return QS_OK;
@@ -1624,7 +1849,7 @@ static int count_batch_wire(qs_ctx *c, const qs_device_batch *b, uint32_t algo) 
         return fail(c, QS_ERR_OVERFLOW, "QS_COUNT_WIRE16X2: more than 65535 trees do not fit 16-bit cells");
     if (d.class_bits[d.n_classes - 1] > 10) return fail(c, QS_ERR_UNSUPPORTED, "QS_COUNT_WIRE16X2: tree depth needs more than 10 bits; count into the table instead");
     { const uint32_t *order; int rc_o = tile_order(c, &order); if (rc_o != QS_OK) return rc_o; }   // (a failure here leaves the last call's events as they were)
-    c->ev_used = 0;
+    c->ev_used = 0; c->last_split = c->last_splits = 0;
     if (timed) QS_HIP(c, mark(c, 0));
     bool first = true;
     c->variant = "gather/binary_full/bitslice_";
@@ -1637,6 +1862,7 @@ static int count_batch_wire(qs_ctx *c, const qs_device_batch *b, uint32_t algo) 
     }
     c->variant += "/wire_u16x2";
     if (d.n_fix) c->variant += "/clamp:" + std::to_string(d.clamped_trees);
+    if (c->last_splits) c->variant += "/overlap:" + std::to_string(c->last_split);
     if (c->n_coop) c->variant += "/coop4";
     c->wire_trees = (overwrite ? 0 : c->wire_trees) + d.n_trees;
     c->last_timed = timed;
@@ -1666,8 +1892,9 @@ extern "C" int qs_count_batch(qs_ctx *c, const qs_device_batch *b, uint32_t algo
     algo &= ~(QS_COUNT_OVERWRITE | QS_COUNT_TIMED);
     if (algo == QS_ALGO_AUTO) algo = QS_ALGO_GATHER;
     if (overwrite && algo != QS_ALGO_GATHER) return fail(c, QS_ERR_ARG, "qs_count_batch: QS_COUNT_OVERWRITE needs the gather algorithm");
-    // (an overwrite resets trees_counted only once nothing can fail any more: a refused call leaves table and count as they were)
-    c->ev_used = 0;
+    // (a call refused before its first launch leaves table and count as they were; run_launch resets trees_counted with the first
+    // overwriting launch it enqueues, so that a refusal after it -- a later class too deep, a panel that cannot grow -- leaves no stale count)
+    c->ev_used = 0; c->last_split = c->last_splits = 0;
     if (timed) QS_HIP(c, mark(c, 0));
     if (algo == QS_ALGO_GATHER) {
         static const char *mode_names[4] = {"binary_full", "general_full", "partial", "binary_partial"};
@@ -1739,6 +1966,7 @@ extern "C" int qs_count_batch(qs_ctx *c, const qs_device_batch *b, uint32_t algo
         if (fused_launch_groups) c->variant += "/fused:" + std::to_string(fused_launch_groups);   // depth-bits groups whose classes shared a launch (count_bitslice3_fused_kernel)
         if (any_coop) c->variant += "/coop4";
         if (!all_swar && d.n_fix) c->variant += "/clamp:" + std::to_string(d.clamped_trees);   // trees counted below their own depth bits + clamp_fix_kernel
+        if (c->last_splits) c->variant += "/overlap:" + std::to_string(c->last_split);           // slices split at that largest id: corrections beside the lower count launch
     } else if (algo == QS_ALGO_SCATTER) {
         if (!d.node_off) return fail(c, QS_ERR_ARG, "qs_count_batch: QS_ALGO_SCATTER needs node_off/rng_off/ranges in the batch");
         if (c->n > 4096) return fail(c, QS_ERR_UNSUPPORTED, "scatter: n too large");
@@ -1786,8 +2014,10 @@ extern "C" int qs_last_count_ms(qs_ctx *c, float out_ms[3]) {
     out_ms[0] = out_ms[1] = 0.f;
     for (uint32_t i = 1; i < c->ev_used; ++i) {
         float ms = 0.f;
-        QS_HIP(c, hipEventElapsedTime(&ms, c->evs[i - 1], c->evs[i]));
-        out_ms[c->ev_kind[i] ? 1 : 0] += ms;   // (the depth-clamp corrections count as count-kernel time: qs_last_count_fix_ms has their share)
+        if (c->ev_kind[i] == 3) continue;      // (a wait for the correction stream or the set-up of a new split, not a kernel of the step)
+        QS_HIP(c, hipEventElapsedTime(&ms, c->evs[c->ev_from[i]], c->evs[i]));
+        out_ms[c->ev_kind[i] ? 1 : 0] += ms;   // (the depth-clamp corrections count as count-kernel time: qs_last_count_fix_ms has their share; those of a
+                                               // split slice's upper range run beside its lower count launch, so the kernels may sum to more than [2])
     }
     QS_HIP(c, hipEventElapsedTime(&out_ms[2], c->evs[0], c->evs[c->ev_used - 1]));
     return QS_OK;
@@ -1806,7 +2036,7 @@ extern "C" float qs_last_count_fix_ms(qs_ctx *c) {
     float sum = 0.f;
     for (uint32_t i = 1; i < c->ev_used; ++i) {
         float ms = 0.f;
-        if (c->ev_kind[i] == 2 && hipEventElapsedTime(&ms, c->evs[i - 1], c->evs[i]) == hipSuccess) sum += ms;
+        if (c->ev_kind[i] == 2 && hipEventElapsedTime(&ms, c->evs[c->ev_from[i]], c->evs[i]) == hipSuccess) sum += ms;
     }
     return sum;
 }
@@ -1815,11 +2045,13 @@ extern "C" int qs_last_count_events(qs_ctx *c, float *ms, uint8_t *kind, int cap
     if (!c || !c->last_timed || c->ev_used < 2) return 0;
     if (hipEventSynchronize(c->evs[c->ev_used - 1]) != hipSuccess) return 0;
     int k = 0;
-    for (uint32_t i = 1; i < c->ev_used && k < cap; ++i, ++k) {
+    for (uint32_t i = 1; i < c->ev_used && k < cap; ++i) {
+        if (c->ev_kind[i] == 3) continue;   // (a wait for the correction stream or the set-up of a new split, not a kernel of the step)
         float t = 0.f;
-        (void)hipEventElapsedTime(&t, c->evs[i - 1], c->evs[i]);
+        (void)hipEventElapsedTime(&t, c->evs[c->ev_from[i]], c->evs[i]);
         if (ms) ms[k] = t;
-        if (kind) kind[k] = c->ev_kind[i];
+        if (kind) kind[k] = c->ev_kind[i] == 4 ? 1 : c->ev_kind[i];   // (the second count launch of a split slice is a count kernel)
+        ++k;
     }
     return k;
 }
@@ -1831,6 +2063,11 @@ extern "C" int qs_batch_clamp_info(const qs_device_batch *b, uint64_t out[3]) {
 }
 
 extern "C" const char *qs_last_count_variant(const qs_ctx *c) { return c ? c->variant.c_str() : ""; }
+
+extern "C" int qs_last_count_split(const qs_ctx *c, uint32_t *n_slices) {
+    if (n_slices) *n_slices = c ? c->last_splits : 0;
+    return c ? (int)c->last_split : 0;
+}
 
 extern "C" int qs_lookup(qs_ctx *c, uint64_t nq, const uint16_t *abcd, uint64_t *out3) {
     if (!c || !c->table) return fail(c, QS_ERR_STATE, "qs_lookup: no table");

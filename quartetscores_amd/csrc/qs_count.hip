@@ -1294,6 +1294,62 @@ hipError_t launch_unpack16x2(hipStream_t s, const void *src, void *dst_u16, uint
     return hipGetLastError();
 }
 
+// ======================================================================================
+// launch order of a split slice's upper d-range: the entries below `limit` of the shard's launch order, in their order
+// ======================================================================================
+// The upper range's tiles are the leading tile ids of the shard's tiling, so its launch order is the shard's with the other
+// entries left out (the nesting stays). Two passes, no flags: every workgroup counts what it keeps of its kFilterItems
+// consecutive entries; then it sums the counts of the workgroups in front of it and writes its own behind them.
+constexpr int kFilterThreads = 256, kFilterPerThread = 8, kFilterItems = kFilterThreads * kFilterPerThread;
+__global__ __launch_bounds__(kFilterThreads) void perm_filter_count_kernel(const uint32_t *__restrict__ perm, uint32_t n, uint32_t limit,
+                                                                           uint32_t *__restrict__ block_counts) {
+    __shared__ uint32_t part[kFilterThreads];
+    const uint32_t first = blockIdx.x * kFilterItems + threadIdx.x * kFilterPerThread;
+    uint32_t k = 0;
+    for (int j = 0; j < kFilterPerThread; ++j) k += (first + j < n && perm[first + j] < limit) ? 1u : 0u;
+    part[threadIdx.x] = k;
+    __syncthreads();
+    for (uint32_t w = kFilterThreads / 2; w; w >>= 1) {
+        if (threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = part[0];
+}
+__global__ __launch_bounds__(kFilterThreads) void perm_filter_write_kernel(const uint32_t *__restrict__ perm, uint32_t n, uint32_t limit,
+                                                                           const uint32_t *__restrict__ block_counts, uint32_t *__restrict__ out,
+                                                                           uint32_t out_cap) {
+    __shared__ uint32_t part[kFilterThreads], scan[kFilterThreads];
+    uint32_t before = 0;
+    for (uint32_t b = threadIdx.x; b < blockIdx.x; b += kFilterThreads) before += block_counts[b];
+    part[threadIdx.x] = before;
+    const uint32_t first = blockIdx.x * kFilterItems + threadIdx.x * kFilterPerThread;
+    uint32_t v[kFilterPerThread], k = 0;
+    for (int j = 0; j < kFilterPerThread; ++j) { v[j] = first + j < n ? perm[first + j] : 0xFFFFFFFFu; k += v[j] < limit ? 1u : 0u; }
+    scan[threadIdx.x] = k;
+    __syncthreads();
+    for (uint32_t w = kFilterThreads / 2; w; w >>= 1) {
+        if (threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    for (uint32_t w = 1; w < kFilterThreads; w <<= 1) {   // inclusive scan of the threads' counts
+        const uint32_t add = threadIdx.x >= w ? scan[threadIdx.x - w] : 0u;
+        __syncthreads();
+        scan[threadIdx.x] += add;
+        __syncthreads();
+    }
+    uint32_t pos = part[0] + scan[threadIdx.x] - k;
+    for (int j = 0; j < kFilterPerThread; ++j)
+        if (v[j] < limit) { if (pos < out_cap) out[pos] = v[j]; ++pos; }
+}
+size_t perm_filter_scratch_bytes(uint32_t n) { return (size_t)((n + kFilterItems - 1) / kFilterItems + 1) * 4; }
+hipError_t launch_perm_filter(hipStream_t s, const uint32_t *perm, uint32_t n, uint32_t limit, uint32_t *out, uint32_t out_cap, uint32_t *scratch) {
+    if (n == 0) return hipSuccess;
+    dim3 grid((n + kFilterItems - 1) / kFilterItems), block(kFilterThreads);
+    hipLaunchKernelGGL(perm_filter_count_kernel, grid, block, 0, s, perm, n, limit, scratch);
+    hipLaunchKernelGGL(perm_filter_write_kernel, grid, block, 0, s, perm, n, limit, scratch, out, out_cap);
+    return hipGetLastError();
+}
+
 // dst[i] += src[0][i] + ... + src[n_src-1][i] over 32-bit words: the single-process reduce(-scatter) of the multi-GPU host
 // (`--reduce p2p`): GPU g sums its chunk of every peer's table with plain 16-byte loads over xGMI (the sources are peer
 // device memory, mapped by hipDeviceEnablePeerAccess), no communicator. Grid-stride; every load is read once: non-temporal.

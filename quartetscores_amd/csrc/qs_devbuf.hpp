@@ -47,4 +47,31 @@ public:
 };
 template <typename T> using PinBuf = DevBuf<T, true>;
 
+// A non-blocking stream of the context's own, created on first use. Move-less; destroyed (after its work has drained) with its owner.
+class DevStream {
+    hipStream_t s_ = nullptr;
+
+public:
+    DevStream() = default;
+    DevStream(const DevStream &) = delete;
+    DevStream &operator=(const DevStream &) = delete;
+    ~DevStream() { if (s_) (void)hipStreamDestroy(s_); }
+    hipStream_t get() const { return s_; }
+    explicit operator bool() const { return s_ != nullptr; }
+    hipError_t ensure() { return s_ ? hipSuccess : hipStreamCreateWithFlags(&s_, hipStreamNonBlocking); }
+};
+
+// An ordering event (no timing), created on first use.
+class DevEvent {
+    hipEvent_t e_ = nullptr;
+
+public:
+    DevEvent() = default;
+    DevEvent(const DevEvent &) = delete;
+    DevEvent &operator=(const DevEvent &) = delete;
+    ~DevEvent() { if (e_) (void)hipEventDestroy(e_); }
+    hipEvent_t get() const { return e_; }
+    hipError_t ensure() { return e_ ? hipSuccess : hipEventCreateWithFlags(&e_, hipEventDisableTiming); }
+};
+
 }  // namespace qs

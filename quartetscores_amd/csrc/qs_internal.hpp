@@ -123,6 +123,9 @@ hipError_t launch_count_bitslice3_fused(hipStream_t s, const CountGeometry &g, c
                                         bool overwrite);
 hipError_t launch_clamp_fix(hipStream_t s, const DeviceBatch &b, const FixUnit *units, uint32_t n_units, uint32_t d_lo, uint32_t d_hi,
                             uint64_t rank_lo, void *table, int count_bits, int mode, uint32_t *wire, uint32_t *overflow_flag); // corrections of the depth clamp (after the class's count kernel)
+// out[0 .. ) <- the entries of perm[0 .. n) below `limit`, in their order (at most out_cap are written); scratch: perm_filter_scratch_bytes(n)
+size_t perm_filter_scratch_bytes(uint32_t n);
+hipError_t launch_perm_filter(hipStream_t s, const uint32_t *perm, uint32_t n, uint32_t limit, uint32_t *out, uint32_t out_cap, uint32_t *scratch);
 uint32_t bitslice3_tiles_for_c(uint32_t c); // wave tiles per (d-block, c) of count_bitslice3_kernel
 hipError_t launch_count_scatter(hipStream_t s, const DeviceBatch &b, uint32_t n, uint32_t d_lo, uint32_t d_hi,
                                 uint64_t rank_lo, void *table, int count_bits, uint32_t *overflow_flag);

@@ -500,6 +500,11 @@ class Context:
         k = int(self.L.qs_last_count_events(self.h, ms, kind, 256))
         return [(("panel", "count", "fix")[min(int(kind[i]), 2)], float(ms[i])) for i in range(k)]
 
+    def last_count_split(self) -> Tuple[int, int]:
+        """(d_mid, slices split there) of the last count_batch (QS_TUNE_FIX_OVERLAP); (0, 0) = every slice was one count launch."""
+        k = C.c_uint32(0)
+        return int(self.L.qs_last_count_split(self.h, C.byref(k))), int(k.value)
+
     def batch_clamp_info(self, hb) -> Tuple[int, int, int]:
         """(trees counted in a class below their own depth bits, their (tree, quartet) corrections, correction workgroups)."""
         out = (C.c_uint64 * 3)()
