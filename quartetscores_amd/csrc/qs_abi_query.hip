@@ -1,0 +1,310 @@
+// qs_abi_query.hip -- what reads a finished table against a reference tree and is not the score: per-taxon support, taxon and clade
+// placement, per-tree agreement. Host code only; the kernels are in qs_taxon.hip, qs_place.hip, qs_place_clade.hip and qs_agree.hip.
+#include "qs_ctx.hpp"
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+using namespace qs;
+
+// Per-taxon quartet support of this context's table against the reference tree (qs_taxon.hip). The reference has no such
+// output: this replaces nothing there (the nearest is printRawQICScores, one text line per quartet).
+extern "C" int qs_taxon_support(qs_ctx *c, const qs_ref_tree *ref, int64_t *dst_device) {
+    if (!c) return QS_ERR_ARG;
+    if (!dst_device) return fail(c, QS_ERR_ARG, "qs_taxon_support: NULL argument");
+    if (reinterpret_cast<uintptr_t>(dst_device) % 8) return fail(c, QS_ERR_ARG, "qs_taxon_support: dst_device is not 8-byte aligned");
+    if (!c->table) return fail(c, QS_ERR_STATE, "qs_taxon_support: no table");
+    if (taxon_lds_bytes(c->n) > 160u * 1024u) return fail(c, QS_ERR_UNSUPPORTED, "qs_taxon_support: more than 3413 taxa (the accumulators of a workgroup live in LDS)");
+    // every sum is at most C(n-1,3) x (largest count): the trees behind the table if known, else what a cell can hold
+    const uint64_t max_count = table_max_count(c);
+    const uint64_t per_taxon = c->n >= 4 ? (uint64_t)(c->n - 1) * (c->n - 2) / 2 * (c->n - 3) / 3 : 0;
+    if (per_taxon && max_count > (uint64_t)INT64_MAX / per_taxon)
+        return fail(c, QS_ERR_OVERFLOW, "qs_taxon_support: C(n-1,3) x the largest possible count exceeds 63 bits");
+    QS_HIP(c, hipSetDevice(c->device));
+    const RefHost *Rp = nullptr;
+    if (int rc = get_ref(c, ref, true, &Rp)) return rc;
+    ScoreDevice sd;
+    fill_score_device(c, *Rp, c->ref_lca_dev.get(), sd);
+    sd.rank_lo = c->rank_lo; sd.n_tuples = c->n_tuples; sd.table = c->table; sd.count_bits = (int)c->count_bits;   // the context's own table, not a scoring view
+    sd.flags = nullptr;
+    if (int rc = ensure_bundle_plan(c, sd, 3)) return rc;
+    // (a context's table is cut by the largest id: it starts and ends at a row start, plan_bundles finds no partial rows)
+    if (c->bundle[2].n_parts) return fail(c, QS_ERR_UNSUPPORTED, "qs_taxon_support: the table does not start and end at a row start");
+    QS_HIP(c, hipMemsetAsync(dst_device, 0, (size_t)c->n * 6 * 8, c->stream));
+    const bool wide = max_count >= (1ull << 32) / 192;   // 64 lanes x 3 counts in a 32-bit partial sum
+    QS_HIP(c, launch_taxon_support(c->stream, sd, wide, c->n_cu, reinterpret_cast<unsigned long long *>(dst_device)));
+    return QS_OK;   // asynchronous on the context's stream
+}
+
+// qs_taxon_placement: the link lookups of the cached reference tree on the device, beside its LCA matrix
+static int ensure_place_ref(qs_ctx *c, const RefHost &R) {
+    if (c->place_child_dev) return QS_OK;
+    const uint32_t n = R.n;
+    uint32_t max_depth = 0;
+    for (uint32_t d : R.depth) max_depth = std::max(max_depth, d);
+    // child[i][j] = the child of lca(i,j) that holds leaf j: j's ancestor one level below the LCA
+    c->place_child.assign((size_t)n * n, 0);
+    std::vector<uint32_t> at_depth(max_depth + 2, 0);
+    for (uint32_t j = 0; j < n; ++j) {
+        for (uint32_t v = R.leaf_node_in[j];; v = (uint32_t)R.parent[v]) { at_depth[R.depth[v]] = v; if (R.parent[v] < 0) break; }
+        for (uint32_t i = 0; i < n; ++i)
+            if (i != j) c->place_child[(size_t)i * n + j] = (uint16_t)at_depth[(R.lca[(size_t)i * n + j] >> 16) + 1];
+    }
+    // next[q][p], p < q: the end of the run of p over which lca(p,q) AND the child of it that holds p stay the same
+    c->place_next.assign((size_t)n * n, 0);
+    for (uint32_t q = 1; q < n; ++q) {
+        const size_t o = (size_t)q * n;
+        c->place_next[o + q - 1] = (uint16_t)q;
+        for (uint32_t p = q - 1; p-- > 0;)
+            c->place_next[o + p] = (R.lca[o + p] != R.lca[o + p + 1] || c->place_child[o + p] != c->place_child[o + p + 1]) ? (uint16_t)(p + 1) : c->place_next[o + p + 1];
+    }
+    DevBuf<uint16_t> child, next; DevBuf<uint32_t> node;
+    QS_HIP(c, child.reserve(c->place_child.size() * 2, nullptr));
+    QS_HIP(c, next.reserve(c->place_next.size() * 2, nullptr));
+    QS_HIP(c, node.reserve(std::max<size_t>(R.inner_node.size(), 1) * 4, nullptr));
+    QS_HIP(c, hipMemcpyAsync(child.get(), c->place_child.data(), c->place_child.size() * 2, hipMemcpyHostToDevice, c->stream));
+    QS_HIP(c, hipMemcpyAsync(next.get(), c->place_next.data(), c->place_next.size() * 2, hipMemcpyHostToDevice, c->stream));
+    QS_HIP(c, hipMemcpyAsync(node.get(), R.inner_node.data(), R.inner_node.size() * 4, hipMemcpyHostToDevice, c->stream));
+    c->place_child_dev = std::move(child); c->place_next_dev = std::move(next); c->place_node_dev = std::move(node);
+    return QS_OK;
+}
+
+// Link sums of the quartet placement of the listed taxa (qs_place.hip). The reference never asks where the evaluation trees would
+// put a taxon: this replaces nothing there.
+extern "C" int qs_taxon_placement(qs_ctx *c, const qs_ref_tree *ref, const uint16_t *taxa, uint32_t n_list, int64_t *dst_device) {
+    if (!c) return QS_ERR_ARG;
+    if (!dst_device) return fail(c, QS_ERR_ARG, "qs_taxon_placement: NULL argument");
+    if (reinterpret_cast<uintptr_t>(dst_device) % 8) return fail(c, QS_ERR_ARG, "qs_taxon_placement: dst_device is not 8-byte aligned");
+    if (!c->table) return fail(c, QS_ERR_STATE, "qs_taxon_placement: no table");
+    // every sum is at most C(n-1,3) x (largest count): the trees behind the table if known, else what a cell can hold (as qs_taxon_support)
+    const uint64_t max_count = table_max_count(c);
+    const uint64_t per_taxon = c->n >= 4 ? (uint64_t)(c->n - 1) * (c->n - 2) / 2 * (c->n - 3) / 3 : 0;
+    if (per_taxon && max_count > (uint64_t)INT64_MAX / per_taxon)
+        return fail(c, QS_ERR_OVERFLOW, "qs_taxon_placement: C(n-1,3) x the largest possible count exceeds 63 bits");
+    if (c->d_lo != 0 || c->d_hi != c->n) return fail(c, QS_ERR_UNSUPPORTED, "qs_taxon_placement: a table-shard context (the walks of a taxon cross every shard: use a whole-table one)");
+    if (taxa ? n_list == 0 || n_list > c->n : n_list != c->n) return fail(c, QS_ERR_ARG, taxa ? "qs_taxon_placement: the list needs 1 .. n_taxa entries" : "qs_taxon_placement: n_list must be n_taxa when taxa is NULL");
+    std::vector<uint16_t> list(n_list);
+    {
+        std::vector<uint8_t> seen(c->n, 0);
+        for (uint32_t i = 0; i < n_list; ++i) {
+            const uint32_t x = taxa ? taxa[i] : i;
+            if (x >= c->n) return fail(c, QS_ERR_ARG, "qs_taxon_placement: taxon id out of range");
+            if (seen[x]) return fail(c, QS_ERR_ARG, "qs_taxon_placement: taxon id " + std::to_string(x) + " is listed twice");
+            seen[x] = 1; list[i] = (uint16_t)x;
+        }
+    }
+    QS_HIP(c, hipSetDevice(c->device));
+    const RefHost *Rp = nullptr;
+    if (int rc = get_ref(c, ref, true, &Rp)) return rc;
+    if (place_lds_bytes(Rp->n_nodes) > 160u * 1024u)
+        return fail(c, QS_ERR_UNSUPPORTED, "qs_taxon_placement: more than 10240 nodes (the link sums of a workgroup live in LDS)");
+    if (int rc = ensure_place_ref(c, *Rp)) return rc;
+    if (int rc = ensure_n_cu(c)) return rc;
+    if (!c->place_tasks_dev) {
+        // a walk = (middle id q, 64 consecutive largest ids): q steps; the long ones first
+        c->place_tasks.clear();
+        for (uint32_t q = c->n - 2; q >= 1; --q)
+            for (uint32_t g = 0; q + 1 + g * kWave < c->n; ++g) c->place_tasks.push_back(q | g << 16);
+        QS_HIP(c, c->place_tasks_dev.reserve(c->place_tasks.size() * 4, nullptr));
+        QS_HIP(c, hipMemcpyAsync(c->place_tasks_dev.get(), c->place_tasks.data(), c->place_tasks.size() * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    if (list != c->place_taxa || !c->place_taxa_dev) {
+        QS_HIP(c, hipStreamSynchronize(c->stream));   // (an earlier call's kernel and upload may still read the old list)
+        c->place_taxa = list;
+        QS_HIP(c, c->place_taxa_dev.reserve((size_t)c->n * 2, nullptr));
+        QS_HIP(c, hipMemcpyAsync(c->place_taxa_dev.get(), c->place_taxa.data(), (size_t)n_list * 2, hipMemcpyHostToDevice, c->stream));
+    }
+    PlaceDevice pd;
+    pd.ref_lca = c->ref_lca_dev.get(); pd.inner_node = c->place_node_dev.get(); pd.tasks = c->place_tasks_dev.get();
+    pd.child = c->place_child_dev.get(); pd.next = c->place_next_dev.get(); pd.taxa = c->place_taxa_dev.get();
+    pd.n = c->n; pd.n_nodes = Rp->n_nodes; pd.n_tasks = (uint32_t)c->place_tasks.size();
+    pd.table = c->table; pd.count_bits = (int)c->count_bits;   // the context's own table, not a scoring view
+    QS_HIP(c, hipMemsetAsync(dst_device, 0, (size_t)n_list * 2 * Rp->n_nodes * 8, c->stream));
+    // 32-bit partial sums: a walk has q < n_taxa steps, so 4096 x (largest count) < 2^32 suffices only while n_taxa <= 4096
+    // (qs_create's cap today; the LDS limit alone would allow more)
+    const bool wide = max_count >= (1ull << 32) / 4096 || c->n > 4096;
+    QS_HIP(c, launch_taxon_placement(c->stream, pd, n_list, wide, c->n_cu, reinterpret_cast<unsigned long long *>(dst_device)));
+    return QS_OK;   // asynchronous on the context's stream
+}
+
+// Link sums of the quartet placement of the listed clades (qs_place_clade.hip): the clade below a node is pruned and regrafted, unchanged
+// inside, on every edge outside it. The reference never asks where the evaluation trees would put a subtree: this replaces nothing there.
+extern "C" int qs_clade_placement(qs_ctx *c, const qs_ref_tree *ref, const uint32_t *nodes, uint32_t n_list, int64_t *dst_device) {
+    if (!c) return QS_ERR_ARG;
+    if (!dst_device) return fail(c, QS_ERR_ARG, "qs_clade_placement: NULL argument");
+    if (reinterpret_cast<uintptr_t>(dst_device) % 8) return fail(c, QS_ERR_ARG, "qs_clade_placement: dst_device is not 8-byte aligned");
+    if (!c->table) return fail(c, QS_ERR_STATE, "qs_clade_placement: no table");
+    if (!nodes || n_list == 0) return fail(c, QS_ERR_ARG, "qs_clade_placement: the list needs at least one node");
+    // the list against the tree's shape, before anything touches the device
+    const uint32_t n = c->n;
+    std::vector<uint32_t> lo(n_list), hi(n_list);
+    {
+        RefHost S;
+        if (int rc = build_ref_shape(c, ref, S)) return rc;
+        std::vector<uint8_t> seen(S.n_nodes, 0);
+        for (uint32_t i = 0; i < n_list; ++i) {
+            const uint32_t v = nodes[i];
+            if (v >= S.n_nodes) return fail(c, QS_ERR_ARG, "qs_clade_placement: node index out of range");
+            if (v == S.root) return fail(c, QS_ERR_ARG, "qs_clade_placement: the root is not a clade to move");
+            if (seen[v]) return fail(c, QS_ERR_ARG, "qs_clade_placement: node " + std::to_string(v) + " is listed twice");
+            seen[v] = 1;
+            lo[i] = S.leaf_lo[v]; hi[i] = lo[i] + S.leaf_cnt[v];
+            if (n - S.leaf_cnt[v] < 3) return fail(c, QS_ERR_ARG, "qs_clade_placement: node " + std::to_string(v) + " leaves fewer than three taxa outside it");
+        }
+    }
+    // every sum is at most |C| x C(n-|C|,3) x (largest count): the trees behind the table if known, else what a cell can hold (as qs_taxon_support)
+    const uint64_t max_count = table_max_count(c);
+    std::vector<uint64_t> cost(n_list);
+    for (uint32_t i = 0; i < n_list; ++i) {
+        const uint64_t s = hi[i] - lo[i], o = n - s;
+        cost[i] = s * (o * (o - 1) / 2 * (o - 2) / 3);        // (n <= 65535: below 2^62)
+        if (max_count > (uint64_t)INT64_MAX / cost[i])
+            return fail(c, QS_ERR_OVERFLOW, "qs_clade_placement: |C| x C(n-|C|,3) x the largest possible count exceeds 63 bits for node " + std::to_string(nodes[i]));
+    }
+    if (c->d_lo != 0 || c->d_hi != c->n) return fail(c, QS_ERR_UNSUPPORTED, "qs_clade_placement: a table-shard context (the walks of a clade cross every shard: use a whole-table one)");
+    if (place_lds_bytes(ref->n_nodes) > 160u * 1024u)
+        return fail(c, QS_ERR_UNSUPPORTED, "qs_clade_placement: more than 10240 nodes (the link sums of a workgroup live in LDS)");
+    QS_HIP(c, hipSetDevice(c->device));
+    const RefHost *Rp = nullptr;
+    if (int rc = get_ref(c, ref, true, &Rp)) return rc;
+    if (int rc = ensure_place_ref(c, *Rp)) return rc;
+    if (int rc = ensure_n_cu(c)) return rc;
+    if (!c->clade_tasks_dev) {
+        // a walk = (middle id, 64 consecutive largest ids) among the ids outside a clade, named by d = the outside ids above the middle
+        // one: a clade with `o` taxa outside owns the entries with d <= o - 2, and the smallest d are its longest walks
+        c->clade_tasks.clear();
+        for (uint32_t d = 1; d + 2 <= n; ++d)
+            for (uint32_t g = 0; g * kWave < d; ++g) c->clade_tasks.push_back(d | g << 16);
+        QS_HIP(c, c->clade_tasks_dev.reserve(std::max<size_t>(c->clade_tasks.size(), 1) * 4, nullptr));
+        QS_HIP(c, hipMemcpyAsync(c->clade_tasks_dev.get(), c->clade_tasks.data(), c->clade_tasks.size() * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    // per clade: its x-slices and its share of about eight workgroups per CU, in proportion to its tuples
+    // 32-bit register sums: a walk has at most n - |C| - 2 steps of `slice` tuples each, so (n - |C|) x slice x (largest count) < 2^32
+    // keeps them exact; slices are shortened to stay below, and the 64-bit instance takes over where that would cut a clade
+    // into slices of fewer than 16 taxa
+    bool wide = false;
+    for (uint32_t i = 0; i < n_list && !wide; ++i) {
+        const uint64_t s = hi[i] - lo[i], cap = 0xFFFFFFFFull / (max_count * (n - s));
+        wide = cap < std::min<uint64_t>(s, 16);
+    }
+    long double total_cost = 0;
+    for (uint64_t v : cost) total_cost += (long double)v;
+    const uint32_t budget = (uint32_t)c->n_cu * 8u;
+    std::vector<uint32_t> list((size_t)n_list * 4), groups;
+    for (uint32_t i = 0; i < n_list; ++i) {
+        const uint32_t s = hi[i] - lo[i], o = n - s;
+        uint64_t walks = 0;
+        for (uint32_t d = 1; d + 2 <= o; ++d) walks += (d + kWave - 1) / kWave;
+        uint32_t share = (uint32_t)std::min<long double>(65535.0L, std::max<long double>(1.0L, (long double)budget * (long double)cost[i] / total_cost + 0.5L));
+        // about four items per wave of the share, from slices of at least 16 taxa
+        uint64_t n_slices = std::max<uint64_t>(1, std::min<uint64_t>(s / 16, ((uint64_t)share * kPlaceWaves * 4 + walks - 1) / walks));
+        uint32_t slice = (uint32_t)((s + n_slices - 1) / n_slices);
+        if (!wide) slice = (uint32_t)std::min<uint64_t>(slice, 0xFFFFFFFFull / (max_count * o));
+        n_slices = (s + slice - 1) / slice;
+        share = (uint32_t)std::min<uint64_t>(share, (walks * n_slices + kPlaceWaves - 1) / kPlaceWaves);
+        list[4 * (size_t)i] = lo[i]; list[4 * (size_t)i + 1] = hi[i]; list[4 * (size_t)i + 2] = slice; list[4 * (size_t)i + 3] = (uint32_t)walks;
+        for (uint32_t k = 0; k < share; ++k) { groups.push_back(i); groups.push_back(k | share << 16); }
+    }
+    const uint32_t n_groups = (uint32_t)(groups.size() / 2);
+    list.insert(list.end(), groups.begin(), groups.end());
+    QS_HIP(c, hipStreamSynchronize(c->stream));   // (an earlier call's kernel and upload may still read the old lists)
+    c->clade_list = std::move(list);
+    QS_HIP(c, c->clade_list_dev.reserve(c->clade_list.size() * 4, nullptr));
+    QS_HIP(c, hipMemcpyAsync(c->clade_list_dev.get(), c->clade_list.data(), c->clade_list.size() * 4, hipMemcpyHostToDevice, c->stream));
+    CladeDevice cd;
+    cd.ref_lca = c->ref_lca_dev.get(); cd.inner_node = c->place_node_dev.get(); cd.tasks = c->clade_tasks_dev.get();
+    cd.clades = c->clade_list_dev.get(); cd.groups = cd.clades + (size_t)n_list * 4;
+    cd.child = c->place_child_dev.get(); cd.next = c->place_next_dev.get();
+    cd.n = c->n; cd.n_nodes = Rp->n_nodes;
+    cd.table = c->table; cd.count_bits = (int)c->count_bits;   // the context's own table, not a scoring view
+    QS_HIP(c, hipMemsetAsync(dst_device, 0, (size_t)n_list * 2 * Rp->n_nodes * 8, c->stream));
+    QS_HIP(c, launch_clade_placement(c->stream, cd, n_groups, wide, reinterpret_cast<unsigned long long *>(dst_device)));
+    return QS_OK;   // asynchronous on the context's stream
+}
+
+// Host-only: the link sums of one taxon -> the placement score of every edge, by the preorder recurrence S(v) = S(parent v) -
+// W[N + parent v] + W[v] with S(root) = the sum of W over all parent links. No device, no context.
+extern "C" int qs_placement_scores(const qs_ref_tree *ref, const int64_t *links_host, int64_t *scores_host) {
+    if (!links_host || !scores_host) return fail(nullptr, QS_ERR_ARG, "qs_placement_scores: NULL argument");
+    RefHost R;
+    if (int rc = build_ref_shape(nullptr, ref, R)) return rc;
+    const uint32_t N = R.n_nodes;
+    std::vector<uint32_t> order(N);
+    for (uint32_t v = 0; v < N; ++v) order[v] = v;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return R.depth[a] < R.depth[b]; });   // parents first
+    int64_t tot_up = 0;
+    for (uint32_t v = 0; v < N; ++v) tot_up += links_host[N + v];
+    scores_host[R.root] = tot_up;
+    for (uint32_t v : order) {
+        if (v == R.root) continue;
+        const uint32_t p = (uint32_t)R.parent[v];
+        scores_host[v] = scores_host[p] - links_host[N + p] + links_host[v];
+    }
+    scores_host[R.root] = 0;
+    return QS_OK;
+}
+
+// Per-tree quartet agreement of a batch with the reference tree (qs_agree.hip). The reference's links come from its depth-first id
+// order: the children of an inner node split its id interval, ordered by their first id, and its parent link holds the other ids.
+// The reference has no per-tree output: this replaces nothing there.
+static int agree_ref_upload(qs_ctx *c, const qs_ref_tree *ref) {
+    if (!ref || !ref->parent || !ref->leaf_node) return fail(c, QS_ERR_ARG, "qs_tree_agreement: NULL reference arrays");
+    if (ref->n_taxa != c->n) return fail(c, QS_ERR_ARG, "qs_tree_agreement: the reference tree's n_taxa differs from the context");
+    const uint32_t N = ref->n_nodes, n = ref->n_taxa;
+    if (c->agree_off && c->agree_parent.size() == N && c->agree_leaf_node.size() == n &&
+        memcmp(c->agree_parent.data(), ref->parent, (size_t)N * 4) == 0 && memcmp(c->agree_leaf_node.data(), ref->leaf_node, (size_t)n * 4) == 0)
+        return QS_OK;
+    RefHost R;
+    if (int rc = build_ref_shape(c, ref, R)) return rc;
+    // children of every node in id order
+    std::vector<std::vector<uint32_t>> kids(N);
+    for (uint32_t v = 0; v < N; ++v)
+        if (R.parent[v] >= 0 && R.leaf_cnt[v]) kids[R.parent[v]].push_back(v);
+    std::vector<uint32_t> off{0};
+    std::vector<uint16_t> bnd;
+    std::vector<uint8_t> par;
+    for (uint32_t u = 0; u < N; ++u) {
+        std::vector<uint32_t> &ks = kids[u];
+        const uint32_t has_parent = R.parent[u] >= 0 ? 1u : 0u;
+        if (ks.size() + has_parent < 3) continue;
+        std::sort(ks.begin(), ks.end(), [&](uint32_t x, uint32_t y) { return R.leaf_lo[x] < R.leaf_lo[y]; });
+        for (uint32_t v : ks) bnd.push_back((uint16_t)R.leaf_lo[v]);
+        bnd.push_back((uint16_t)(R.leaf_lo[ks.back()] + R.leaf_cnt[ks.back()]));
+        off.push_back((uint32_t)bnd.size());
+        par.push_back((uint8_t)has_parent);
+    }
+    QS_HIP(c, hipSetDevice(c->device));
+    QS_HIP(c, hipStreamSynchronize(c->stream));   // kernels of this context may still read the previous tree's arrays
+    // The cache key goes BEFORE the first buffer: whatever fails below, the next call finds no tree cached and builds all three anew.
+    c->agree_parent.clear(); c->agree_leaf_node.clear();
+    c->agree_off.reset(); c->agree_bnd.reset(); c->agree_par.reset();   // (each tree gets arrays of its own size, as before)
+    QS_HIP(c, c->agree_off.reserve(off.size() * 4, nullptr));
+    QS_HIP(c, c->agree_bnd.reserve(std::max<size_t>(bnd.size(), 1) * 2, nullptr));
+    QS_HIP(c, c->agree_par.reserve(std::max<size_t>(par.size(), 1), nullptr));
+    QS_HIP(c, hipMemcpy(c->agree_off.get(), off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    if (!bnd.empty()) QS_HIP(c, hipMemcpy(c->agree_bnd.get(), bnd.data(), bnd.size() * 2, hipMemcpyHostToDevice));
+    if (!par.empty()) QS_HIP(c, hipMemcpy(c->agree_par.get(), par.data(), par.size(), hipMemcpyHostToDevice));
+    c->agree_n_u = (uint32_t)par.size();
+    c->agree_parent.assign(ref->parent, ref->parent + N);
+    c->agree_leaf_node.assign(ref->leaf_node, ref->leaf_node + n);
+    return QS_OK;
+}
+
+extern "C" int qs_tree_agreement(qs_ctx *c, const qs_ref_tree *ref, const qs_device_batch *b, uint64_t *dst_device) {
+    if (!c) return QS_ERR_ARG;
+    if (!b || !dst_device) return fail(c, QS_ERR_ARG, "qs_tree_agreement: NULL argument");
+    if (c->d_lo != 0 || c->d_hi != c->n)
+        return fail(c, QS_ERR_UNSUPPORTED, "qs_tree_agreement: whole-table contexts only (no table shards)");
+    if (reinterpret_cast<uintptr_t>(dst_device) % 8) return fail(c, QS_ERR_ARG, "qs_tree_agreement: dst_device is not 8-byte aligned");
+    if (int rc = agree_ref_upload(c, ref)) return rc;
+    const DeviceBatch &d = b->d;
+    if (d.n_trees && !d.node_off) return fail(c, QS_ERR_STATE, "qs_tree_agreement: the batch was uploaded without node ranges");
+    QS_HIP(c, hipSetDevice(c->device));
+    if (d.ready) QS_HIP(c, hipStreamWaitEvent(c->stream, d.ready, 0));
+    QS_HIP(c, launch_tree_agree(c->stream, d, c->n, d.max_tree_nodes, c->agree_off.get(), c->agree_bnd.get(), c->agree_par.get(), c->agree_n_u,
+                                reinterpret_cast<unsigned long long *>(dst_device)));
+    return QS_OK;   // asynchronous on the context's stream
+}

@@ -755,7 +755,7 @@ __global__ __launch_bounds__(kCountThreads) __attribute__((amdgpu_waves_per_eu(b
 // answered without touching the L1) runs 12 % faster while changing the tile order for better L2 hits changes nothing
 // (profiles/r03_experiments.md). This kernel cuts the requests themselves. The four waves of a workgroup take four
 // tiles with the SAME a-blocks, b-block and d-block and consecutive third ids c (the host builds that launch order:
-// tile_order in qs_abi.hip, groups padded with "shadow" tiles that compute but do not store). Of a wave's 216 panel
+// tile_order in qs_abi_count.hip, groups padded with "shadow" tiles that compute but do not store). Of a wave's 216 panel
 // elements per step only M[c,d] (8) and M[x,c] (16) depend on c; M[ab] (2 x 64) and M[bd] (64) are identical for the
 // whole workgroup. So per step
 //   wave w < 3 loads ONE of the three shared sets (one element per lane), every wave its own 24 private elements,
@@ -1122,7 +1122,7 @@ hipError_t launch_count_scatter(hipStream_t s, const DeviceBatch &b, uint32_t n,
 // can be counted in the B-bit class with every depth cut at 2^B - 1 (the panel builders do that), at the price of the
 // quartets the cut ties: exactly those with at least THREE leaves below one node of depth 2^B - 1 -- in centred random
 // trees a handful of small subtrees (512 taxa: 76 % of the trees need 5 bits, median 5 600 such quartets of 2.8e9 per
-// tree). In the tour arrays such a subtree is a maximal run of adjacent-LCA depths >= 2^B - 1 (qs_abi.hip plan_depth_clamp
+// tree). In the tour arrays such a subtree is a maximal run of adjacent-LCA depths >= 2^B - 1 (qs_plan.hip plan_depth_clamp
 // finds them and decides per tree whether the cut pays). This kernel adds what the cut lost: for every triple (i < j < k)
 // of a run and every fourth leaf -- outside the run: the triple's cherry pairs up, the topology follows from the two
 // adjacent LCA depths of the triple alone; inside the run behind k: the four-point rule on the three adjacent depths --

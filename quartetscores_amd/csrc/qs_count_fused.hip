@@ -1,6 +1,6 @@
 // qs_count_fused.hip -- the classes of a mixed batch in ONE launch of the bit-sliced count kernel.
 //
-// A batch is counted class by class (class = kernel mode x depth bits per TREE, qs_abi.hip plan_classes): full binary trees,
+// A batch is counted class by class (class = kernel mode x depth bits per TREE, qs_plan.hip plan_classes): full binary trees,
 // binary trees with missing taxa, multifurcating trees and trees with both take different 32-tree steps (2(B+1)+2 ... 3(B+1)+7
 // instructions per quartet). With one launch per class every class costs a pass over the table (34 GB at 512 taxa: the first
 // stores it, every further one reads and writes it) plus the fixed cost of ~3 M waves (tile decode, prologue, epilogue): 25 ms

@@ -1,4 +1,4 @@
-// qs_devbuf.hpp -- the one owner of device and pinned-host memory in the host code (qs_abi.hip).
+// qs_devbuf.hpp -- the one owner of device and pinned-host memory in the host code (the C-ABI layer, qs_ctx.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,4 +1,4 @@
-// qs_internal.hpp -- launcher interface between the C-ABI layer (qs_abi.hip) and the kernels.
+// qs_internal.hpp -- launcher interface between the C-ABI layer (qs_abi*.hip, qs_plan.hip) and the kernels.
 #pragma once
 #include <vector>
 
@@ -77,7 +77,7 @@ struct DeviceBatch {
     uint32_t *node_off = nullptr, *rng_off = nullptr, *node_tree = nullptr;
     uint16_t *ranges = nullptr;
     uint32_t max_tree_nodes = 0;    // most inner nodes of one tree (qs_tree_agreement's grid)
-    // depth clamp (qs_abi.hip plan_depth_clamp): the correction units of the trees counted in a class below their own depth bits,
+    // depth clamp (qs_plan.hip plan_depth_clamp): the correction units of the trees counted in a class below their own depth bits,
     // ordered by the tree's slot in the class-ordered batch (qs_device_batch::fix_slot = that slot per unit, host)
     FixUnit *fix_units = nullptr;   // device
     uint32_t n_fix = 0;
@@ -95,7 +95,7 @@ struct CountGeometry {
     uint32_t total_tiles;
     const uint32_t *dprefix; // device, n_dblk+1
     const uint32_t *cprefix; // device, n+1
-    const uint32_t *perm = nullptr; // device, total_tiles: launch slot -> tile id (nullptr = identity); see qs_abi.hip tile_order
+    const uint32_t *perm = nullptr; // device, total_tiles: launch slot -> tile id (nullptr = identity); see qs_abi_count.hip tile_order
     // binary_full tiling only: the launch order split for count_bitslice4_kernel. perm_coop: n_coop slots (a multiple of 4;
     // every aligned group of 4 = tiles of one (a-blocks, b-block, d-block), bit 31 = shadow tile that must not store);
     // perm_rest: the n_rest tiles count_bitslice3_kernel still runs. NULL / 0 = everything through count_bitslice3_kernel.
@@ -235,7 +235,7 @@ hipError_t launch_score_pass1(hipStream_t s, const ScoreDevice &sd, int kernel, 
 hipError_t launch_score_log(hipStream_t s, const ScoreDevice &sd, double tol, unsigned long long n_rec); // single-read scoring: filter pass 1's candidate log (sd.list)
 hipError_t launch_score_pass2(hipStream_t s, const ScoreDevice &sd, double tol, int kernel, int n_cu, const uint64_t *part_lo, const uint64_t *part_n, int n_parts);
 hipError_t launch_score_overflow_list(hipStream_t s, const ScoreDevice &sd, double tol);
-// sums of the node pairs (degree-2 root, v): pairs_dev = RootPairHost records (qs_abi.hip), total = number of (v,a,b,c,d) items
+// sums of the node pairs (degree-2 root, v): pairs_dev = RootPairHost records (qs_abi_score.hip), total = number of (v,a,b,c,d) items
 struct RootPairHost { uint32_t s1_lo, s1_n, s2_lo, s2_n, s3_lo, s3_n, s4_lo, s4_n, key, pad; unsigned long long first; };
 hipError_t launch_root_pair_sums(hipStream_t s, const ScoreDevice &sd, const void *pairs_dev, uint32_t n_pairs, uint64_t total);
 hipError_t launch_raw_qic(hipStream_t s, const ScoreDevice &sd, uint64_t r0, uint64_t nq, uint8_t *topo_dev,

@@ -202,7 +202,7 @@ def scores_from_table(ref, T, qp_exact64=False):
     return np.array(lq), np.array(qp), np.array(eqp)
 
 
-# ---- depth clamp of the bit-sliced count classes (qs_abi.hip plan_depth_clamp, qs_count.hip clamp_fix_kernel) ----
+# ---- depth clamp of the bit-sliced count classes (qs_plan.hip plan_depth_clamp, qs_count.hip clamp_fix_kernel) ----
 
 def clamp_runs(adj_depth, L, clamp):
     """Maximal runs of tour-adjacent LCA depths >= clamp: (first leaf position, leaves) of every subtree whose root sits at

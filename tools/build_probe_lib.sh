@@ -2,14 +2,11 @@
 # A/B builds of the count kernels with other compile-time switches, next to the product library (never loaded unless the Python
 # harness is told to: QS_PY_LIB=<path>; the library itself reads no environment):
 #   tools/build_probe_lib.sh <name> "<extra hipcc flags>"   ->  quartetscores_amd/lib/libqs_probe_<name>.so
+# What makes up the library is csrc/Makefile's list; only the two count-kernel files are compiled with the flags.
 set -e
 name=${1:?name}; flags=${2:-}
 cd "$(dirname "$0")/../quartetscores_amd/csrc"
 tmp=$(mktemp -d)
-for f in qs_count qs_count_fused; do
-  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wextra -Wno-unused-parameter $flags -c $f.hip -o $tmp/$f.o &
-done
-wait
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../lib/libqs_probe_$name.so $tmp/qs_count.o $tmp/qs_count_fused.o qs_score.o qs_abi.o
-rm -rf $tmp
+trap 'rm -rf "$tmp"' EXIT
+make -j4 OBJDIR="$tmp" OUT=../lib/libqs_probe_$name.so EXTRA_SRCS="qs_count.hip qs_count_fused.hip" EXTRA_HIPFLAGS="$flags"
 ls -la ../lib/libqs_probe_$name.so
