@@ -20,6 +20,8 @@
  *   qs_tree_agreement             replaces nothing in the reference (it reports no per-tree agreement)
  *   qs_taxon_support              replaces nothing in the reference (the nearest is printRawQICScores, :612-680: one text
  *                                 line per quartet, which a user would reduce per taxon on the host)
+ *   qs_group_check /              replace nothing in the reference; the nearest is the metaquartet sum of processNodePair
+ *   qs_group_support              (QuartetScoreComputer.hpp:379-472), which knows only the four subtrees beside a node pair of the tree
  *   qs_taxon_placement /          replace nothing in the reference (it never asks where the evaluation trees would put a taxon; the
  *   qs_placement_scores           nearest route is one more reference tree and one more run per candidate position)
  *   qs_clade_placement            replaces nothing in the reference (it never asks where the evaluation trees would put a subtree)
@@ -375,6 +377,31 @@ int qs_tree_agreement(qs_ctx *ctx, const qs_ref_tree *ref, const qs_device_batch
  * QS_TUNE_TABLE_TREES -- if known, else the largest count a cell holds) exceeds 63 bits; QS_ERR_UNSUPPORTED = more than 3413 taxa
  * (table-shard contexts only; a whole table ends at 2259). Asynchronous on the context's stream. */
 int qs_taxon_support(qs_ctx *ctx, const qs_ref_tree *ref, int64_t *dst_device);
+
+/* Quartet support of user-defined taxon groups from the count table: how often do the evaluation trees show each resolution around a
+ * branch the caller names -- whether or not any reference tree has it. Replaces nothing in the reference; the nearest is the metaquartet
+ * sum of processNodePair. A hypothesis labels every taxon (lookup id) with 0..4, 0 = takes no part; labels = host array
+ * [n_hyp][n_taxa], lent for the call.
+ *   quad  (labels 1, 2, 3, 4 all occur): asserts S1 S2 | S3 S4. Counted: the 4-sets with one taxon of each label, a in S1, b in S2,
+ *         c in S3, d in S4; q1 = n(ab|cd), q2 = n(ac|bd), q3 = n(ad|bc).
+ *   split (only labels 1 and 2, each on at least two taxa): asserts S1 | S2. Counted: the 4-sets with two taxa of each label,
+ *         g1 < g2 in S1, h1 < h2 in S2 by lookup id; q1 = n(g1g2|h1h2), q2 = n(g1h1|g2h2), q3 = n(g1h2|g2h1). How the discordant
+ *         counts divide into q2 and q3 follows the id order and means nothing; only q2 + q3 does.
+ * Per hypothesis six exact words over the 4-sets of THIS context's table (whole table or [d_lo, d_hi) shard: the caller adds the shards):
+ *   k = 0 quartets  4-sets counted       k = 3 F3          sum of q3
+ *   k = 1 F1        sum of q1            k = 4 outvoted    4-sets with max(q2,q3) > q1
+ *   k = 2 F2        sum of q2            k = 5 uninformed  4-sets with q1+q2+q3 = 0
+ * independent of grid, order and the way hypotheses are batched (one read of the table serves eight of them).
+ * qs_group_check is host-only (no device, no context; the message of a failure comes from qs_last_error(NULL)): kind_out[h] = 0 quad,
+ * 1 split; quartets_out[h] = the whole-table number of counted 4-sets, |S1||S2||S3||S4| or C(|S1|,2) C(|S2|,2); either may be NULL.
+ * qs_group_support: dst_device (caller-owned device memory, 8-byte aligned, [n_hyp][6] words) is OVERWRITTEN. Asynchronous on the
+ * context's stream; changes neither the table nor trees-counted nor a pending score log; a scoring view is not looked at; needs no
+ * reference tree.
+ * Errors: QS_ERR_STATE = no table; QS_ERR_ARG = NULL or misaligned pointer, n_hyp = 0, a label > 4, a pattern that is neither quad nor
+ * split (the message names the hypothesis and what is missing); QS_ERR_OVERFLOW = (whole-table number of counted 4-sets) x (the trees
+ * behind the table -- counted, or QS_TUNE_TABLE_TREES -- if known, else the largest count a cell holds) exceeds 63 bits. */
+int qs_group_check(uint32_t n_taxa, const uint8_t *labels, uint32_t n_hyp, uint8_t *kind_out, uint64_t *quartets_out);
+int qs_group_support(qs_ctx *ctx, const uint8_t *labels, uint32_t n_hyp, int64_t *dst_device);
 
 /* Quartet placement of taxa on the reference tree from the count table: where would the evaluation trees put taxon x? With x attached
  * on an edge e of the reference tree T without x, the placement score of e is the sum, over the 4-sets {x,p,q,r}, of the count of the

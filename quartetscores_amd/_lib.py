@@ -39,7 +39,7 @@ EXPORTS = [
     "qs_score_plan", "qs_last_score_ms", "qs_prepare", "qs_table_pack32x2", "qs_unpack32x2", "qs_last_score_log", "qs_last_score_estimate", "qs_score_prepare",
     "qs_sum_words", "qs_issue_probe", "qs_last_count_fix_ms", "qs_batch_clamp_info", "qs_depth_clamp_plan", "qs_score_check", "qs_last_count_events", "qs_class_plan", "qs_shard_bounds",
     "qs_table_remap", "qs_tree_agreement", "qs_taxon_support", "qs_table_restrict", "qs_taxon_placement", "qs_placement_scores", "qs_clade_placement",
-    "qs_last_count_split", "qs_fix_overlap_plan",
+    "qs_last_count_split", "qs_fix_overlap_plan", "qs_group_check", "qs_group_support",
 ]
 
 
@@ -121,6 +121,10 @@ def load():
     L.qs_placement_scores.argtypes = [vp, vp, vp]
     L.qs_clade_placement.restype = i32
     L.qs_clade_placement.argtypes = [vp, vp, vp, u32, vp]
+    L.qs_group_check.restype = i32
+    L.qs_group_check.argtypes = [u32, vp, u32, vp, vp]
+    L.qs_group_support.restype = i32
+    L.qs_group_support.argtypes = [vp, vp, u32, vp]
     L.qs_sum_words.restype = i32
     L.qs_sum_words.argtypes = [vp, vp, vp, u32, u64]
     L.qs_table_device_ptr.restype = vp

@@ -18,6 +18,9 @@
 // score of each edge as a position of the taxon, from the same count table (qs_taxon_placement, qs_placement_scores).
 // --place-clades FILE [--place-clades-only SPEC] does the same for whole clades of the -r tree, pruned and regrafted unchanged inside
 // (qs_clade_placement, qs_placement_scores).
+// --test-groups SPEC FILE writes how often the evaluation trees show each of the three resolutions around branches the user names as
+// taxon groups -- four groups S1 S2 | S3 S4 or a bipartition S1 | S2 --, whether or not the -r tree has them, from the same count
+// table (qs_group_check, qs_group_support).
 #include "QuartetScoreComputer.hpp"
 #include "multi_gpu.hpp"
 #include "table_shards.hpp"
@@ -77,6 +80,9 @@ struct Args {
     std::string place_clades;      // --place-clades FILE: quartet placement of the clades of -r from the count table (TSV)
     std::string place_clades_only; // --place-clades-only SPEC: a file of the clades to place, one per line (default: every eligible inner clade)
     std::vector<uint32_t> place_nodes; // the nodes to place, in output order (check_place_clades)
+    std::string test_groups_spec, test_groups;   // --test-groups SPEC FILE: quartet support of the taxon groups of SPEC from the count table (TSV)
+    std::vector<std::string> group_names;        // the hypotheses of SPEC in its order (check_test_groups): name, labels [hypothesis][taxon], kind
+    std::vector<uint8_t> group_labels, group_kind;
     std::vector<AlsoRef> also;
     std::vector<WithoutTaxa> without;
     size_t threads = 0;
@@ -165,7 +171,22 @@ void usage(std::ostream &os) {
           "                  beside the other outputs (always the full -r tree)\n"
           "   --place-clades-only SPEC  with --place-clades: place only the clades of SPEC, in its order: one clade per line, given as one\n"
           "                  or more labels separated by tabs = the smallest subtree of the -r tree, as rooted in its file, that holds\n"
-          "                  them all (one label: that leaf)\n";
+          "                  them all (one label: that leaf)\n"
+          "   --test-groups SPEC F  write the quartet support of user-defined taxon groups to F (TSV, one line per hypothesis of SPEC in\n"
+          "                  its order after a header: name kind quartets q1 q2 q3 outvoted uninformed support qpic). SPEC holds one\n"
+          "                  hypothesis per line (blank lines and lines that start with # are skipped): NAME<TAB>G1<TAB>G2<TAB>G3<TAB>G4\n"
+          "                  asserts the branch G1 G2 | G3 G4 (kind quad), NAME<TAB>G1<TAB>G2 the bipartition G1 | G2 (kind split); a\n"
+          "                  group is a comma-separated list of leaf labels of the -r tree, the groups of a line share no label, and one\n"
+          "                  group of a split may be * = every taxon the other group does not name (is the named group monophyletic?).\n"
+          "                  Labels that contain a tab or a comma cannot be named. quartets = the 4-sets with one taxon of each group\n"
+          "                  (split: two of either); q1 = how often the evaluation trees show the asserted resolution of them, q2 and q3\n"
+          "                  the two others; outvoted = 4-sets where another resolution is the most frequent, uninformed = 4-sets no\n"
+          "                  tree resolves; support = q1 / (q1 + q2 + q3); qpic = the QP-IC of (q1, q2, q3), for the four subtrees beside\n"
+          "                  an edge of a binary -r tree that edge's qp-ic with --exact-qp. In a split line the division of the\n"
+          "                  discordant counts into q2 and q3 follows the order of the taxa in the -r tree and means nothing (only\n"
+          "                  q2 + q3 does), and qpic is nan. The groups need not be clades of any tree; one more read of the table on the\n"
+          "                  device per eight hypotheses; one GPU with the whole table (not with --gpus / --table-shards); works with\n"
+          "                  --load-table and beside every other output\n";
 }
 
 // returns 0 ok, 1 error (message printed like the reference prints TCLAP::ArgException), 2 exit quietly
@@ -242,6 +263,14 @@ int parse(int argc, char **argv, Args &a) {
         else if (f == "--place-only") { if (!(v = need(i, "--place-only"))) return 1; a.place_only = v; }
         else if (f == "--place-clades") { if (!(v = need(i, "--place-clades"))) return 1; a.place_clades = v; }
         else if (f == "--place-clades-only") { if (!(v = need(i, "--place-clades-only"))) return 1; a.place_clades_only = v; }
+        else if (f == "--test-groups") {
+            if (i + 2 >= argc) {
+                std::cerr << "ERROR: Missing a value for this argument! for arg --test-groups (it takes two: SPEC FILE)" << std::endl;
+                return 1;
+            }
+            a.test_groups_spec = argv[++i];
+            a.test_groups = argv[++i];
+        }
         else if (f == "--load-table") { if (!(v = need(i, "--load-table"))) return 1; a.dev.load_table = v; }
         else if (f == "--also-ref") {
             if (i + 2 >= argc || argv[i + 2][0] == '-') {
@@ -758,6 +787,107 @@ void score_without_taxa(const Args &a, qs_ctx *src, const RefFlat &primary, uint
     }
 }
 
+// --test-groups: everything that needs no GPU, before the device is touched -- the whole table is on one GPU, FILE neither exists nor is
+// another output, every line of SPEC parses against the labels of -r, and qs_group_check accepts the patterns; leaves the hypotheses in
+// a.group_names / a.group_labels / a.group_kind
+void check_test_groups(Args &a) {
+    if (a.test_groups.empty()) return;
+    if (a.gpus > 0 || a.table_shards >= 0)
+        throw std::runtime_error("--test-groups needs the whole count table on one GPU: omit --gpus / --table-shards");
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.place_clades};
+    for (const AlsoRef &x : a.also) others.insert(x.out);
+    for (const WithoutTaxa &x : a.without) others.insert(x.out);
+    if (others.count(a.test_groups)) throw std::runtime_error("--test-groups: " + a.test_groups + " is also another output file");
+    if (std::ifstream(a.test_groups).good()) throw std::runtime_error("--test-groups: the output file " + a.test_groups + " already exists");
+    Tree primary;
+    {
+        const std::string text = slurp(a.ref);
+        NewickReader rr(text);
+        if (!rr.next(primary)) throw std::runtime_error("empty reference tree file");
+    }
+    const RefFlat rf = flatten_reference(primary);
+    const size_t n = rf.names.size();
+    auto trimmed = [](const std::string &t) {
+        const size_t b = t.find_first_not_of(" \r"), e = t.find_last_not_of(" \r");
+        return b == std::string::npos ? std::string() : t.substr(b, e - b + 1);
+    };
+    std::istringstream lines(slurp(a.test_groups_spec));
+    size_t line_no = 0;
+    for (std::string line; std::getline(lines, line);) {
+        ++line_no;
+        const std::string what = "--test-groups " + a.test_groups_spec + " line " + std::to_string(line_no) + ": ";
+        const size_t first = line.find_first_not_of(" \t\r");
+        if (first == std::string::npos || line[first] == '#') continue;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        std::vector<std::string> cols;
+        for (size_t at = 0;;) {
+            const size_t tab = line.find('\t', at);
+            cols.push_back(line.substr(at, tab == std::string::npos ? std::string::npos : tab - at));
+            if (tab == std::string::npos) break;
+            at = tab + 1;
+        }
+        if (cols.size() != 3 && cols.size() != 5)
+            throw std::runtime_error(what + "a hypothesis needs a name and two or four groups, found " + std::to_string(cols.size() - 1) + " group(s)");
+        std::vector<uint8_t> row(n, 0);
+        size_t star = 0, stars = 0;
+        for (size_t k = 1; k < cols.size(); ++k)
+            if (trimmed(cols[k]) == "*") { star = k; ++stars; }
+        if (stars && (cols.size() != 3 || stars > 1)) throw std::runtime_error(what + "'*' may stand for one group of a split only");
+        for (size_t k = 1; k < cols.size(); ++k) {
+            if (k == star) continue;
+            if (trimmed(cols[k]).empty()) throw std::runtime_error(what + "group " + std::to_string(k) + " is empty");
+            std::istringstream members(cols[k]);
+            for (std::string member; std::getline(members, member, ',');) {
+                const std::string name = trimmed(member);
+                const auto it = rf.name_to_id.find(name);
+                if (it == rf.name_to_id.end()) throw std::runtime_error(what + "unknown taxon '" + name + "' in group " + std::to_string(k) + " (not in the reference tree " + a.ref + ")");
+                if (row[it->second]) throw std::runtime_error(what + "taxon '" + name + "' is in two groups (or twice in one)");
+                row[it->second] = (uint8_t)k;
+            }
+        }
+        if (star) for (uint8_t &l : row) if (!l) l = (uint8_t)star;
+        if (cols.size() == 3)
+            for (uint8_t k = 1; k <= 2; ++k) {
+                const size_t members = (size_t)std::count(row.begin(), row.end(), k);
+                if (members == 0) throw std::runtime_error(what + "group " + std::to_string(k) + " is empty");
+                if (members < 2) throw std::runtime_error(what + "group " + std::to_string(k) + " of a split needs at least two taxa");
+            }
+        a.group_names.push_back(cols[0]);
+        a.group_labels.insert(a.group_labels.end(), row.begin(), row.end());
+    }
+    if (a.group_names.empty()) throw std::runtime_error("--test-groups " + a.test_groups_spec + ": no hypothesis in the file");
+    a.group_kind.assign(a.group_names.size(), 0);
+    if (qs_group_check((uint32_t)n, a.group_labels.data(), (uint32_t)a.group_names.size(), a.group_kind.data(), nullptr) != QS_OK)
+        throw std::runtime_error("--test-groups " + a.test_groups_spec + ": " + qs_last_error(nullptr));
+}
+
+// --test-groups: one qs_group_support over the counted (or loaded) table, 6 words per hypothesis downloaded, one TSV line each
+void write_test_groups(qs_ctx *ctx, int device, const Args &a) {
+    const size_t H = a.group_names.size();
+    qs::DevBuf<int64_t> dev;
+    if (hipSetDevice(device) != hipSuccess || dev.reserve(6 * H * 8, nullptr) != hipSuccess) throw std::runtime_error("--test-groups: Insufficient memory!");
+    if (qs_group_support(ctx, a.group_labels.data(), (uint32_t)H, dev.get()) != QS_OK || qs_sync(ctx) != QS_OK)
+        throw std::runtime_error(std::string("--test-groups: ") + qs_last_error(ctx));
+    std::vector<int64_t> w(6 * H);
+    if (hipMemcpy(w.data(), dev.get(), 6 * H * 8, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("--test-groups: download failed");
+    std::ofstream f(a.test_groups);
+    if (!f) throw std::runtime_error("cannot write " + a.test_groups);
+    f << "name\tkind\tquartets\tq1\tq2\tq3\toutvoted\tuninformed\tsupport\tqpic\n";
+    char support[64], qpic[64];
+    for (size_t h = 0; h < H; ++h) {
+        const int64_t *v = &w[6 * h];
+        const bool split = a.group_kind[h] != 0;
+        if (v[1] + v[2] + v[3]) std::snprintf(support, sizeof support, "%.6f", (double)v[1] / (double)(v[1] + v[2] + v[3]));
+        else std::snprintf(support, sizeof support, "nan");
+        if (split) std::snprintf(qpic, sizeof qpic, "nan");
+        else std::snprintf(qpic, sizeof qpic, "%.6f", raw_log_score((size_t)v[1], (size_t)v[2], (size_t)v[3]));
+        f << a.group_names[h] << '\t' << (split ? "split" : "quad");
+        for (int k = 0; k < 6; ++k) f << '\t' << v[k];
+        f << '\t' << support << '\t' << qpic << '\n';
+    }
+    if (!f) throw std::runtime_error("cannot write " + a.test_groups);
+}
+
 // --gpus N: trees split over N GPUs, one collective on the table, sharded scoring (multi_gpu.hpp)
 void run_multi(const Tree &referenceTree, const Args &a, size_t m, uint32_t count_bits, std::vector<double> &lqic,
                std::vector<double> &qpic, std::vector<double> &eqpic) {
@@ -866,6 +996,7 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
     if (!a.per_taxon.empty()) write_per_taxon(qsc.context(), qsc.reference(), a.dev.device, a.per_taxon);
     if (!a.place_taxa.empty()) write_place_taxa(qsc.context(), qsc.reference(), a.dev.device, a.place_taxa, a.place_ids);
     if (!a.place_clades.empty()) write_place_clades(qsc.context(), qsc.reference(), a.dev.device, a.place_clades, a.place_nodes);
+    if (!a.test_groups.empty()) write_test_groups(qsc.context(), a.dev.device, a);
     if (!a.also.empty() || !a.without.empty()) {   // the primary tree's output first, exactly as without --also-ref / --without-taxa
         write_annotated(referenceTree, a.out, lqic, qpic, eqpic);
         score_also_refs(a, qsc.context(), qsc.reference(), also_table);
@@ -896,6 +1027,7 @@ int main(int argc, char *argv[]) {
         check_per_taxon(a);
         check_place_taxa(a);
         check_place_clades(a);
+        check_test_groups(a);
     } catch (const std::exception &e) {
         std::cerr << "ERROR: " << e.what() << std::endl;
         return 1;

@@ -1,6 +1,8 @@
-// qs_abi_query.hip -- what reads a finished table against a reference tree and is not the score: per-taxon support, taxon and clade
-// placement, per-tree agreement. Host code only; the kernels are in qs_taxon.hip, qs_place.hip, qs_place_clade.hip and qs_agree.hip.
+// qs_abi_query.hip -- what reads a finished table and is not the score: per-taxon support, taxon and clade placement, per-tree
+// agreement (against a reference tree) and the support of taxon groups (against none). Host code only; the kernels are in qs_taxon.hip,
+// qs_place.hip, qs_place_clade.hip, qs_agree.hip and qs_groups.hip.
 #include "qs_ctx.hpp"
+#include "qs_plan.hpp"
 
 #include <algorithm>
 #include <cstdint>
@@ -36,6 +38,64 @@ extern "C" int qs_taxon_support(qs_ctx *c, const qs_ref_tree *ref, int64_t *dst_
     QS_HIP(c, hipMemsetAsync(dst_device, 0, (size_t)c->n * 6 * 8, c->stream));
     const bool wide = max_count >= (1ull << 32) / 192;   // 64 lanes x 3 counts in a 32-bit partial sum
     QS_HIP(c, launch_taxon_support(c->stream, sd, wide, c->n_cu, reinterpret_cast<unsigned long long *>(dst_device)));
+    return QS_OK;   // asynchronous on the context's stream
+}
+
+// Host-only: kind and whole-table number of counted 4-sets of every hypothesis, or the first malformed one (qs_plan.hip group_classify).
+extern "C" int qs_group_check(uint32_t n_taxa, const uint8_t *labels, uint32_t n_hyp, uint8_t *kind_out, uint64_t *quartets_out) {
+    if (!labels) return fail(nullptr, QS_ERR_ARG, "qs_group_check: NULL argument");
+    if (n_hyp == 0) return fail(nullptr, QS_ERR_ARG, "qs_group_check: n_hyp must be at least 1");
+    if (n_taxa < 4 || n_taxa > 65535) return fail(nullptr, QS_ERR_ARG, "qs_group_check: n_taxa must be 4 .. 65535");
+    std::string err;
+    if (!group_classify(n_taxa, labels, n_hyp, kind_out, quartets_out, err)) return fail(nullptr, QS_ERR_ARG, "qs_group_check: " + err);
+    return QS_OK;
+}
+
+// The six words of every group hypothesis over this context's table (qs_groups.hip). Replaces nothing in the reference; the nearest is
+// the metaquartet sum of processNodePair, which knows only the four subtrees beside a node pair of the reference tree.
+extern "C" int qs_group_support(qs_ctx *c, const uint8_t *labels, uint32_t n_hyp, int64_t *dst_device) {
+    if (!c) return QS_ERR_ARG;
+    if (!labels || !dst_device) return fail(c, QS_ERR_ARG, "qs_group_support: NULL argument");
+    if (reinterpret_cast<uintptr_t>(dst_device) % 8) return fail(c, QS_ERR_ARG, "qs_group_support: dst_device is not 8-byte aligned");
+    if (n_hyp == 0) return fail(c, QS_ERR_ARG, "qs_group_support: n_hyp must be at least 1");
+    if (!c->table) return fail(c, QS_ERR_STATE, "qs_group_support: no table");
+    const uint32_t n = c->n;
+    std::vector<uint8_t> kind(n_hyp);
+    std::vector<uint64_t> quartets(n_hyp);
+    {
+        std::string err;
+        if (!group_classify(n, labels, n_hyp, kind.data(), quartets.data(), err)) return fail(c, QS_ERR_ARG, "qs_group_support: " + err);
+    }
+    // every sum is at most (counted 4-sets of the whole table) x (largest count): the trees behind the table if known, else what a cell can hold
+    const uint64_t max_count = table_max_count(c);
+    for (uint32_t h = 0; h < n_hyp; ++h)
+        if (quartets[h] && max_count > (uint64_t)INT64_MAX / quartets[h])
+            return fail(c, QS_ERR_OVERFLOW, "qs_group_support: the counted 4-sets x the largest possible count exceed 63 bits for hypothesis " + std::to_string(h));
+    QS_HIP(c, hipSetDevice(c->device));
+    ScoreDevice sd{};
+    sd.n = n; sd.d_lo = c->d_lo; sd.d_hi = c->d_hi;
+    sd.rank_lo = c->rank_lo; sd.n_tuples = c->n_tuples; sd.table = c->table; sd.count_bits = (int)c->count_bits;   // the context's own table, not a scoring view
+    if (int rc = ensure_bundle_plan(c, sd, 3)) return rc;   // (the per-taxon pass' rounds: the same rows, the same waves)
+    // (a context's table is cut by the largest id: it starts and ends at a row start, plan_bundles finds no partial rows)
+    if (c->bundle[2].n_parts) return fail(c, QS_ERR_UNSUPPORTED, "qs_group_support: the table does not start and end at a row start");
+    const uint32_t n_pass = (n_hyp + kGroupHyp - 1) / kGroupHyp;
+    QS_HIP(c, hipStreamSynchronize(c->stream));   // (an earlier call's kernels and upload may still read the old label words)
+    c->group_labels.assign((size_t)n_pass * n, 0u);
+    for (uint32_t h = 0; h < n_hyp; ++h) {
+        uint32_t *w = c->group_labels.data() + (size_t)(h / kGroupHyp) * n;
+        for (uint32_t t = 0; t < n; ++t) w[t] |= (uint32_t)labels[(size_t)h * n + t] << (4 * (h % kGroupHyp));
+    }
+    QS_HIP(c, c->group_labels_dev.reserve(c->group_labels.size() * 4, nullptr));
+    QS_HIP(c, hipMemcpyAsync(c->group_labels_dev.get(), c->group_labels.data(), c->group_labels.size() * 4, hipMemcpyHostToDevice, c->stream));
+    QS_HIP(c, hipMemsetAsync(dst_device, 0, (size_t)n_hyp * kGroupWords * 8, c->stream));
+    const bool wide = max_count >= (1ull << 32) / 192;   // the per-taxon pass' rule: 64 lanes x 3 counts in a 32-bit partial sum
+    for (uint32_t p = 0; p < n_pass; ++p) {
+        const uint32_t h0 = p * kGroupHyp, nh = std::min<uint32_t>(kGroupHyp, n_hyp - h0);
+        uint32_t split_mask = 0;
+        for (uint32_t i = 0; i < nh; ++i) split_mask |= (uint32_t)kind[h0 + i] << i;
+        QS_HIP(c, launch_group_support(c->stream, sd, c->group_labels_dev.get() + (size_t)p * n, split_mask, nh, wide, c->n_cu,
+                                       reinterpret_cast<unsigned long long *>(dst_device) + (size_t)h0 * kGroupWords));
+    }
     return QS_OK;   // asynchronous on the context's stream
 }
 

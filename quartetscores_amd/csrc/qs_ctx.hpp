@@ -174,6 +174,9 @@ struct qs_ctx {
     // clades and workgroups, kept like the lists above
     std::vector<uint32_t> clade_tasks, clade_list;
     DevBuf<uint32_t> clade_tasks_dev, clade_list_dev;
+    // qs_group_support: the label words of the last call (per pass of kGroupHyp hypotheses one word per taxon), kept like the lists above
+    std::vector<uint32_t> group_labels;
+    DevBuf<uint32_t> group_labels_dev;
 };
 
 namespace qs {

@@ -155,6 +155,14 @@ struct ScoreDevice;
 constexpr int kTaxonWaves = 12;   // waves per workgroup = consecutive b per round (the logging pass 1's count, qs_score.hip)
 size_t taxon_lds_bytes(uint32_t n);
 hipError_t launch_taxon_support(hipStream_t s, const ScoreDevice &sd, bool wide, int n_cu, unsigned long long *dst);
+// qs_groups.hip: the six words of up to kGroupHyp group hypotheses over the whole rows of the rank range of a ScoreDevice
+// (qs_group_support); needs sd.bundle_* = plan_bundles with kTaxonWaves waves (of sd only n, rank_lo, table, count_bits and the plan are
+// read). labw[t] = the labels 0..4 of taxon t, hypothesis h in bits 4h .. 4h+3; split_mask bit h = hypothesis h is a split;
+// dst = 6 words per hypothesis, zeroed beforehand; wide: counts may reach 2^32 / 192
+constexpr int kGroupHyp = 8;      // hypotheses one read of the table serves
+constexpr int kGroupWords = 6;    // quartets, F1, F2, F3, outvoted, uninformed
+hipError_t launch_group_support(hipStream_t s, const ScoreDevice &sd, const uint32_t *labw, uint32_t split_mask, uint32_t n_hyp, bool wide,
+                                int n_cu, unsigned long long *dst);
 // qs_place.hip: link sums of the quartet placement of the taxa pd.taxa[0 .. n_list) (qs_taxon_placement); whole tables only. child[i][j] =
 // node of the child of lca(i,j) that holds leaf j; next[q][p], p < q = the first p' > p at which lca(p',q) or child[q][p'] differs (q if
 // none); inner_node = node index of a compact inner id of ref_lca; tasks = q | group of 64 largest ids << 16, longest walks first;

@@ -441,6 +441,34 @@ extern "C" int qs_shard_bounds(uint32_t n_taxa, uint32_t n_shards, uint32_t by, 
     return QS_OK;
 }
 
+// ---- group hypotheses: what a label pattern asserts and how many 4-sets of the whole table it counts ------------------------------
+bool qs::group_classify(uint32_t n, const uint8_t *labels, uint32_t n_hyp, uint8_t *kind, uint64_t *quartets, std::string &err) {
+    for (uint32_t h = 0; h < n_hyp; ++h) {
+        uint64_t cnt[5] = {0, 0, 0, 0, 0};
+        const uint8_t *row = labels + (size_t)h * n;
+        for (uint32_t t = 0; t < n; ++t) {
+            if (row[t] > 4) { err = "hypothesis " + std::to_string(h) + ": taxon " + std::to_string(t) + " carries label " + std::to_string(row[t]) + " (labels are 0..4)"; return false; }
+            cnt[row[t]]++;
+        }
+        const std::string who = "hypothesis " + std::to_string(h) + ": ";
+        if (cnt[3] || cnt[4]) {   // a quad: S1 S2 | S3 S4
+            for (uint32_t l = 1; l <= 4; ++l)
+                if (!cnt[l]) { err = who + "no taxon carries label " + std::to_string(l) + " (a quad hypothesis needs labels 1, 2, 3 and 4)"; return false; }
+            if (kind) kind[h] = 0;
+            if (quartets) quartets[h] = cnt[1] * cnt[2] * cnt[3] * cnt[4];
+        } else {                  // a split: S1 | S2
+            for (uint32_t l = 1; l <= 2; ++l)
+                if (cnt[l] < 2) {
+                    err = who + (cnt[l] ? "only one taxon carries label " : "no taxon carries label ") + std::to_string(l) + " (a split hypothesis needs two taxa on either side)";
+                    return false;
+                }
+            if (kind) kind[h] = 1;
+            if (quartets) quartets[h] = binom2(cnt[1]) * binom2(cnt[2]);
+        }
+    }
+    return true;
+}
+
 extern "C" int qs_score_plan(uint32_t n_taxa, uint64_t rank_lo, uint64_t n_tuples, uint32_t *first_pair, uint32_t *n_pairs, uint64_t parts[4]) {
     if (!first_pair || !n_pairs || !parts || n_taxa < 4 || n_taxa > 65535) return QS_ERR_ARG;
     if (rank_lo > binom4(n_taxa) || n_tuples > binom4(n_taxa) - rank_lo) return QS_ERR_ARG;

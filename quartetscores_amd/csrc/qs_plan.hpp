@@ -35,4 +35,9 @@ struct ClassPlan {
 void plan_classes(uint32_t n, uint32_t nt, const uint32_t *leaf_off, const uint16_t *adj_depth, const TreeFacts &F, uint32_t class_min,
                   uint32_t class_pct, uint32_t clamp_ppm, ClassPlan &P, bool fuse = false);
 
+// ---- group hypotheses (qs_group_check, qs_group_support) ----
+// labels[h * n + t] in 0..4 for n_hyp hypotheses over n taxa: kind (0 quad: labels 1..4 all occur; 1 split: only 1 and 2, each on at
+// least two taxa) and the whole-table number of counted 4-sets of each. false: err names the first hypothesis that is neither.
+bool group_classify(uint32_t n, const uint8_t *labels, uint32_t n_hyp, uint8_t *kind, uint64_t *quartets, std::string &err);
+
 }  // namespace qs

@@ -81,6 +81,89 @@ def taxon_columns(counts) -> dict:
     return out
 
 
+GROUP_FIELDS = ("quartets", "q1", "q2", "q3", "outvoted", "uninformed")
+GROUP_KINDS = ("quad", "split")
+
+
+def _group_labels(n_taxa, labels) -> np.ndarray:
+    a = np.asarray(labels)
+    if a.ndim == 1:
+        a = a[None, :]
+    if a.ndim != 2 or a.shape[1] != n_taxa:
+        raise ValueError(f"group labels need the shape (n_hyp, {n_taxa}), got {a.shape}")
+    if a.size and (a.min() < 0 or a.max() > 255):
+        raise QSError(_lib.QS_ERR_ARG, "group labels are 0..4")
+    return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def group_check(n_taxa: int, labels) -> Tuple[np.ndarray, np.ndarray]:
+    """qs_group_check (host-only, no device): labels (n_hyp, n_taxa) in 0..4 -> (kind uint8 (n_hyp,): 0 quad, 1 split -- GROUP_KINDS --,
+    quartets uint64 (n_hyp,): the whole-table number of counted 4-sets). QSError(QS_ERR_ARG) names the first hypothesis that is
+    neither a quad nor a split and what it lacks."""
+    L = _lib.load()
+    a = _group_labels(n_taxa, labels)
+    kind, quartets = np.zeros(len(a), dtype=np.uint8), np.zeros(len(a), dtype=np.uint64)
+    rc = L.qs_group_check(n_taxa, a.ctypes.data_as(C.c_void_p), len(a), kind.ctypes.data_as(C.c_void_p), quartets.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise QSError(rc, L.qs_last_error(None).decode())
+    return kind, quartets
+
+
+def parse_group_spec(text: str, name_to_id) -> Tuple[List[str], np.ndarray]:
+    """The SPEC file of QuartetScores --test-groups -> (names, labels uint8 (n_hyp, n_taxa)) for Context.group_support. One
+    hypothesis per non-empty line that does not start with '#': NAME<TAB>G1<TAB>G2 (split S1 | S2) or NAME<TAB>G1<TAB>G2<TAB>G3<TAB>G4
+    (quad S1 S2 | S3 S4); a group is a comma-separated list of taxon names, and one group of a split may be '*' = every taxon the
+    other group does not name. ValueError names the line (from 1) of an unknown name, a name in two groups, an empty group, a
+    split group with one taxon, or a line with three or more than four groups."""
+    n = len(name_to_id)
+    names, rows = [], []
+    for ln, line in enumerate(text.splitlines(), 1):
+        line = line.rstrip("\r")
+        if not line.strip() or line.lstrip().startswith("#"):
+            continue
+        cols = line.split("\t")
+        if len(cols) not in (3, 5):
+            raise ValueError(f"line {ln}: a hypothesis needs a name and two or four groups, found {len(cols) - 1} group(s)")
+        row = np.zeros(n, dtype=np.uint8)
+        stars = [k for k, g in enumerate(cols[1:], 1) if g.strip() == "*"]
+        if stars and (len(cols) != 3 or len(stars) > 1):
+            raise ValueError(f"line {ln}: '*' may stand for one group of a split only")
+        for k, g in enumerate(cols[1:], 1):
+            if k in stars:
+                continue
+            members = [x.strip() for x in g.split(",")]
+            if members == [""]:
+                raise ValueError(f"line {ln}: group {k} is empty")
+            for x in members:
+                if x not in name_to_id:
+                    raise ValueError(f"line {ln}: unknown taxon '{x}' in group {k}")
+                if row[name_to_id[x]]:
+                    raise ValueError(f"line {ln}: taxon '{x}' is in two groups (or twice in one)")
+                row[name_to_id[x]] = k
+        if stars:
+            row[row == 0] = stars[0]
+        if len(cols) == 3:
+            for k in (1, 2):
+                if (row == k).sum() < 2:
+                    raise ValueError(f"line {ln}: group {k} of a split needs at least two taxa" if (row == k).sum() else f"line {ln}: group {k} is empty")
+        names.append(cols[0])
+        rows.append(row)
+    return names, (np.stack(rows) if rows else np.zeros((0, n), dtype=np.uint8))
+
+
+def group_columns(kind, counts) -> dict:
+    """The columns of QuartetScores --test-groups from Context.group_support's (n_hyp, 6) words and group_check's kinds: the six
+    GROUP_FIELDS as int64 arrays, support = q1 / (q1 + q2 + q3) (nan where that is 0) and qpic = log_score(q1, q2, q3) for quad
+    hypotheses (nan for splits, whose q2 / q3 division means nothing)."""
+    a = np.asarray(counts, dtype=np.int64).reshape(-1, 6)
+    out = {name: a[:, k] for k, name in enumerate(GROUP_FIELDS)}
+    tot = a[:, 1] + a[:, 2] + a[:, 3]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["support"] = np.where(tot > 0, a[:, 1] / np.maximum(tot, 1), np.nan)
+    out["qpic"] = np.array([log_score(int(r[1]), int(r[2]), int(r[3])) if k == 0 else math.nan for k, r in zip(np.asarray(kind).reshape(-1), a)], dtype=np.float64)
+    return out
+
+
 PLACEMENT_COLUMNS = ("taxon", "name", "current", "best", "gain", "n_best", "best_node", "best_lo", "best_hi", "distance")
 
 
@@ -368,6 +451,18 @@ class Context:
         self.sync()
         del keep
         return buf.cpu().numpy().reshape(self.n, 6)
+
+    def group_support(self, labels) -> np.ndarray:
+        """qs_group_support: per hypothesis (labels (n_hyp, n_taxa) in 0..4; parse_group_spec builds them) the six words of
+        GROUP_FIELDS over the 4-sets of this context's table (whole table or shard: add the shards) -> int64 (n_hyp, 6);
+        group_columns derives the ratios. Needs no reference tree. Allocates the device buffer, waits for the result and
+        downloads it."""
+        import torch
+        a = _group_labels(self.n, labels)
+        buf = torch.empty(max(1, 6 * len(a)), dtype=torch.int64, device=f"cuda:{self.device}")
+        self._chk(self.L.qs_group_support(self.h, a.ctypes.data_as(C.c_void_p), len(a), C.c_void_p(buf.data_ptr())))
+        self.sync()
+        return buf[: 6 * len(a)].cpu().numpy().reshape(len(a), 6)
 
     def taxon_placement(self, ref: flatten.RefTree, taxa=None) -> np.ndarray:
         """qs_taxon_placement: per listed taxon (lookup ids; None = all, in id order) the 2 * n_nodes link sums W_x of its
