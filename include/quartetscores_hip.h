@@ -221,6 +221,13 @@ const char *qs_last_error(const qs_ctx *ctx); /* ctx may be NULL: message of the
                                        * The forced value also bypasses the planner's word alignment for 16-bit cells: the last cell of the lower
                                        * range and the first of the upper may then share a 32-bit word, which a halfword store and an atomic on the
                                        * other half reach at the same time (distinct cells; both are resolved in the L2). Not for production use. */
+#define QS_TUNE_STEP_ORDER 21u        /* count_bitslice3_kernel, binary_full classes of 4 and 5 depth bits: order of the 32-tree step. 1 = prefetch: the next
+                                       * group's panel elements are requested before the compare chains and held in registers across them (4 waves per
+                                       * SIMD). 2 = late loads: requested behind the step's first planes -- one set of pair registers, 5 waves per SIMD --
+                                       * in front of the second row of chains (4 bits: the load-to-use distance is the prefetch order's less one row
+                                       * of eight; what "late" buys there is the fifth wave, not a shorter distance) or behind the last (5 bits). 0 (default) = automatic: late
+                                       * loads for the instances measured faster that way (4 bits), prefetch for all others. Same table. The
+                                       * variant string names a late instance that ran as a segment /late<waves>. Other classes: no effect. */
 #define QS_TUNE_CLASS_MIN_TREES 16u   /* ... and the absolute floor of a class (default 1024 trees; tests lower it to split small batches) */
 #define QS_TUNE_SCORE_LOAD 14u        /* bundle score kernel, shape of the table loads: 0 (default) = every lane loads its own row in 16-byte pieces;
                                        * 2 = ... and requests the next chunk before it processes the current one; 1 = eight lanes load the

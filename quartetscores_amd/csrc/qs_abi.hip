@@ -60,6 +60,9 @@ extern "C" int qs_set_tuning(qs_ctx *c, uint32_t key, uint64_t value) {
         case QS_TUNE_FIX_SPLIT_AT:
             if (value > c->n) return fail(c, QS_ERR_ARG, "qs_set_tuning: QS_TUNE_FIX_SPLIT_AT takes 0 (planned) or a largest id up to n_taxa");
             c->tune_fix_split_at = (uint32_t)value; return QS_OK;
+        case QS_TUNE_STEP_ORDER:
+            if (value > 2) return fail(c, QS_ERR_ARG, "qs_set_tuning: QS_TUNE_STEP_ORDER takes 0 (automatic), 1 (prefetch) or 2 (late loads)");
+            c->tune_step_order = (uint32_t)value; return QS_OK;
         case QS_TUNE_CLASS_PCT: if (value > 100) return fail(c, QS_ERR_ARG, "qs_set_tuning: QS_TUNE_CLASS_PCT takes 0 .. 100"); c->tune_class_pct = (uint32_t)value; return QS_OK;
         case QS_TUNE_SCORE_LOAD:
             if (value > 3) return fail(c, QS_ERR_ARG, "qs_set_tuning: QS_TUNE_SCORE_LOAD takes 0 .. 3");

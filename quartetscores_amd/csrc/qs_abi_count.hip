@@ -515,6 +515,29 @@ static std::string class_name(const Launch &L, const Seg &sg, bool family, const
     return nm;
 }
 
+// QS_TUNE_STEP_ORDER: which order of the 32-tree step a class of count_bitslice3_kernel runs. 1 = prefetch everywhere, 2 = late loads
+// wherever the instance exists (bitslice3_late_waves), 0 = automatic: late loads for exactly the instances listed here, prefetch for all
+// others. A row = (mode, depth bits, cell bits) MEASURED faster late than prefetch on an MI355X, with the workload and its ms per step,
+// prefetch -> late (profiles/r13_step_order.md; the bar: every late run below every prefetch run and the mean difference at least three
+// times the spread of the prefetch runs). The wire format counts into 32-bit words: it follows the u32 rows.
+struct LateAuto { int mode, bits, cell_bits; const char *measured; };
+static constexpr LateAuto kLateAuto[] = {
+    {MODE_BINARY_FULL, 4, 32, "512 taxa x 10000 trees: 296.43 / 297.51 / 297.01 -> 288.29 / 288.91 / 289.77 (-2.7 %, 7.4 spreads); "
+                              "128 x 1000: 0.1675 / 0.1678 / 0.1680 -> 0.1592 / 0.1600 / 0.1601 (-4.8 %); "
+                              "256 x 12500: 25.46 / 25.54 / 25.41 -> 24.59 / 24.72 / 24.62 (-3.2 %, 6.5 spreads)"},
+    {MODE_BINARY_FULL, 4, 16, "1024 taxa x 5000 trees, shard 0 of 8: 313.85 / 314.56 / 314.14 -> 309.75 / 309.56 / 310.00 (-1.4 %, 6.1 spreads)"},
+    // not listed: 5 bits (u32, u16) -- compiled and tested, measured only as the smaller class of the --nni batch (with the 4-bit class:
+    // 297.37 / 296.90 / 294.74 -> 286.79 / 286.99 / 284.12), not on a batch of its own
+};
+// waves per SIMD of the late instance the class takes under `knob`; 0 = it takes the prefetch instance
+static int step_order_late_waves(uint32_t knob, int mode, int depth_bits, int cell_bits) {
+    const int w = knob == 1 ? 0 : bitslice3_late_waves(mode, depth_bits);
+    if (!w || knob == 2) return w;
+    for (const LateAuto &e : kLateAuto)
+        if (e.mode == mode && e.bits == std::max(depth_bits, 4) && e.cell_bits == cell_bits) return w;
+    return 0;
+}
+
 // Enqueue one launch, slice by slice (slice_groups over the concatenated group list [0, g_total) of its segments; slice [g0, g1)
 // takes from every segment the groups that fall into it): panel build(s), count kernel, depth-clamp corrections, and with
 // `timed` an event after each of the three. Into the table, or (wire != NULL) the two-cell wire words.
@@ -588,9 +611,13 @@ static int run_launch(qs_ctx *c, const qs_device_batch *b, const Launch &L, uint
         auto count_range = [&](const CountGeometry &gg) -> hipError_t {
             if (L.kernel == KERNEL_FUSED)
                 return launch_count_bitslice3_fused(c->stream, gg, seg_panel, seg_groups, seg_trees, L.bits, c->table, (int)c->count_bits, c->dev_flags.get(), ow);
-            if (L.kernel == KERNEL_BITSLICE3)
+            if (L.kernel == KERNEL_BITSLICE3) {
+                // (the cooperative lists send only the rest tiles through this kernel: they keep the prefetch order)
+                const int lw = gg.perm_coop ? 0 : step_order_late_waves(c->tune_step_order, mode0, L.bits, wire ? 32 : (int)c->count_bits);
+                if (lw) c->last_late_waves = (uint32_t)lw;
                 return launch_count_bitslice3(c->stream, gg, seg_panel[mode0], L.bits, mode0, seg_groups[mode0], seg_trees[mode0], wire ? nullptr : c->table,
-                                              wire ? 32 : (int)c->count_bits, c->dev_flags.get(), ow, wire);
+                                              wire ? 32 : (int)c->count_bits, c->dev_flags.get(), ow, wire, lw != 0);
+            }
             return launch_count_gather(c->stream, gg, seg_panel[mode0], L.bits, mode0, seg_groups[mode0], seg_trees[mode0], c->table, (int)c->count_bits, c->dev_flags.get(), ow);
         };
         // the corrections of the slice's trees in the d-range [d_a, d_b), on stream s
@@ -669,7 +696,7 @@ static int count_batch_wire(qs_ctx *c, const qs_device_batch *b, uint32_t algo) 
         return fail(c, QS_ERR_OVERFLOW, "QS_COUNT_WIRE16X2: more than 65535 trees do not fit 16-bit cells");
     if (d.class_bits[d.n_classes - 1] > 10) return fail(c, QS_ERR_UNSUPPORTED, "QS_COUNT_WIRE16X2: tree depth needs more than 10 bits; count into the table instead");
     { const uint32_t *order; int rc_o = tile_order(c, &order); if (rc_o != QS_OK) return rc_o; }   // (a failure here leaves the last call's events as they were)
-    c->ev_used = 0; c->last_split = c->last_splits = 0;
+    c->ev_used = 0; c->last_split = c->last_splits = 0; c->last_late_waves = 0;
     if (timed) QS_HIP(c, mark(c, 0));
     bool first = true;
     c->variant = "gather/binary_full/bitslice_";
@@ -681,6 +708,7 @@ static int count_batch_wire(qs_ctx *c, const qs_device_batch *b, uint32_t algo) 
         c->variant += (k ? "+" : "") + class_name(L, L.segs[0], false, nullptr, d.n_classes > 1);
     }
     c->variant += "/wire_u16x2";
+    if (c->last_late_waves) c->variant += "/late" + std::to_string(c->last_late_waves);
     if (d.n_fix) c->variant += "/clamp:" + std::to_string(d.clamped_trees);
     if (c->last_splits) c->variant += "/overlap:" + std::to_string(c->last_split);
     if (c->n_coop) c->variant += "/coop4";
@@ -714,7 +742,7 @@ extern "C" int qs_count_batch(qs_ctx *c, const qs_device_batch *b, uint32_t algo
     if (overwrite && algo != QS_ALGO_GATHER) return fail(c, QS_ERR_ARG, "qs_count_batch: QS_COUNT_OVERWRITE needs the gather algorithm");
     // (a call refused before its first launch leaves table and count as they were; run_launch resets trees_counted with the first
     // overwriting launch it enqueues, so that a refusal after it -- a later class too deep, a panel that cannot grow -- leaves no stale count)
-    c->ev_used = 0; c->last_split = c->last_splits = 0;
+    c->ev_used = 0; c->last_split = c->last_splits = 0; c->last_late_waves = 0;
     if (timed) QS_HIP(c, mark(c, 0));
     if (algo == QS_ALGO_GATHER) {
         static const char *mode_names[4] = {"binary_full", "general_full", "partial", "binary_partial"};
@@ -785,6 +813,7 @@ extern "C" int qs_count_batch(qs_ctx *c, const qs_device_batch *b, uint32_t algo
         c->variant = std::string("gather/") + (mixed ? "mixed" : mode_names[(!all_swar && d.class_bits[0] > top_bits && one_mode == MODE_BINARY_PARTIAL) ? (int)MODE_PARTIAL : one_mode]) + "/" + names + "/count_u" + std::to_string(c->count_bits);
         if (fused_launch_groups) c->variant += "/fused:" + std::to_string(fused_launch_groups);   // depth-bits groups whose classes shared a launch (count_bitslice3_fused_kernel)
         if (any_coop) c->variant += "/coop4";
+        if (c->last_late_waves) c->variant += "/late" + std::to_string(c->last_late_waves);   // a binary_full class ran the late-load instance (QS_TUNE_STEP_ORDER) at that many waves per SIMD
         if (!all_swar && d.n_fix) c->variant += "/clamp:" + std::to_string(d.clamped_trees);   // trees counted below their own depth bits + clamp_fix_kernel
         if (c->last_splits) c->variant += "/overlap:" + std::to_string(c->last_split);           // slices split at that largest id: corrections beside the lower count launch
     } else if (algo == QS_ALGO_SCATTER) {

@@ -259,6 +259,29 @@ template <int B, int MODE> constexpr int bs3_waves() {
     return QS_BS3_WAVES;
 }
 
+// The instances that exist a second time in the late-load order (bs3_segment<.., LATE = true>) and the waves per SIMD that one is
+// held to; 0 = no late instance. Only where the late order fits the higher occupancy WITHOUT scratch (hipcc -O3, gfx950, u32 and
+// u16 cells alike): binary_full at 4 bits 93 VGPRs (QS_LATE_ROW = 1; 82 at 8), at 5 bits 95 -- five waves per SIMD (<= 96) where the prefetch order needs 126 /
+// 115 and runs four. At 6 bits the late order needs 98: no fifth wave, no late instance. (At 4 bits six waves, <= 80, cost 16
+// spilled registers.) Both are product settings that follow from those register counts, overridable only for variant builds.
+#ifndef QS_LATE_MAXB
+#define QS_LATE_MAXB 5    /* deepest class with a late instance */
+#endif
+#ifndef QS_LATE_WAVES
+#define QS_LATE_WAVES 5   /* its waves per SIMD (6: one run, 300.4 against 311.5-313.2 at 5 in a build with 8 % more instructions; spills in this one) */
+#endif
+#ifndef QS_LATE_ROW
+#define QS_LATE_ROW 1     /* 4 depth bits: the late order requests the next group in front of this d-row's chains; 8 (kDB) = behind the last row.
+                           * Measured (512 taxa x 10 000 trees, ms per step, three runs each on one box; profiles/r13_step_order.md): prefetch order at
+                           * 4 waves 296.4-297.5, row 8 at 5 waves 295.4-295.7, row 1 at 5 waves 288.3-289.8 -- the load-to-use distance IS needed;
+                           * what the late order buys is the one M[ab] set and the two address bases, i.e. the fifth wave (row 1: 93 VGPRs, row 8: 82) */
+#endif
+// in front of which d-row the late order requests the next group: at 5 bits any row but "behind the last" spills at five waves
+template <int B> constexpr int bs3_late_row() { return B <= 4 ? QS_LATE_ROW : 8; }
+template <int B, int MODE> constexpr int bs3_late_waves() {
+    return (MODE == MODE_BINARY_FULL && B <= QS_LATE_MAXB) ? QS_LATE_WAVES : 0;
+}
+
 constexpr int kWavesPerBlock = kCountThreads / kWave;   // 4: a workgroup = four independent wave tiles (consecutive in the launch order)
 
 // ======================================================================================
@@ -385,12 +408,14 @@ __device__ __forceinline__ int bs3_tile_variant(const Bs3Tile &t) {
     const bool full = t.jlo == 0 && t.jhi == (uint32_t)kDB;
     return t.has_a2 ? (full ? 0 : 1) : (t.offdiag ? 2 : 3);
 }
-template <int B, int MODE, int VAR = -1>
+// LATE: the step order of the instance (binary modes only): false = prefetch (`step`), true = late loads (`step_late`).
+template <int B, int MODE, int VAR = -1, bool LATE = false>
 __device__ __forceinline__ void bs3_segment(const Bs3Tile &t, const uint4 *__restrict__ P, uint32_t npairs, uint32_t n_groups, uint32_t xcd_remap,
                                             uint4 *lds, uint32_t (&x0)[kDB], uint32_t (&x1)[kDB], uint32_t (&y0)[kDB], uint32_t (&y1)[kDB],
                                             uint32_t (&z0)[kDB], uint32_t (&z1)[kDB]) {
     using Lay = Bs3Layout<B, MODE>;
     constexpr bool BIN = Lay::BIN, GEN = Lay::GEN, PART = Lay::PART, BP = Lay::BP;
+    static_assert(!LATE || BIN, "the late-load step exists for the binary modes");
     constexpr int RC = Lay::RC, kS3Row0 = Lay::kS3Row0, kS3Slots = Lay::kS3Slots, NBUF = Lay::NBUF, NB = Lay::NB, NW = Lay::NW, HW = Lay::HW, PW = Lay::PW;
     uint4 *buf0 = lds, *buf1 = lds + (NBUF - 1) * Lay::kImg;
     const uint32_t lane = t.lane, c = t.c, d0 = t.d0, d1 = t.d1, jlo = t.jlo, jhi = t.jhi, blk0 = t.blk0, blk1 = t.blk1, blkB = t.blkB;
@@ -458,6 +483,30 @@ __device__ __forceinline__ void bs3_segment(const Bs3Tile &t, const uint4 *__res
         return lload(buf, kS3Row0 + col);
     };
     struct Staged { Planes x0, x1, x2, y, row; };
+    // binary modes, both step orders: the compare chains of d-row j -- R element Rb of (b,d) against L1 and, where the second
+    // a-column exists, L2
+    auto bin_row = [&](int j, const Planes &L1, const Planes &L2, const Planes &Rb, auto a2_tag) {
+        uint32_t gt, lt;
+        cmp_planes<NB>(L1, Rb, gt, lt);
+        if (BP) {
+            const uint32_t v = L1.w[kPres] & Rb.w[kPres];   // a1, b, c, d all present
+            gt &= v; lt &= v;
+            popc_acc(v, z0[j]);   // trees that hold all four: a binary one resolves the quartet, so ad|bc = this count - the other two (epilogue)
+        }
+        popc_acc(gt, x0[j]);
+        popc_acc(lt, x1[j]);
+        if (decltype(a2_tag)::value) {
+            uint32_t gt2, lt2;
+            cmp_planes<NB>(L2, Rb, gt2, lt2);
+            if (BP) {
+                const uint32_t v2 = L2.w[kPres] & Rb.w[kPres];
+                gt2 &= v2; lt2 &= v2;
+                popc_acc(v2, z1[j]);
+            }
+            popc_acc(gt2, y0[j]);
+            popc_acc(lt2, y1[j]);
+        }
+    };
 
     // one 32-tree step: request group g_next into (st, abn1, abn2), count group g from (cur, abc1, abc2), then
     // turn the requested elements into the LDS image `nxt`
@@ -514,28 +563,10 @@ __device__ __forceinline__ void bs3_segment(const Bs3Tile &t, const uint4 *__res
                     if (QS_GEN_PREFETCH == 2) __builtin_amdgcn_sched_barrier(0);
                 }
                 const Planes Rb = PFR ? pRb : lload(cur, j * RC + colB);   // M[bd] - M[cd] + 2^B
-                uint32_t gt, lt;
-                cmp_planes<NB>(L1, Rb, gt, lt);
-                if (BIN) {
-                    if (BP) {
-                        const uint32_t v = L1.w[kPres] & Rb.w[kPres];   // a1, b, c, d all present
-                        gt &= v; lt &= v;
-                        popc_acc(v, z0[j]);   // trees that hold all four: a binary one resolves the quartet, so ad|bc = this count - the other two (epilogue)
-                    }
-                    popc_acc(gt, x0[j]);
-                    popc_acc(lt, x1[j]);
-                    if (A2) {
-                        uint32_t gt2, lt2;
-                        cmp_planes<NB>(L2, Rb, gt2, lt2);
-                        if (BP) {
-                            const uint32_t v2 = L2.w[kPres] & Rb.w[kPres];
-                            gt2 &= v2; lt2 &= v2;
-                            popc_acc(v2, z1[j]);
-                        }
-                        popc_acc(gt2, y0[j]);
-                        popc_acc(lt2, y1[j]);
-                    }
-                } else {
+                if (BIN) bin_row(j, L1, L2, Rb, a2_tag);
+                else {
+                    uint32_t gt, lt;
+                    cmp_planes<NB>(L1, Rb, gt, lt);
                     const Planes Ra = PFR ? pRa : lload(cur, j * RC + colA1);    // M[a1 d] - M[cd] + 2^B
                     // [S3 > S1]. In a tree the two smaller of the three sums are equal (four-point condition), so S3 > S1 already
                     // implies S1 == S2: no masking with ~(gt | lt) (round 4: one instruction per quartet less)
@@ -576,6 +607,79 @@ __device__ __forceinline__ void bs3_segment(const Bs3Tile &t, const uint4 *__res
         if (NBUF == 1) lds_order<QS_GEN_WBAR>();   // ... and the next step's reads stay behind these stores
     };
 
+    // The same step in the LATE order (binary modes): L1 / L2 of group g from (cur, ab1, ab2) FIRST, then -- in front of d-row
+    // bs3_late_row<B>() of the compare chains, or behind the last row -- the request of group g_next, whose M[ab] elements so land in
+    // the ONE register set that L has just finished with; behind the chains the wait and the LDS image `nxt`. Behind the last row
+    // nothing requested is held across the chains and the latency is exposed per wave; in front of row 1 it is the prefetch order's
+    // load-to-use distance less one row. Either way the instance fits five waves per SIMD, which the prefetch order (two M[ab] sets,
+    // loads in front of L) does not. The two scheduling barriers keep the machine scheduler from moving the requests.
+    // The lane's LDS columns and the byte offsets of its b-column in the two word arrays of a d-row are re-defined behind an empty
+    // asm: LLVM otherwise hoists every (d-row, word array) address of both images out of the loop as a value of its own (16
+    // registers). Behind the asm the rows are immediate offsets from two bases -- given as constant indices from the byte offsets
+    // (rload): from an opaque COLUMN the compiler rebuilds every row address with an add (+17 VALU instructions per step, 8 %).
+    uint32_t colA_o = colA1_, colB_o = colB_, bLo_o = colB_ * 16u, bHi_o = colB_ * (uint32_t)(HW * 4);
+    if (LATE) asm volatile("" : "+v"(colA_o), "+v"(colB_o), "+v"(bLo_o), "+v"(bHi_o));
+    auto step_late = [&](uint32_t g_next, const uint4 *cur, uint4 *nxt, Planes &ab1, Planes &ab2, auto a2_tag, auto full_tag, auto nr_tag) {
+        constexpr bool A2 = decltype(a2_tag)::value, FULL = decltype(full_tag)::value;
+        constexpr int NR = decltype(nr_tag)::value;
+        if (xcd_remap & 2u) __builtin_amdgcn_s_barrier();   // waves of a workgroup in step: see `step`
+        // 4 bits: the bases re-defined once per segment (above); from 5 bits on once per STEP (four moves; once per segment costs 12
+        // spilled registers at five waves). The second a-column, where it exists, lies kTA columns behind the first (off-diagonal tiles).
+        uint32_t colA = colA1_, colB = colB_, bLo = colB_ * 16u, bHi = colB_ * (uint32_t)(HW * 4);
+        if (NW > 4) asm volatile("" : "+v"(colA), "+v"(colB), "+v"(bLo), "+v"(bHi));
+        else { colA = colA_o; colB = colB_o; bLo = bLo_o; bHi = bHi_o; }
+        // R element of d-row j: constant offsets from the two column bases (HW <= 2: up to six words per element)
+        auto rload = [&](int j) {
+            if (HW > 2) return lload(cur, j * RC + colB);
+            Planes r;
+            const uint4 lo = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(cur) + bLo)[j * RC];
+            r.w[0] = lo.x; r.w[1] = lo.y; r.w[2] = lo.z; r.w[3] = lo.w;
+#pragma unroll
+            for (int k = 4; k < kBitWords; ++k) r.w[k] = 0;
+            const char *hi = reinterpret_cast<const char *>(cur + kS3Slots) + bHi;
+            if (HW == 1) r.w[4] = reinterpret_cast<const uint32_t *>(hi)[j * RC];
+            else { const uint2 h = reinterpret_cast<const uint2 *>(hi)[j * RC]; r.w[4] = h.x; r.w[5] = h.y; }
+            if (PART && PW != kPres) { r.w[kPres] = r.w[PW]; r.w[PW] = 0; }
+            return r;
+        };
+        if (QS_BIN_PRIO) __builtin_amdgcn_s_setprio(1);
+        const Planes L1 = sub_biased<B>(ab1, row0_load(cur, colA));
+        Planes L2 = L1;
+        if (A2) L2 = sub_biased<B>(ab2, row0_load(cur, colA + kTA));
+        Planes sx0 = L1, sy = L1, sx1 = L1, srow = L1;
+        auto request = [&] {
+            __builtin_amdgcn_sched_barrier(0);
+            const __amdgpu_buffer_rsrc_t r = rsrc_of(g_next);
+            // From 5 planes on an element has upper words, in arrays of their own both in the panel and in LDS: every offset and slot
+            // would live in two or three derived forms through the compare chains. Re-defined here, the derived forms are rebuilt per
+            // step (a shift or an add each) right where they are used.
+            uint32_t o_x0 = x0off, o_y = yoff, o_x1 = x1off, o_row = rowoff, o_ab = ab1off;
+            if (NW > 4) asm volatile("" : "+v"(o_x0), "+v"(o_y), "+v"(o_x1), "+v"(o_row), "+v"(o_ab));
+            sx0 = gload(r, o_x0);
+            sy = gload(r, o_y);
+            if (NR >= 2) sx1 = gload(r, o_x1);
+            srow = gload(r, o_row);
+            ab1 = gload(r, o_ab);
+            // (a2,b) is the pair kTA behind (a1,b), and exists exactly where (a1,b) does (off-diagonal tile: both a-blocks lie below the
+            // b-block); kS3Inv + kTA * 16 is as far beyond the group as kS3Inv
+            if (A2) ab2 = gload(r, o_ab + (uint32_t)kTA * 16u);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+#pragma unroll
+        for (int j = 0; j < QS_PROBE_ROWS; ++j) {
+            if (j == bs3_late_row<B>()) request();
+            if (FULL || ((uint32_t)j >= jlo && (uint32_t)j < jhi)) bin_row(j, L1, L2, rload(j), a2_tag); // wave-uniform
+        }
+        if (QS_BIN_PRIO) __builtin_amdgcn_s_setprio(0);
+        if (bs3_late_row<B>() >= QS_PROBE_ROWS) request();
+        uint32_t s_0 = slot0, s_row = rowslot;
+        if (NW > 4) asm volatile("" : "+v"(s_0), "+v"(s_row));
+        lstore(nxt, s_0, sub_biased<B>(sx0, sy));
+        if (NR >= 2) lstore(nxt, s_0 + 8, sub_biased<B>(sx1, sy));
+        if (B <= 4 && !PART) nxt[s_row] = make_uint4(srow.w[0], srow.w[1], srow.w[2], srow.w[3]);
+        else lstore(nxt, s_row, srow);
+    };
+
     auto run = [&](auto a2_tag, auto full_tag, auto nr_tag) {
         constexpr bool A2 = decltype(a2_tag)::value;
         constexpr int NR = decltype(nr_tag)::value;
@@ -599,11 +703,19 @@ __device__ __forceinline__ void bs3_segment(const Bs3Tile &t, const uint4 *__res
         // i.e. behind the whole compute of the first step and directly in front of their first use -- one exposed L2
         // round trip per two steps, taken by all waves of a SIMD at about the same time.
         uint32_t g = 0;
-        for (; g + 2 <= n_groups; g += 2) {
-            step(g + 1, buf0, buf1, abA1, abA2, abB1, abB2, a2_tag, full_tag, nr_tag);
-            step(min(g + 2, g_last), buf1, buf0, abB1, abB2, abA1, abA2, a2_tag, full_tag, nr_tag); // past the end: re-reads the last group (unused)
+        if constexpr (LATE) {   // one M[ab] set; the two-step trip stays for the two LDS images, which swap roles without a register move
+            for (; g + 2 <= n_groups; g += 2) {
+                step_late(g + 1, buf0, buf1, abA1, abA2, a2_tag, full_tag, nr_tag);
+                step_late(min(g + 2, g_last), buf1, buf0, abA1, abA2, a2_tag, full_tag, nr_tag);
+            }
+            if (g < n_groups) step_late(g_last, buf0, buf1, abA1, abA2, a2_tag, full_tag, nr_tag);
+        } else {
+            for (; g + 2 <= n_groups; g += 2) {
+                step(g + 1, buf0, buf1, abA1, abA2, abB1, abB2, a2_tag, full_tag, nr_tag);
+                step(min(g + 2, g_last), buf1, buf0, abB1, abB2, abA1, abA2, a2_tag, full_tag, nr_tag); // past the end: re-reads the last group (unused)
+            }
+            if (g < n_groups) step(g_last, buf0, buf1, abA1, abA2, abB1, abB2, a2_tag, full_tag, nr_tag);
         }
-        if (g < n_groups) step(g_last, buf0, buf1, abA1, abA2, abB1, abB2, a2_tag, full_tag, nr_tag);
     };
     using T_ = std::true_type; using F_ = std::false_type;
     using N1 = std::integral_constant<int, 1>; using N2 = std::integral_constant<int, 2>; using N3 = std::integral_constant<int, 3>;

@@ -720,8 +720,10 @@ uint32_t bitslice3_tiles_for_c(uint32_t c) {
 
 // One class of trees per launch: tile decode, the class's groups past the tile (bs3_segment), the tuples to the table. The mixed
 // batches' single launch over several classes is count_bitslice3_fused_kernel (qs_count_fused.hip).
-template <int B, int MODE, typename CT>
-__global__ __launch_bounds__(kCountThreads) __attribute__((amdgpu_waves_per_eu(bs3_waves<B, MODE>(), bs3_waves<B, MODE>()))) void count_bitslice3_kernel(const uint4 *__restrict__ P, uint32_t npairs,
+// LATE: the step order (bs3_segment) -- the register budget, and with it the occupancy, is a property of the instance.
+template <int B, int MODE, bool LATE> constexpr int bs3_kernel_waves() { return LATE ? bs3_late_waves<B, MODE>() : bs3_waves<B, MODE>(); }
+template <int B, int MODE, typename CT, bool LATE = false>
+__global__ __launch_bounds__(kCountThreads) __attribute__((amdgpu_waves_per_eu(bs3_kernel_waves<B, MODE, LATE>(), bs3_kernel_waves<B, MODE, LATE>()))) void count_bitslice3_kernel(const uint4 *__restrict__ P, uint32_t npairs,
                                                                         uint32_t n_groups, uint32_t m_trees,
                                                                         uint32_t d_start, uint32_t d_hi, uint64_t rank_lo,
                                                                         uint32_t n_dblk, uint32_t total_tiles,
@@ -739,7 +741,7 @@ __global__ __launch_bounds__(kCountThreads) __attribute__((amdgpu_waves_per_eu(b
     uint32_t x0[kDB], x1[kDB], y0[kDB], y1[kDB], z0[kDB], z1[kDB];
 #pragma unroll
     for (int j = 0; j < kDB; ++j) x0[j] = x1[j] = y0[j] = y1[j] = z0[j] = z1[j] = 0;
-    bs3_segment<B, MODE>(t, P, npairs, n_groups, xcd_remap, stage_all[wave], x0, x1, y0, y1, z0, z1);
+    bs3_segment<B, MODE, -1, LATE>(t, P, npairs, n_groups, xcd_remap, stage_all[wave], x0, x1, y0, y1, z0, z1);
     constexpr int THIRD = MODE == MODE_BINARY_FULL ? 0 : MODE == MODE_BINARY_PARTIAL ? 1 : 2;
     bs3_store<CT, THIRD>(t, rank_lo, table, overflow_flag, overwrite, m_trees, MODE == MODE_BINARY_FULL ? wire : nullptr, x0, x1, y0, y1, z0, z1);
 }
@@ -956,10 +958,24 @@ __global__ __launch_bounds__(kCountThreads) __attribute__((amdgpu_waves_per_eu(b
 }
 
 
+template <int B> constexpr int late_waves_bf() { return bs3_late_waves<B, MODE_BINARY_FULL>(); }
+// f(integral_constant<B>) only where the late instance of B exists (nothing else is instantiated)
+template <int B, typename F> static void bs3_if_late(F f) {
+    if constexpr (late_waves_bf<B>() > 0) f(std::integral_constant<int, B>{});
+}
+// waves per SIMD of the late-load instance of (mode, depth bits); 0 = that class has none (which of them the automatic setting of
+// QS_TUNE_STEP_ORDER takes is the caller's table: qs_abi_count.hip)
+int bitslice3_late_waves(int mode, int depth_bits) {
+    if (mode != MODE_BINARY_FULL) return 0;
+    const int b = depth_bits <= 4 ? 4 : depth_bits;
+    return b == 4 ? late_waves_bf<4>() : b == 5 ? late_waves_bf<5>() : b == 6 ? late_waves_bf<6>() : 0;
+}
+
 hipError_t launch_count_bitslice3(hipStream_t s, const CountGeometry &g_in, const void *panel, int depth_bits, int mode,
                                   uint32_t n_groups, uint32_t m_trees, void *table, int count_bits, uint32_t *overflow_flag,
-                                  bool overwrite, uint32_t *wire) {
+                                  bool overwrite, uint32_t *wire, bool late) {
     if (g_in.total_tiles == 0 || n_groups == 0) return hipSuccess;
+    if (late && !bitslice3_late_waves(mode, depth_bits)) return hipErrorInvalidValue;
     const uint32_t npairs = (uint32_t)binom2(g_in.n);
     CountGeometry g = g_in;
     // (count_bitslice4_kernel carries at most 7 planes per element: deeper classes take the plain kernel over g.perm with all tiles)
@@ -987,10 +1003,26 @@ hipError_t launch_count_bitslice3(hipStream_t s, const CountGeometry &g_in, cons
         if (g.total_tiles == 0) return hipSuccess;
     }
     dim3 grid((g.total_tiles + kWavesPerBlock - 1) / kWavesPerBlock), block(kCountThreads);
-#define QS_BS3(BB, MM, CT)                                                                                          \
-    hipLaunchKernelGGL((count_bitslice3_kernel<BB, MM, CT>), grid, block, 0, s, (const uint4 *)panel, npairs, n_groups, \
+#define QS_BS3X(BB, MM, CT, LATE)                                                                                   \
+    hipLaunchKernelGGL((count_bitslice3_kernel<BB, MM, CT, LATE>), grid, block, 0, s, (const uint4 *)panel, npairs, n_groups, \
                        m_trees, g.d_lo, g.d_hi, g.rank_lo, g.n_dblk, g.total_tiles, g.dprefix, g.cprefix,           \
                        (CT *)table, overflow_flag, overwrite ? 1u : 0u, g.n >= 200 ? (((kSyncModes >> (MM)) & 1u) ? 3u : 1u) : 0u /* bit 0: XCD remap, bit 1: waves of a workgroup in step (QS_SYNC_MODES) */, wire, g.perm)
+#define QS_BS3(BB, MM, CT) QS_BS3X(BB, MM, CT, false)
+    // the late-load instances (binary_full, the depth bits of bs3_late_waves): the same launch, the other step order
+    if (late) {
+#define QS_BS3L(BB, CT) bs3_if_late<BB>([&](auto b_tag) { QS_BS3X(decltype(b_tag)::value, MODE_BINARY_FULL, CT, true); })
+#define QS_BS3L_B(CT)                                                                                               \
+    do {                                                                                                            \
+        if (depth_bits <= 4) QS_BS3L(4, CT);                                                                        \
+        else if (depth_bits == 5) QS_BS3L(5, CT);                                                                   \
+        else if (depth_bits == 6) QS_BS3L(6, CT);                                                                   \
+        else return hipErrorInvalidValue;                                                                           \
+    } while (0)
+        if (count_bits == 32) QS_BS3L_B(uint32_t); else QS_BS3L_B(uint16_t);
+#undef QS_BS3L_B
+#undef QS_BS3L
+        return hipGetLastError();
+    }
 #define QS_BS3_B(MM, CT)                                                                                            \
     do {                                                                                                            \
         switch (depth_bits <= 4 ? 4 : depth_bits) {                                                                 \
@@ -1019,6 +1051,7 @@ hipError_t launch_count_bitslice3(hipStream_t s, const CountGeometry &g_in, cons
 #undef QS_BS3_BP
 #undef QS_BS3_B
 #undef QS_BS3
+#undef QS_BS3X
     return hipGetLastError();
 }
 

@@ -114,7 +114,10 @@ hipError_t launch_build_bitpanel(hipStream_t s, const DeviceBatch &b, uint32_t n
                                  bool force_general);
 hipError_t launch_count_bitslice3(hipStream_t s, const CountGeometry &g, const void *panel, int depth_bits, int mode,
                                   uint32_t n_groups, uint32_t m_trees, void *table, int count_bits, uint32_t *overflow_flag,
-                                  bool overwrite, uint32_t *wire); // wire != NULL (binary_full only): one word n0 | n1 << 16 per tuple instead of the table
+                                  bool overwrite, uint32_t *wire, // wire != NULL (binary_full only): one word n0 | n1 << 16 per tuple instead of the table
+                                  bool late = false);             // the late-load instance of the class (bitslice3_late_waves != 0) instead of the prefetch one
+// waves per SIMD of the late-load instance of (mode, depth bits); 0 = the class has none
+int bitslice3_late_waves(int mode, int depth_bits);
 // the classes of a mixed batch that share their depth bits in ONE launch (qs_count_fused.hip); seg_* are indexed by CountMode, a mode
 // without trees in this launch has seg_groups = 0
 constexpr int kFusedMaxBits = 7;

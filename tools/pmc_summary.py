@@ -62,7 +62,8 @@ if bench:
     cell = "unsigned int" if bench["dtype"] == "u32" else "unsigned short"
 
     def mine(name):
-        return kname in name and (cell + ">") in name.replace(" >", ">")
+        n_ = name.split("(")[0].replace(" >", ">")   # template arguments only; count_bitslice3_kernel carries its step order behind the cell type ("unsigned int, true>")
+        return kname in n_ and ((cell + ">") in n_ or (cell + ", ") in n_)
 
     def avg(counter):
         tot = cnt = 0.0
