@@ -18,6 +18,7 @@
  *                                 qs_table_remap replaces nothing (the reference recounts per reference tree), nor does
  *                                 qs_table_restrict (the reference recounts per taxon set)
  *   qs_tree_agreement             replaces nothing in the reference (it reports no per-tree agreement)
+ *   qs_tree_pair_agreement        replaces nothing in the reference (it never compares the evaluation trees with each other)
  *   qs_taxon_support              replaces nothing in the reference (the nearest is printRawQICScores, :612-680: one text
  *                                 line per quartet, which a user would reduce per taxon on the host)
  *   qs_group_check /              replace nothing in the reference; the nearest is the metaquartet sum of processNodePair
@@ -366,6 +367,30 @@ int qs_lookup(qs_ctx *ctx, uint64_t nq, const uint16_t *abcd, uint64_t *out3);
  * from the context's or its ids are not in depth-first order; QS_ERR_UNSUPPORTED = a table-shard context (use a whole-table one).
  * Asynchronous on the context's stream, ordered behind the batch's upload. */
 int qs_tree_agreement(qs_ctx *ctx, const qs_ref_tree *ref, const qs_device_batch *b, uint64_t *dst_device);
+
+/* Quartet agreement of the evaluation trees with EACH OTHER: the trees [r0, r1) of `rows` against the trees [c0, c1) of `cols`, indexed
+ * as in their batches (upload order). For row tree s with taxon set P_s and column tree t with P_t let S = P_s & P_t and N = |S|; over
+ * the C(N,4) quartets of S, both trees restricted to S, dst_device[((s - r0) * (c1 - c0) + (t - c0)) * 5 + k] receives the exact counts
+ *   k = 0 concordant    resolved in both trees, same topology       k = 3 resolved_col  resolved in t
+ *   k = 1 discordant    resolved in both, different topologies      k = 4 shared        N
+ *   k = 2 resolved_row  resolved in s
+ * row_only = resolved_row - concordant - discordant, col_only likewise, unresolved = C(N,4) - concordant - discordant - row_only -
+ * col_only; (discordant + row_only + col_only) / C(N,4) is the normalised quartet distance that takes "unresolved" as a topology of
+ * its own. N < 4 gives four zeros and N. Multifurcating and rooted trees on both sides; (s,t) is (t,s) with words 2 and 3 exchanged.
+ * O(#inner nodes of s x #inner nodes of t) per pair for binary trees, O(min(k,l) k l) per node pair of degrees k and l: no quartet
+ * is enumerated, but two stars of a thousand leaves meeting are 1e9 operations in one lane. Exact integers,
+ * independent of grid, batching and rooting. `rows` and `cols` are the same batch or two batches of this context, both uploaded with
+ * node_off / rng_off / ranges. flags: QS_PAIRS_UPPER = rows and cols are the same batch and the pairs with column index <= row index
+ * are skipped (their five words are 0). dst_device (caller-owned device memory, 8-byte aligned, (r1 - r0) x (c1 - c0) x 5 words) is
+ * OVERWRITTEN. Needs no reference tree and no count table; changes neither the table nor trees-counted nor a pending score log.
+ * An empty range is QS_OK with no work.
+ * Errors: QS_ERR_STATE = a batch was uploaded without node ranges; QS_ERR_ARG = NULL or misaligned pointer, r0 > r1 or r1 beyond the
+ * batch (the same for columns), an unknown flag, QS_PAIRS_UPPER with two different batches, more than 2^28 pairs in one call;
+ * QS_ERR_UNSUPPORTED = a table-shard context (use a whole-table one). Asynchronous on the context's stream, ordered behind both
+ * batches' uploads. The reference never compares the evaluation trees with each other: this replaces nothing there. */
+#define QS_PAIRS_UPPER 1u
+int qs_tree_pair_agreement(qs_ctx *ctx, const qs_device_batch *rows, uint32_t r0, uint32_t r1, const qs_device_batch *cols, uint32_t c0,
+                           uint32_t c1, uint32_t flags, uint64_t *dst_device);
 
 /* Per-taxon quartet support from the count table: which taxa carry the conflict with the reference tree. Taxa are lookup ids
  * (the reference's depth-first leaf order). For a 4-set with table tuple (n0,n1,n2) the reference's topology is decided as in

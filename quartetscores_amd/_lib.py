@@ -29,6 +29,7 @@ QS_TUNE_STEP_ORDER = 21   # 0 = automatic, 1 = prefetch, 2 = late loads (binary_
 QS_CLASS_PLAN_FUSED = 0x100
 QS_IMPL_AUTO, QS_IMPL_SWAR, QS_IMPL_BITSLICE = 0, 1, 2
 QS_SHARDS_BY_TUPLES, QS_SHARDS_BY_COST = 0, 1
+QS_PAIRS_UPPER = 1
 
 # every symbol include/quartetscores_hip.h declares
 EXPORTS = [
@@ -40,7 +41,7 @@ EXPORTS = [
     "qs_score_plan", "qs_last_score_ms", "qs_prepare", "qs_table_pack32x2", "qs_unpack32x2", "qs_last_score_log", "qs_last_score_estimate", "qs_score_prepare",
     "qs_sum_words", "qs_issue_probe", "qs_last_count_fix_ms", "qs_batch_clamp_info", "qs_depth_clamp_plan", "qs_score_check", "qs_last_count_events", "qs_class_plan", "qs_shard_bounds",
     "qs_table_remap", "qs_tree_agreement", "qs_taxon_support", "qs_table_restrict", "qs_taxon_placement", "qs_placement_scores", "qs_clade_placement",
-    "qs_last_count_split", "qs_fix_overlap_plan", "qs_group_check", "qs_group_support",
+    "qs_last_count_split", "qs_fix_overlap_plan", "qs_group_check", "qs_group_support", "qs_tree_pair_agreement",
 ]
 
 
@@ -114,6 +115,8 @@ def load():
     L.qs_table_restrict.argtypes = [vp, vp, vp]
     L.qs_tree_agreement.restype = i32
     L.qs_tree_agreement.argtypes = [vp, vp, vp, vp]
+    L.qs_tree_pair_agreement.restype = i32
+    L.qs_tree_pair_agreement.argtypes = [vp, vp, u32, u32, vp, u32, u32, u32, vp]
     L.qs_taxon_support.restype = i32
     L.qs_taxon_support.argtypes = [vp, vp, vp]
     L.qs_taxon_placement.restype = i32

@@ -24,6 +24,7 @@
 #include "QuartetScoreComputer.hpp"
 #include "multi_gpu.hpp"
 #include "table_shards.hpp"
+#include "tree_distances.hpp"
 
 #include <cerrno>
 #include <map>
@@ -73,6 +74,7 @@ struct WithoutTaxa {
 struct Args {
     std::string ref, eval, out, raw, raw_bin;
     std::string per_tree;   // --per-tree FILE: quartet agreement of every evaluation tree with -r (TSV)
+    std::string tree_distances;   // --tree-distances FILE: quartet agreement and distance of every pair of evaluation trees (TSV)
     std::string per_taxon;  // --per-taxon FILE: quartet support per taxon of -r from the count table (TSV)
     std::string place_taxa; // --place-taxa FILE: quartet placement of the taxa of -r from the count table (TSV)
     std::string place_only; // --place-only NAMES: a file of the taxon labels to place (default: all)
@@ -145,6 +147,13 @@ void usage(std::ostream &os) {
           "                  -e order after a header: tree taxa quartets concordant discordant eval_only ref_only unresolved\n"
           "                  concordance); computed on the device behind the counting; one GPU that counts (not with --gpus /\n"
           "                  --table-shards / --load-table)\n"
+          "   --tree-distances F  write the quartet agreement of every PAIR of evaluation trees to F (TSV, one line per pair a < b in\n"
+          "                  row-major order of their -e numbers after a header: a b taxa quartets concordant discordant a_only b_only\n"
+          "                  unresolved concordance distance). taxa = the taxa both trees hold, quartets = the 4-sets of those; both\n"
+          "                  trees are restricted to them. distance = (discordant + a_only + b_only) / quartets, the normalised quartet\n"
+          "                  distance that takes \"unresolved\" as a topology of its own; nan where quartets = 0. Needs no -r tree beyond\n"
+          "                  its taxon names; computed on the device after the counting, m (m - 1) / 2 lines for m trees; one GPU that\n"
+          "                  counts (not with --gpus / --table-shards / --load-table); works with --per-tree and beside the other outputs\n"
           "   --per-taxon F  write, per taxon of the -r tree, the support its quartets get from the count table to F (TSV, one line per\n"
           "                  taxon in lookup-id order after a header: taxon name quartets ref_resolved concordant discordant eval_only\n"
           "                  outvoted uninformed concordance concordance_without); one more read of the table on the device; a taxon\n"
@@ -258,6 +267,7 @@ int parse(int argc, char **argv, Args &a) {
         else if (f == "--save-table") { if (!(v = need(i, "--save-table"))) return 1; a.dev.save_table = v; }
         else if (f == "--qic-binary") { if (!(v = need(i, "--qic-binary"))) return 1; a.raw_bin = v; }
         else if (f == "--per-tree") { if (!(v = need(i, "--per-tree"))) return 1; a.per_tree = v; }
+        else if (f == "--tree-distances") { if (!(v = need(i, "--tree-distances"))) return 1; a.tree_distances = v; }
         else if (f == "--per-taxon") { if (!(v = need(i, "--per-taxon"))) return 1; a.per_taxon = v; }
         else if (f == "--place-taxa") { if (!(v = need(i, "--place-taxa"))) return 1; a.place_taxa = v; }
         else if (f == "--place-only") { if (!(v = need(i, "--place-only"))) return 1; a.place_only = v; }
@@ -415,6 +425,18 @@ void check_per_tree(const Args &a) {
     if (std::ifstream(a.per_tree).good()) throw std::runtime_error("--per-tree: the output file " + a.per_tree + " already exists");
 }
 
+// --tree-distances: refused like --per-tree, before the device is touched
+void check_tree_distances(const Args &a) {
+    if (a.tree_distances.empty()) return;
+    if (a.gpus > 0 || a.table_shards >= 0 || !a.dev.load_table.empty())
+        throw std::runtime_error("--tree-distances needs the evaluation trees counted on one GPU: omit --gpus / --table-shards / --load-table");
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.place_clades, a.test_groups};
+    for (const AlsoRef &x : a.also) others.insert(x.out);
+    for (const WithoutTaxa &x : a.without) others.insert(x.out);
+    if (others.count(a.tree_distances)) throw std::runtime_error("--tree-distances: " + a.tree_distances + " is also another output file");
+    if (std::ifstream(a.tree_distances).good()) throw std::runtime_error("--tree-distances: the output file " + a.tree_distances + " already exists");
+}
+
 // --per-tree: qs_tree_agreement behind every batch's count into one device buffer of 4 x m words, downloaded once after the last
 // qs_sync; taxa per tree from the flattened batches
 struct PerTree {
@@ -425,7 +447,7 @@ struct PerTree {
     std::vector<uint32_t> taxa;
     void hook(DeviceOptions &opt, const RefFlat &ref) {
         taxa.assign(m, 0);
-        opt.after_count = [this, &ref](qs_ctx *ctx, const qs_device_batch *db, size_t i0, const BatchFlat &b) {
+        add_after_count(opt, [this, &ref](qs_ctx *ctx, const qs_device_batch *db, size_t i0, const BatchFlat &b) {
             if (!dev) {
                 if (hipSetDevice(device) != hipSuccess || dev.reserve(std::max<size_t>(1, 4 * m) * 8, nullptr) != hipSuccess)
                     throw std::runtime_error("--per-tree: Insufficient memory!");
@@ -433,12 +455,12 @@ struct PerTree {
             for (uint32_t t = 0; t < b.n_trees; ++t) taxa[i0 + t] = b.leaf_off[t + 1] - b.leaf_off[t];
             const qs_ref_tree rt = ref_view(ref);
             if (qs_tree_agreement(ctx, &rt, db, dev.get() + 4 * i0) != QS_OK) throw std::runtime_error(qs_last_error(ctx));
-        };
-        opt.after_sync = [this](qs_ctx *) {
+        });
+        add_after_sync(opt, [this](qs_ctx *) {
             counts.assign(4 * m, 0);
             if (m && hipMemcpy(counts.data(), dev.get(), 4 * m * 8, hipMemcpyDeviceToHost) != hipSuccess)
                 throw std::runtime_error("--per-tree: download failed");
-        };
+        });
     }
     void write(const std::string &path) const {
         std::ofstream f(path);
@@ -983,6 +1005,11 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
         dev.per_tree = a.per_tree;
         per_tree.hook(dev, per_tree_ref);
     }
+    TreeDistances tree_distances;
+    if (!a.tree_distances.empty()) {
+        dev.tree_distances = a.tree_distances;
+        tree_distances.hook(dev);
+    }
     std::unique_ptr<QuartetScoreComputer<CINT>> holder(new QuartetScoreComputer<CINT>(referenceTree, a.eval, m, a.verbose, a.savemem, dev));
     QuartetScoreComputer<CINT> &qsc = *holder;
     lqic = qsc.getLQICScores();
@@ -993,6 +1020,7 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
     if (!a.raw.empty()) qsc.printRawQICScores(a.raw);
     if (!a.raw_bin.empty()) qsc.printRawQICBinary(a.raw_bin);
     if (!a.per_tree.empty()) per_tree.write(a.per_tree);
+    if (!a.tree_distances.empty()) tree_distances.write(qsc.context(), a.dev.device, a.tree_distances);
     if (!a.per_taxon.empty()) write_per_taxon(qsc.context(), qsc.reference(), a.dev.device, a.per_taxon);
     if (!a.place_taxa.empty()) write_place_taxa(qsc.context(), qsc.reference(), a.dev.device, a.place_taxa, a.place_ids);
     if (!a.place_clades.empty()) write_place_clades(qsc.context(), qsc.reference(), a.dev.device, a.place_clades, a.place_nodes);
@@ -1024,6 +1052,7 @@ int main(int argc, char *argv[]) {
         check_also_refs(a);
         check_without_taxa(a);
         check_per_tree(a);
+        check_tree_distances(a);
         check_per_taxon(a);
         check_place_taxa(a);
         check_place_clades(a);

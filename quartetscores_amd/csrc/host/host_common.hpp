@@ -35,10 +35,24 @@ struct DeviceOptions {
     std::string load_table, save_table; // count-table persistence
     bool trace = false;          // --trace: time stamps of the counting pipeline on stderr
     std::string per_tree;        // --per-tree FILE: batches carry their node ranges (qs_tree_agreement reads them)
-    // called behind every batch's qs_count_batch (first tree of the batch, the flattened batch) and behind the final qs_sync
+    std::string tree_distances;  // --tree-distances FILE: likewise (qs_tree_pair_agreement reads them)
+    // called behind every batch's qs_count_batch (first tree of the batch, the flattened batch) and behind the final qs_sync;
+    // several features share them through add_after_count / add_after_sync
     std::function<void(qs_ctx *, const qs_device_batch *, size_t, const BatchFlat &)> after_count;
     std::function<void(qs_ctx *)> after_sync;
 };
+
+// one more callback behind those the option already holds, in the order they were added
+inline void add_after_count(DeviceOptions &opt, std::function<void(qs_ctx *, const qs_device_batch *, size_t, const BatchFlat &)> f) {
+    if (!opt.after_count) { opt.after_count = std::move(f); return; }
+    auto first = std::move(opt.after_count);
+    opt.after_count = [first, f](qs_ctx *ctx, const qs_device_batch *db, size_t i0, const BatchFlat &b) { first(ctx, db, i0, b); f(ctx, db, i0, b); };
+}
+inline void add_after_sync(DeviceOptions &opt, std::function<void(qs_ctx *)> f) {
+    if (!opt.after_sync) { opt.after_sync = std::move(f); return; }
+    auto first = std::move(opt.after_sync);
+    opt.after_sync = [first, f](qs_ctx *ctx) { first(ctx); f(ctx); };
+}
 
 // --trace: "[trace] +12.3 ms  what" relative to the first call (process start for practical purposes)
 inline void trace_mark(const DeviceOptions &opt, const char *what) {

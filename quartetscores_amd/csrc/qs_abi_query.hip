@@ -1,6 +1,7 @@
 // qs_abi_query.hip -- what reads a finished table and is not the score: per-taxon support, taxon and clade placement, per-tree
-// agreement (against a reference tree) and the support of taxon groups (against none). Host code only; the kernels are in qs_taxon.hip,
-// qs_place.hip, qs_place_clade.hip, qs_agree.hip and qs_groups.hip.
+// agreement (against a reference tree), the agreement of the evaluation trees with each other and the support of taxon groups (against
+// none). Host code only; the kernels are in qs_taxon.hip, qs_place.hip, qs_place_clade.hip, qs_agree.hip, qs_agree_pairs.hip and
+// qs_groups.hip.
 #include "qs_ctx.hpp"
 #include "qs_plan.hpp"
 
@@ -365,6 +366,34 @@ extern "C" int qs_tree_agreement(qs_ctx *c, const qs_ref_tree *ref, const qs_dev
     QS_HIP(c, hipSetDevice(c->device));
     if (d.ready) QS_HIP(c, hipStreamWaitEvent(c->stream, d.ready, 0));
     QS_HIP(c, launch_tree_agree(c->stream, d, c->n, d.max_tree_nodes, c->agree_off.get(), c->agree_bnd.get(), c->agree_par.get(), c->agree_n_u,
+                                reinterpret_cast<unsigned long long *>(dst_device)));
+    return QS_OK;   // asynchronous on the context's stream
+}
+
+// Quartet agreement of the trees of one batch with those of another, or of a batch with itself (qs_agree_pairs.hip). The reference never
+// compares the evaluation trees with each other: this replaces nothing there.
+extern "C" int qs_tree_pair_agreement(qs_ctx *c, const qs_device_batch *rows, uint32_t r0, uint32_t r1, const qs_device_batch *cols,
+                                      uint32_t c0, uint32_t c1, uint32_t flags, uint64_t *dst_device) {
+    if (!c) return QS_ERR_ARG;
+    if (!rows || !cols || !dst_device) return fail(c, QS_ERR_ARG, "qs_tree_pair_agreement: NULL argument");
+    if (c->d_lo != 0 || c->d_hi != c->n)
+        return fail(c, QS_ERR_UNSUPPORTED, "qs_tree_pair_agreement: whole-table contexts only (no table shards)");
+    if (reinterpret_cast<uintptr_t>(dst_device) % 8) return fail(c, QS_ERR_ARG, "qs_tree_pair_agreement: dst_device is not 8-byte aligned");
+    if (flags & ~QS_PAIRS_UPPER) return fail(c, QS_ERR_ARG, "qs_tree_pair_agreement: unknown flag");
+    if ((flags & QS_PAIRS_UPPER) && rows != cols) return fail(c, QS_ERR_ARG, "qs_tree_pair_agreement: QS_PAIRS_UPPER needs rows and cols to be the same batch");
+    const DeviceBatch &dr = rows->d, &dc = cols->d;
+    if (r0 > r1 || r1 > dr.n_trees) return fail(c, QS_ERR_ARG, "qs_tree_pair_agreement: the row range is not within the batch");
+    if (c0 > c1 || c1 > dc.n_trees) return fail(c, QS_ERR_ARG, "qs_tree_pair_agreement: the column range is not within the batch");
+    if ((dr.n_trees && !dr.node_off) || (dc.n_trees && !dc.node_off))
+        return fail(c, QS_ERR_STATE, "qs_tree_pair_agreement: a batch was uploaded without node ranges");
+    const uint64_t n_pairs = (uint64_t)(r1 - r0) * (c1 - c0);
+    if (n_pairs > (1ull << 28)) return fail(c, QS_ERR_ARG, "qs_tree_pair_agreement: more than 2^28 pairs in one call");
+    if (n_pairs == 0) return QS_OK;
+    QS_HIP(c, hipSetDevice(c->device));
+    QS_HIP(c, c->pair_pos.reserve(tree_pairs_work_words(dr, r1 - r0, c->n) * sizeof(uint16_t), &c->stream));
+    if (dr.ready) QS_HIP(c, hipStreamWaitEvent(c->stream, dr.ready, 0));
+    if (dc.ready && rows != cols) QS_HIP(c, hipStreamWaitEvent(c->stream, dc.ready, 0));
+    QS_HIP(c, launch_tree_pairs(c->stream, dr, r0, r1, dc, c0, c1, (flags & QS_PAIRS_UPPER) != 0, c->n, c->pair_pos.get(),
                                 reinterpret_cast<unsigned long long *>(dst_device)));
     return QS_OK;   // asynchronous on the context's stream
 }

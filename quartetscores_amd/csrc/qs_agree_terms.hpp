@@ -1,0 +1,84 @@
+// qs_agree_terms.hpp -- the node-pair closed forms of the quartet agreement of two trees, shared by the kernels that
+// compare the evaluation trees with the reference (qs_agree.hip) and with each other (qs_agree_pairs.hip). Device code only.
+#pragma once
+#include "qs_common.hpp"
+
+namespace qs {
+
+__device__ __forceinline__ long long c2(long long x) { return x * (x - 1) / 2; }
+
+// ids < x among the entries of one LDS bitmap (W words of {bits, popcount of the words before})
+__device__ __forceinline__ int bm_count(const uint2 *bm, uint32_t x) {
+    const uint2 e = bm[x >> 5];
+    return (int)e.y + __popc(e.x & ((1u << (x & 31)) - 1u));
+}
+
+struct ClaimSums {
+    long long sm = 0;   // sum over node pairs of same + mixed = 4 x concordant
+    long long dc = 0;   // 4 x discordant
+};
+
+// One node pair: I(r,c), row sizes R(r), column sizes C(c) as accessors (r < K, c < Lc). Row and column aggregates are
+// recomputed where they are needed, so nothing of size K or Lc is stored: O(K Lc (1 + K)) accessor calls, so K should be
+// the shorter side.
+template <class IF, class RF, class CF>
+__device__ __forceinline__ void pair_terms(int K, int Lc, IF I, RF R, CF C, long long N, ClaimSums &acc) {
+    long long T2 = 0;
+    for (int r = 0; r < K; ++r)
+        for (int c = 0; c < Lc; ++c) T2 += c2(I(r, c));
+    long long sm = 0, dc = 0;
+    for (int r = 0; r < K; ++r) {
+        const long long Rr = R(r);
+        long long rowC2 = 0, rowX = 0, rowIC = 0, rowSq = 0;
+        for (int c = 0; c < Lc; ++c) {
+            const long long x = I(r, c), Cc = C(c);
+            rowC2 += c2(x); rowX += c2(Cc - x); rowIC += x * Cc; rowSq += x * x;
+        }
+        for (int c = 0; c < Lc; ++c) {
+            const long long x = I(r, c), Cc = C(c);
+            long long colC2 = 0, colX = 0, colIR = 0, colSq = 0;
+            for (int i = 0; i < K; ++i) {
+                const long long y = I(i, c), Ri = R(i);
+                colC2 += c2(y); colX += c2(Ri - y); colIR += y * Ri; colSq += y * y;
+            }
+            const long long ci = c2(x), X = N - Rr - Cc + x, A = Rr - x, B = Cc - x;
+            const long long D = c2(X) - (colX - c2(A)) - (rowX - c2(B)) + (T2 - rowC2 - colC2 + ci);
+            sm += ci * D + (c2(A) - (rowC2 - ci)) * (c2(B) - (colC2 - ci));
+            if (x) dc += x * (X * A * B - A * (colIR - x * Rr) - (rowIC - x * Cc) * B + (rowSq - x * x) * B + A * (colSq - x * x));
+        }
+    }
+    // sum over r != i, c != j of I_rc I_rj I_ic I_ij, along the shorter side
+    if (K <= Lc) {
+        for (int r = 0; r < K; ++r)
+            for (int i = r + 1; i < K; ++i) {
+                long long G = 0, H = 0;
+                for (int c = 0; c < Lc; ++c) { const long long a = I(r, c), b = I(i, c); G += a * b; H += a * a * b * b; }
+                dc += 2 * (G * G - H);
+            }
+    } else {
+        for (int c = 0; c < Lc; ++c)
+            for (int j = c + 1; j < Lc; ++j) {
+                long long G = 0, H = 0;
+                for (int r = 0; r < K; ++r) { const long long a = I(r, c), b = I(r, j); G += a * b; H += a * a * b * b; }
+                dc += 2 * (G * G - H);
+            }
+    }
+    acc.sm += sm;
+    acc.dc += dc;
+}
+
+// 2 x the quartets one node resolves, from its link sizes
+template <class SF>
+__device__ __forceinline__ long long node_resolved2(int K, SF S, long long N) {
+    long long s2 = 0, out = 0;
+    for (int r = 0; r < K; ++r) s2 += c2(S(r));
+    for (int r = 0; r < K; ++r) { const long long x = S(r); out += c2(x) * (c2(N - x) - (s2 - c2(x))); }
+    return out;
+}
+
+__device__ __forceinline__ void wave_add(unsigned long long *dst, long long v) {
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    if ((threadIdx.x % kWave) == 0 && v) atomicAdd(dst, (unsigned long long)v);
+}
+
+}  // namespace qs

@@ -166,6 +166,8 @@ struct qs_ctx {
     DevBuf<uint16_t> agree_bnd;
     DevBuf<uint8_t> agree_par;
     uint32_t agree_n_u = 0;
+    // qs_tree_pair_agreement: the position maps and node orders of the last call's row trees (tree_pairs_work_words; grown, never shrunk)
+    DevBuf<uint16_t> pair_pos;
     // qs_taxon_placement: the cached reference tree's link lookups (dropped with ref_lca_dev), the walks of an n-taxon table and
     // the list of the last call; the host copies stay until the uploads on `stream` have read them
     std::vector<uint16_t> place_child, place_next, place_taxa;

@@ -152,6 +152,16 @@ hipError_t launch_table_restrict(hipStream_t s, const void *src, int src_bits, v
 // links as id boundaries (ref_off / ref_bnd, ref_par = has a parent link); dst = 4 words per tree of the batch
 hipError_t launch_tree_agree(hipStream_t s, const DeviceBatch &b, uint32_t n, uint32_t max_tree_nodes, const uint32_t *ref_off,
                              const uint16_t *ref_bnd, const uint8_t *ref_par, uint32_t n_u, unsigned long long *dst);
+// LDS plan of an agreement launch for n taxa: W words per bitmap, the link budget of one round, the inner nodes of one workgroup
+void agree_plan(uint32_t n, uint32_t &W, uint32_t &cap, uint32_t &nb);
+// qs_agree_pairs.hip: quartet agreement of the trees [r0, r1) of `rows` with the trees [c0, c1) of `cols` (qs_tree_pair_agreement);
+// both batches uploaded with node ranges; upper: the two are one batch, pairs with column index <= row index are skipped; work =
+// tree_pairs_work_words(...) 16-bit words of workspace (the row trees' position maps and node orders); dst = kPairWords words per pair,
+// row-major, overwritten
+constexpr int kPairWords = 5;     // concordant, discordant, resolved_row, resolved_col, shared
+hipError_t launch_tree_pairs(hipStream_t s, const DeviceBatch &rows, uint32_t r0, uint32_t r1, const DeviceBatch &cols, uint32_t c0,
+                             uint32_t c1, bool upper, uint32_t n, uint16_t *work, unsigned long long *dst);
+inline size_t tree_pairs_work_words(const DeviceBatch &rows, uint32_t n_rows, uint32_t n) { return (size_t)n_rows * ((size_t)n + rows.max_tree_nodes); }
 // qs_taxon.hip: per-taxon sums over the whole rows of the rank range of a ScoreDevice (qs_taxon_support); needs sd.bundle_* =
 // plan_bundles with kTaxonWaves waves; dst = 6 words per taxon, zeroed beforehand; wide: counts may reach 2^32 / 192
 struct ScoreDevice;

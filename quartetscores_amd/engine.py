@@ -61,6 +61,27 @@ def agreement_columns(counts, taxa) -> dict:
             "unresolved": quartets - both - eval_only - ref_only, "concordance": concordance}
 
 
+PAIR_FIELDS = ("concordant", "discordant", "resolved_row", "resolved_col", "shared")
+
+
+def pair_columns(counts) -> dict:
+    """The derived columns of Context.tree_pair_agreement: counts (..., 5) uint64 in PAIR_FIELDS order -> dict of int64 arrays (of the
+    leading shape) shared, quartets = C(shared,4), concordant, discordant, row_only = resolved_row - concordant - discordant,
+    col_only likewise, unresolved = the rest, and the float64 arrays concordance = concordant / (concordant + discordant) (nan where
+    that sum is 0) and distance = (discordant + row_only + col_only) / quartets, the normalised quartet distance in which
+    "unresolved" is a topology of its own (nan where quartets = 0)."""
+    a = np.asarray(counts).astype(np.int64)
+    conc, disc, res_r, res_c, n = (a[..., k] for k in range(5))
+    quartets = np.where(n >= 4, n * (n - 1) * (n - 2) * (n - 3) // 24, 0)
+    row_only, col_only = res_r - conc - disc, res_c - conc - disc
+    both, differ = conc + disc, disc + row_only + col_only
+    with np.errstate(invalid="ignore", divide="ignore"):
+        concordance = np.where(both > 0, conc / np.maximum(both, 1), np.nan)
+        distance = np.where(quartets > 0, differ / np.maximum(quartets, 1), np.nan)
+    return {"shared": n, "quartets": quartets, "concordant": conc, "discordant": disc, "row_only": row_only, "col_only": col_only,
+            "unresolved": quartets - both - row_only - col_only, "concordance": concordance, "distance": distance}
+
+
 TAXON_FIELDS = ("ref_resolved", "concordant", "discordant", "eval_only", "outvoted", "uninformed")
 
 
@@ -439,6 +460,23 @@ class Context:
         self.sync()
         del keep
         return buf[: 4 * n_trees].cpu().numpy().view(np.uint64).reshape(n_trees, 4)
+
+    def tree_pair_agreement(self, hb_rows, hb_cols=None, rows=None, cols=None, upper=False) -> np.ndarray:
+        """qs_tree_pair_agreement: the quartet agreement of the trees rows = (r0, r1) of the uploaded batch `hb_rows` with the trees
+        cols = (c0, c1) of `hb_cols` (None = the same batch; None ranges = all trees; both batches uploaded with their node ranges)
+        -> uint64 (r1 - r0, c1 - c0, 5) in PAIR_FIELDS order (pair_columns derives the rest). upper: same batch only; the pairs with
+        column index <= row index are skipped and give zeros. Allocates the device buffer, waits for the result and downloads it."""
+        import torch
+        if hb_cols is None:
+            hb_cols = hb_rows
+        r0, r1 = rows if rows is not None else (0, self._batch_trees[hb_rows.value])
+        c0, c1 = cols if cols is not None else (0, self._batch_trees[hb_cols.value])
+        n_r, n_c = max(0, r1 - r0), max(0, c1 - c0)
+        buf = torch.empty(max(1, 5 * n_r * n_c), dtype=torch.int64, device=f"cuda:{self.device}")
+        self._chk(self.L.qs_tree_pair_agreement(self.h, hb_rows, r0, r1, hb_cols, c0, c1, _lib.QS_PAIRS_UPPER if upper else 0,
+                                                C.c_void_p(buf.data_ptr())))
+        self.sync()
+        return buf[: 5 * n_r * n_c].cpu().numpy().view(np.uint64).reshape(n_r, n_c, 5)
 
     def taxon_support(self, ref: flatten.RefTree) -> np.ndarray:
         """qs_taxon_support: per taxon (lookup id) the six sums of TAXON_FIELDS over the 4-sets of this context's table (whole
