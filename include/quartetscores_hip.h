@@ -229,6 +229,14 @@ const char *qs_last_error(const qs_ctx *ctx); /* ctx may be NULL: message of the
                                        * of eight; what "late" buys there is the fifth wave, not a shorter distance) or behind the last (5 bits). 0 (default) = automatic: late
                                        * loads for the instances measured faster that way (4 bits), prefetch for all others. Same table. The
                                        * variant string names a late instance that ran as a segment /late<waves>. Other classes: no effect. */
+#define QS_TUNE_STAGE_SIX 22u         /* count_bitslice3_kernel, binary_full classes of 4 depth bits (u32 and u16 cells, wire format): the instance held to SIX
+                                       * waves per SIMD (<= 80 VGPRs). Its step stages the next group's M[b,d], M[c,d] and M[x,c] elements by loads that
+                                       * write LDS directly (a raw area per wave, one LDS image instead of two), so the request holds no register and
+                                       * stands at the top of the step, behind L1 / L2. 1 = never: the instances QS_TUNE_STEP_ORDER selects, exactly as
+                                       * without this key. 2 = the six-wave instance wherever it exists, whatever QS_TUNE_STEP_ORDER says. 0 (default) =
+                                       * automatic: with QS_TUNE_STEP_ORDER at 0 the six-wave instance for the classes measured faster with it, else as 1;
+                                       * an explicit QS_TUNE_STEP_ORDER of 1 or 2 is obeyed. Same table. The variant string names the instance that
+                                       * ran as a segment /dma<waves> where /late<waves> stands otherwise. Other classes: no effect. */
 #define QS_TUNE_CLASS_MIN_TREES 16u   /* ... and the absolute floor of a class (default 1024 trees; tests lower it to split small batches) */
 #define QS_TUNE_SCORE_LOAD 14u        /* bundle score kernel, shape of the table loads: 0 (default) = every lane loads its own row in 16-byte pieces;
                                        * 2 = ... and requests the next chunk before it processes the current one; 1 = eight lanes load the

@@ -26,6 +26,7 @@ QS_TUNE_DEPTH_CLAMP = 17
 QS_TUNE_FUSE_CLASSES = 18
 QS_TUNE_FIX_OVERLAP, QS_TUNE_FIX_SPLIT_AT = 19, 20
 QS_TUNE_STEP_ORDER = 21   # 0 = automatic, 1 = prefetch, 2 = late loads (binary_full classes of 4 / 5 depth bits)
+QS_TUNE_STAGE_SIX = 22    # 0 = automatic, 1 = the instances QS_TUNE_STEP_ORDER selects, 2 = the six-wave (LDS-DMA) instance (binary_full, 4 depth bits)
 QS_CLASS_PLAN_FUSED = 0x100
 QS_IMPL_AUTO, QS_IMPL_SWAR, QS_IMPL_BITSLICE = 0, 1, 2
 QS_SHARDS_BY_TUPLES, QS_SHARDS_BY_COST = 0, 1

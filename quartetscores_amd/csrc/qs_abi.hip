@@ -63,6 +63,9 @@ extern "C" int qs_set_tuning(qs_ctx *c, uint32_t key, uint64_t value) {
         case QS_TUNE_STEP_ORDER:
             if (value > 2) return fail(c, QS_ERR_ARG, "qs_set_tuning: QS_TUNE_STEP_ORDER takes 0 (automatic), 1 (prefetch) or 2 (late loads)");
             c->tune_step_order = (uint32_t)value; return QS_OK;
+        case QS_TUNE_STAGE_SIX:
+            if (value > 2) return fail(c, QS_ERR_ARG, "qs_set_tuning: QS_TUNE_STAGE_SIX takes 0 (automatic), 1 (the instances QS_TUNE_STEP_ORDER selects) or 2 (the six-wave instance)");
+            c->tune_stage_six = (uint32_t)value; return QS_OK;
         case QS_TUNE_CLASS_PCT: if (value > 100) return fail(c, QS_ERR_ARG, "qs_set_tuning: QS_TUNE_CLASS_PCT takes 0 .. 100"); c->tune_class_pct = (uint32_t)value; return QS_OK;
         case QS_TUNE_SCORE_LOAD:
             if (value > 3) return fail(c, QS_ERR_ARG, "qs_set_tuning: QS_TUNE_SCORE_LOAD takes 0 .. 3");

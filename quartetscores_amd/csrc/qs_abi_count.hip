@@ -538,6 +538,25 @@ static int step_order_late_waves(uint32_t knob, int mode, int depth_bits, int ce
     return 0;
 }
 
+// QS_TUNE_STAGE_SIX: the six-wave instance (bitslice3_six_waves; the dma order). 2 = wherever it exists, 1 = never, 0 = automatic: where
+// QS_TUNE_STEP_ORDER is automatic too, exactly the instances listed here; an explicit step order is obeyed. A row as in kLateAuto, measured
+// against the five-wave late instance the class took before (profiles/r15_stage_dma.md; the same bar).
+static constexpr LateAuto kSixAuto[] = {
+    {MODE_BINARY_FULL, 4, 32, "512 taxa x 10000 trees, late at five waves -> dma at six: 282.58 / 283.13 / 283.32 -> 278.36 / 279.18 / 278.92 (-1.5 %, 5.6 spreads); "
+                              "on a second box 292.68 / 292.91 / 293.96 -> 290.04 / 290.05 / 290.38 (-1.0 %, 2.4 spreads: every run below, the bar missed there); "
+                              "128 x 1000: 0.1596 / 0.1603 / 0.1586 -> 0.1577 / 0.1584 / 0.1579 (-0.9 %); 256 x 12500: 24.35 / 24.39 / 24.55 -> 24.03 / 24.02 / 24.05 (-1.6 %)"},
+    {MODE_BINARY_FULL, 4, 16, "1024 taxa x 5000 trees, shard 0 of 8: 313.49 / 312.71 -> 306.49 / 306.90 (-2.0 %)"},
+};
+// waves per SIMD of the six-wave instance the class takes; 0 = it takes what step_order_late_waves says
+static int stage_six_waves(uint32_t six_knob, uint32_t order_knob, int mode, int depth_bits, int cell_bits) {
+    const int w = six_knob == 1 ? 0 : bitslice3_six_waves(mode, depth_bits);
+    if (!w || six_knob == 2) return w;
+    if (order_knob != 0) return 0;
+    for (const LateAuto &e : kSixAuto)
+        if (e.mode == mode && e.bits == std::max(depth_bits, 4) && e.cell_bits == cell_bits) return w;
+    return 0;
+}
+
 // Enqueue one launch, slice by slice (slice_groups over the concatenated group list [0, g_total) of its segments; slice [g0, g1)
 // takes from every segment the groups that fall into it): panel build(s), count kernel, depth-clamp corrections, and with
 // `timed` an event after each of the three. Into the table, or (wire != NULL) the two-cell wire words.
@@ -613,10 +632,13 @@ static int run_launch(qs_ctx *c, const qs_device_batch *b, const Launch &L, uint
                 return launch_count_bitslice3_fused(c->stream, gg, seg_panel, seg_groups, seg_trees, L.bits, c->table, (int)c->count_bits, c->dev_flags.get(), ow);
             if (L.kernel == KERNEL_BITSLICE3) {
                 // (the cooperative lists send only the rest tiles through this kernel: they keep the prefetch order)
-                const int lw = gg.perm_coop ? 0 : step_order_late_waves(c->tune_step_order, mode0, L.bits, wire ? 32 : (int)c->count_bits);
+                const int cell_bits = wire ? 32 : (int)c->count_bits;
+                const int sw = gg.perm_coop ? 0 : stage_six_waves(c->tune_stage_six, c->tune_step_order, mode0, L.bits, cell_bits);
+                const int lw = (gg.perm_coop || sw) ? 0 : step_order_late_waves(c->tune_step_order, mode0, L.bits, cell_bits);
+                if (sw) c->last_six_waves = (uint32_t)sw;
                 if (lw) c->last_late_waves = (uint32_t)lw;
                 return launch_count_bitslice3(c->stream, gg, seg_panel[mode0], L.bits, mode0, seg_groups[mode0], seg_trees[mode0], wire ? nullptr : c->table,
-                                              wire ? 32 : (int)c->count_bits, c->dev_flags.get(), ow, wire, lw != 0);
+                                              cell_bits, c->dev_flags.get(), ow, wire, sw ? 2 : lw ? 1 : 0);
             }
             return launch_count_gather(c->stream, gg, seg_panel[mode0], L.bits, mode0, seg_groups[mode0], seg_trees[mode0], c->table, (int)c->count_bits, c->dev_flags.get(), ow);
         };
@@ -696,7 +718,7 @@ static int count_batch_wire(qs_ctx *c, const qs_device_batch *b, uint32_t algo) 
         return fail(c, QS_ERR_OVERFLOW, "QS_COUNT_WIRE16X2: more than 65535 trees do not fit 16-bit cells");
     if (d.class_bits[d.n_classes - 1] > 10) return fail(c, QS_ERR_UNSUPPORTED, "QS_COUNT_WIRE16X2: tree depth needs more than 10 bits; count into the table instead");
     { const uint32_t *order; int rc_o = tile_order(c, &order); if (rc_o != QS_OK) return rc_o; }   // (a failure here leaves the last call's events as they were)
-    c->ev_used = 0; c->last_split = c->last_splits = 0; c->last_late_waves = 0;
+    c->ev_used = 0; c->last_split = c->last_splits = 0; c->last_late_waves = c->last_six_waves = 0;
     if (timed) QS_HIP(c, mark(c, 0));
     bool first = true;
     c->variant = "gather/binary_full/bitslice_";
@@ -708,6 +730,7 @@ static int count_batch_wire(qs_ctx *c, const qs_device_batch *b, uint32_t algo) 
         c->variant += (k ? "+" : "") + class_name(L, L.segs[0], false, nullptr, d.n_classes > 1);
     }
     c->variant += "/wire_u16x2";
+    if (c->last_six_waves) c->variant += std::string("/") + bitslice3_six_name() + std::to_string(c->last_six_waves);
     if (c->last_late_waves) c->variant += "/late" + std::to_string(c->last_late_waves);
     if (d.n_fix) c->variant += "/clamp:" + std::to_string(d.clamped_trees);
     if (c->last_splits) c->variant += "/overlap:" + std::to_string(c->last_split);
@@ -742,7 +765,7 @@ extern "C" int qs_count_batch(qs_ctx *c, const qs_device_batch *b, uint32_t algo
     if (overwrite && algo != QS_ALGO_GATHER) return fail(c, QS_ERR_ARG, "qs_count_batch: QS_COUNT_OVERWRITE needs the gather algorithm");
     // (a call refused before its first launch leaves table and count as they were; run_launch resets trees_counted with the first
     // overwriting launch it enqueues, so that a refusal after it -- a later class too deep, a panel that cannot grow -- leaves no stale count)
-    c->ev_used = 0; c->last_split = c->last_splits = 0; c->last_late_waves = 0;
+    c->ev_used = 0; c->last_split = c->last_splits = 0; c->last_late_waves = c->last_six_waves = 0;
     if (timed) QS_HIP(c, mark(c, 0));
     if (algo == QS_ALGO_GATHER) {
         static const char *mode_names[4] = {"binary_full", "general_full", "partial", "binary_partial"};
@@ -813,6 +836,7 @@ extern "C" int qs_count_batch(qs_ctx *c, const qs_device_batch *b, uint32_t algo
         c->variant = std::string("gather/") + (mixed ? "mixed" : mode_names[(!all_swar && d.class_bits[0] > top_bits && one_mode == MODE_BINARY_PARTIAL) ? (int)MODE_PARTIAL : one_mode]) + "/" + names + "/count_u" + std::to_string(c->count_bits);
         if (fused_launch_groups) c->variant += "/fused:" + std::to_string(fused_launch_groups);   // depth-bits groups whose classes shared a launch (count_bitslice3_fused_kernel)
         if (any_coop) c->variant += "/coop4";
+        if (c->last_six_waves) c->variant += std::string("/") + bitslice3_six_name() + std::to_string(c->last_six_waves);   // ... the six-wave instance (QS_TUNE_STAGE_SIX)
         if (c->last_late_waves) c->variant += "/late" + std::to_string(c->last_late_waves);   // a binary_full class ran the late-load instance (QS_TUNE_STEP_ORDER) at that many waves per SIMD
         if (!all_swar && d.n_fix) c->variant += "/clamp:" + std::to_string(d.clamped_trees);   // trees counted below their own depth bits + clamp_fix_kernel
         if (c->last_splits) c->variant += "/overlap:" + std::to_string(c->last_split);           // slices split at that largest id: corrections beside the lower count launch

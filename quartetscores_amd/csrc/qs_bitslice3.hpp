@@ -282,6 +282,23 @@ template <int B, int MODE> constexpr int bs3_late_waves() {
     return (MODE == MODE_BINARY_FULL && B <= QS_LATE_MAXB) ? QS_LATE_WAVES : 0;
 }
 
+// The step order of an instance (template parameter ORD of bs3_segment / count_bitslice3_kernel): prefetch, late loads, or the
+// SIX-wave instance of binary_full at 4 depth bits. What the sixth wave (<= 80 VGPRs) runs is a build setting:
+//   QS_SIX_DMA = 1: the "dma" order -- the staged panel elements M[b,d], M[c,d], M[x,c] (16 bytes each at 4 bits) go from the panel
+//                   straight into a lane-linear raw area of the wave's LDS region (buffer_load ... lds), so the request holds no
+//                   register and stands right behind L1 / L2, at the top of the step; ONE LDS image per wave (bs3_segment, step_dma);
+//   QS_SIX_DMA = 0: the late order with the request behind the last d-row (82 VGPRs unconstrained) held to 80.
+constexpr int kOrdPrefetch = 0, kOrdLate = 1, kOrdSix = 2;
+#ifndef QS_SIX_WAVES
+#define QS_SIX_WAVES 6    /* waves per SIMD of the kOrdSix instance */
+#endif
+#ifndef QS_SIX_DMA
+#define QS_SIX_DMA 1
+#endif
+template <int B, int MODE> constexpr int bs3_six_waves() { return (MODE == MODE_BINARY_FULL && B == 4) ? QS_SIX_WAVES : 0; }
+// raw area of the dma order, uint4 per wave: 64 x M[b,d] (lane = d-row * 8 + b-column), 8 x M[c,d], 16 x M[x,c]
+constexpr int kDmaY = 64, kDmaRow = 72, kDmaRaw = 88;
+
 constexpr int kWavesPerBlock = kCountThreads / kWave;   // 4: a workgroup = four independent wave tiles (consecutive in the launch order)
 
 // ======================================================================================
@@ -408,14 +425,18 @@ __device__ __forceinline__ int bs3_tile_variant(const Bs3Tile &t) {
     const bool full = t.jlo == 0 && t.jhi == (uint32_t)kDB;
     return t.has_a2 ? (full ? 0 : 1) : (t.offdiag ? 2 : 3);
 }
-// LATE: the step order of the instance (binary modes only): false = prefetch (`step`), true = late loads (`step_late`).
-template <int B, int MODE, int VAR = -1, bool LATE = false>
+// ORD: the step order of the instance (binary modes only): kOrdPrefetch (`step`), kOrdLate (`step_late`), kOrdSix (`step_dma` with its
+// raw area `raw`, kDmaRaw uint4 of this wave's own, and ONE image at `lds`; or `step_late` with the request behind the last row).
+template <int B, int MODE, int VAR = -1, int ORD = kOrdPrefetch>
 __device__ __forceinline__ void bs3_segment(const Bs3Tile &t, const uint4 *__restrict__ P, uint32_t npairs, uint32_t n_groups, uint32_t xcd_remap,
                                             uint4 *lds, uint32_t (&x0)[kDB], uint32_t (&x1)[kDB], uint32_t (&y0)[kDB], uint32_t (&y1)[kDB],
-                                            uint32_t (&z0)[kDB], uint32_t (&z1)[kDB]) {
+                                            uint32_t (&z0)[kDB], uint32_t (&z1)[kDB], uint4 *raw = nullptr) {
     using Lay = Bs3Layout<B, MODE>;
     constexpr bool BIN = Lay::BIN, GEN = Lay::GEN, PART = Lay::PART, BP = Lay::BP;
+    constexpr bool DMA = ORD == kOrdSix && QS_SIX_DMA, LATE = ORD == kOrdLate || (ORD == kOrdSix && !DMA);
+    constexpr int LROW = ORD == kOrdSix ? kDB : bs3_late_row<B>();   // in front of which d-row the late order requests the next group
     static_assert(!LATE || BIN, "the late-load step exists for the binary modes");
+    static_assert(ORD != kOrdSix || (MODE == MODE_BINARY_FULL && B == 4), "the six-wave instance: binary_full, 16-byte panel elements");
     constexpr int RC = Lay::RC, kS3Row0 = Lay::kS3Row0, kS3Slots = Lay::kS3Slots, NBUF = Lay::NBUF, NB = Lay::NB, NW = Lay::NW, HW = Lay::HW, PW = Lay::PW;
     uint4 *buf0 = lds, *buf1 = lds + (NBUF - 1) * Lay::kImg;
     const uint32_t lane = t.lane, c = t.c, d0 = t.d0, d1 = t.d1, jlo = t.jlo, jhi = t.jhi, blk0 = t.blk0, blk1 = t.blk1, blkB = t.blkB;
@@ -618,7 +639,7 @@ __device__ __forceinline__ void bs3_segment(const Bs3Tile &t, const uint4 *__res
     // registers). Behind the asm the rows are immediate offsets from two bases -- given as constant indices from the byte offsets
     // (rload): from an opaque COLUMN the compiler rebuilds every row address with an add (+17 VALU instructions per step, 8 %).
     uint32_t colA_o = colA1_, colB_o = colB_, bLo_o = colB_ * 16u, bHi_o = colB_ * (uint32_t)(HW * 4);
-    if (LATE) asm volatile("" : "+v"(colA_o), "+v"(colB_o), "+v"(bLo_o), "+v"(bHi_o));
+    if (LATE || DMA) asm volatile("" : "+v"(colA_o), "+v"(colB_o), "+v"(bLo_o), "+v"(bHi_o));
     auto step_late = [&](uint32_t g_next, const uint4 *cur, uint4 *nxt, Planes &ab1, Planes &ab2, auto a2_tag, auto full_tag, auto nr_tag) {
         constexpr bool A2 = decltype(a2_tag)::value, FULL = decltype(full_tag)::value;
         constexpr int NR = decltype(nr_tag)::value;
@@ -667,11 +688,11 @@ __device__ __forceinline__ void bs3_segment(const Bs3Tile &t, const uint4 *__res
         };
 #pragma unroll
         for (int j = 0; j < QS_PROBE_ROWS; ++j) {
-            if (j == bs3_late_row<B>()) request();
+            if (j == LROW) request();
             if (FULL || ((uint32_t)j >= jlo && (uint32_t)j < jhi)) bin_row(j, L1, L2, rload(j), a2_tag); // wave-uniform
         }
         if (QS_BIN_PRIO) __builtin_amdgcn_s_setprio(0);
-        if (bs3_late_row<B>() >= QS_PROBE_ROWS) request();
+        if (LROW >= QS_PROBE_ROWS) request();
         uint32_t s_0 = slot0, s_row = rowslot;
         if (NW > 4) asm volatile("" : "+v"(s_0), "+v"(s_row));
         lstore(nxt, s_0, sub_biased<B>(sx0, sy));
@@ -680,9 +701,117 @@ __device__ __forceinline__ void bs3_segment(const Bs3Tile &t, const uint4 *__res
         else lstore(nxt, s_row, srow);
     };
 
+    // The same step in the DMA order (binary_full, 16-byte elements). The staged elements never pass through registers:
+    //   dma_request: 64 lanes x M[b,d] -> raw[lane]; lanes 0..7 M[c,d] of d-row `lane`, lanes 8..23 M[x,c] of column lane - 8 ->
+    //                raw[64 + lane] (one instruction under an EXEC mask); the two M[ab] loads are ordinary ones into the ONE register set
+    //                (the second R block of a diagonal tile, whose instance has no second a-column, travels through registers);
+    //   dma_finish:  vmcnt(0), then the staging lanes read M[b,d] and M[c,d] from the raw area and store R into the ONE image.
+    // A wave reads only what its OWN DMA wrote, and only behind its own vmcnt(0); the LDS operations of a wave execute in order, so
+    // the image's stores stay behind the chains' reads, and the next request (which overwrites the raw area) is issued only after
+    // L1 / L2 have consumed the M[x,c] elements they read from it in place.
+    // Absent elements are requested at offset 0 (pair 0 of the group: inside the buffer) -- no cell that is stored depends on one:
+    // M[x,c] with x >= c belongs to lanes with v1 / v2 false, M[b,d] with b >= c likewise, and a d outside (c, d1) is a d-row that
+    // bs3_store skips. Nothing is ever read from a part of the raw area that no DMA of this wave has written (lanes 24..63 of the
+    // masked instruction write nothing and raw[88..] does not exist).
+    uint32_t o_dx = 0, o_dyr = 0;
+    if (DMA) {
+        o_dx = ok0 ? x0off : 0u;
+        const uint32_t dJ = d0 + lane, xr = lane - 8;   // lanes 0..7: d-row `lane`; lanes 8..23: row column lane - 8
+        uint32_t xa2 = 0xFFFFFFFFu;
+        if (xr < 8) xa2 = blk0 * kTA + xr;
+        else if (xr < 16 && blk1 != 0xFFFFFFFFu) xa2 = blk1 * kTA + (xr - 8);
+        if (lane < 8) o_dyr = (dJ < d1 && dJ > c) ? ((uint32_t)binom2(dJ) + c) * 16u : 0u;
+        else o_dyr = xa2 < c ? ((uint32_t)binom2(c) + xa2) * 16u : 0u;
+    }
+    typedef __attribute__((address_space(3))) void *lds_ptr_t;
+    // the lane's b-column in the image's two word arrays as LDS addresses (image base included), re-defined behind an empty asm for
+    // the reason given at the late order: the d-rows are immediate offsets from these two registers
+    typedef const __attribute__((address_space(3))) char *lds_cptr_t;
+    lds_cptr_t pLo = nullptr, pHi = nullptr;
+    if (DMA) {
+        pLo = (lds_cptr_t)lds + colB_ * 16u;
+        pHi = (lds_cptr_t)(lds + kS3Slots) + colB_ * (uint32_t)(HW * 4);
+        asm volatile("" : "+v"(pLo), "+v"(pHi));
+    }
+    auto raw_load = [&](uint32_t e) {
+        const uint4 v = raw[e];
+        Planes r;
+        r.w[0] = v.x; r.w[1] = v.y; r.w[2] = v.z; r.w[3] = v.w;
+#pragma unroll
+        for (int k = 4; k < kBitWords; ++k) r.w[k] = 0;
+        return r;
+    };
+    auto dma_request = [&](uint32_t g_next, Planes &ab1, Planes &ab2, Planes &sx1, auto a2_tag, auto nr_tag) {
+        __builtin_amdgcn_sched_barrier(0);
+        const __amdgpu_buffer_rsrc_t r = rsrc_of(g_next);
+        // The two DMA loads are written out: behind the builtin the compiler, which cannot tell the raw area from the image, waits for
+        // the DMA in front of the chains' first read of the IMAGE -- the whole latency exposed. Every offset lies inside the group
+        // (absent elements: pair 0), so the plain global form (scalar base + 32-bit lane offset) is in bounds. M0 = LDS destination
+        // of lane 0, saved and restored; s_nop 4: the scalar base may come straight from the SALU. The compiler does not count these
+        // loads: dma_finish waits for them (they are older than the M[ab] loads it does count, so its own waits stay sufficient).
+        const uint64_t gbase = (uint64_t)(reinterpret_cast<const char *>(P) + (size_t)g_next * group_bytes);
+        const uint32_t l_x = (uint32_t)(uintptr_t)(lds_ptr_t)raw, l_yr = (uint32_t)(uintptr_t)(lds_ptr_t)(raw + kDmaY);
+        uint32_t keep;
+        asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(o_dx), "s"(gbase), "s"(l_x) : "memory");
+        if (lane < 24)
+            asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                         : "=&s"(keep) : "v"(o_dyr), "s"(gbase), "s"(l_yr) : "memory");
+        if (decltype(nr_tag)::value >= 2) sx1 = gload(r, x1off);
+        ab1 = gload(r, ab1off);
+        if (decltype(a2_tag)::value) ab2 = gload(r, ab1off + (uint32_t)kTA * 16u);   // (as in the late order)
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto dma_finish = [&](const Planes &sx1, auto nr_tag) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const Planes sx0 = raw_load(lane), sy = raw_load(kDmaY + r_j);
+        lds_order<1>();   // one image: the chains' reads above, the stores of the next image below
+        lstore(lds, slot0, sub_biased<B>(sx0, sy));
+        if (decltype(nr_tag)::value >= 2) lstore(lds, slot0 + 8, sub_biased<B>(sx1, sy));
+        lds_order<1>();
+    };
+    auto step_dma = [&](uint32_t g_next, Planes &ab1, Planes &ab2, auto a2_tag, auto full_tag, auto nr_tag) {
+        constexpr bool A2 = decltype(a2_tag)::value, FULL = decltype(full_tag)::value;
+        if (xcd_remap & 2u) __builtin_amdgcn_s_barrier();   // waves of a workgroup in step: see `step`
+        const uint32_t colA = colA_o;
+        if (QS_BIN_PRIO) __builtin_amdgcn_s_setprio(1);
+        Planes L1 = sub_biased<B>(ab1, raw_load(kDmaRow + colA));
+        Planes L2 = L1, sx1 = L1;
+        if (A2) L2 = sub_biased<B>(ab2, raw_load(kDmaRow + kTA + colA));
+        // L1 / L2 are pinned in front of the request: the masked DMA is a branch, and the compiler otherwise sinks the two differences
+        // into the block behind it -- behind a wait for the DMA that has just been issued (the raw area is read AND written here)
+        asm volatile("" : "+v"(L1.w[0]), "+v"(L1.w[1]), "+v"(L1.w[2]), "+v"(L1.w[3]), "+v"(L1.w[4]));
+        if (A2) asm volatile("" : "+v"(L2.w[0]), "+v"(L2.w[1]), "+v"(L2.w[2]), "+v"(L2.w[3]), "+v"(L2.w[4]));
+        dma_request(g_next, ab1, ab2, sx1, a2_tag, nr_tag);
+#pragma unroll
+        for (int j = 0; j < kDB; ++j) {
+            if (FULL || ((uint32_t)j >= jlo && (uint32_t)j < jhi)) {   // wave-uniform
+                Planes r;   // R element of d-row j: constant offsets from the lane's two addresses
+                const qs_u32x4 lo = *reinterpret_cast<const __attribute__((address_space(3))) qs_u32x4 *>(pLo + j * RC * 16);
+                r.w[0] = lo.x; r.w[1] = lo.y; r.w[2] = lo.z; r.w[3] = lo.w;
+#pragma unroll
+                for (int k = 4; k < kBitWords; ++k) r.w[k] = 0;
+                r.w[4] = *reinterpret_cast<const __attribute__((address_space(3))) uint32_t *>(pHi + j * RC * 4);
+                bin_row(j, L1, L2, r, a2_tag);
+            }
+        }
+        if (QS_BIN_PRIO) __builtin_amdgcn_s_setprio(0);
+        dma_finish(sx1, nr_tag);
+    };
+
     auto run = [&](auto a2_tag, auto full_tag, auto nr_tag) {
         constexpr bool A2 = decltype(a2_tag)::value;
         constexpr int NR = decltype(nr_tag)::value;
+        if constexpr (DMA) {   // one M[ab] set, one image: a trip is one step
+            Planes ab1, ab2, sx1;
+#pragma unroll
+            for (int w = 0; w < kBitWords; ++w) ab2.w[w] = sx1.w[w] = 0;
+            dma_request(0, ab1, ab2, sx1, a2_tag, nr_tag);
+            dma_finish(sx1, nr_tag);
+            const uint32_t g_last = n_groups - 1;
+            for (uint32_t g = 0; g < n_groups; ++g) step_dma(min(g + 1, g_last), ab1, ab2, a2_tag, full_tag, nr_tag);   // past the end: re-reads the last group (unused)
+            return;
+        }
         Planes abA1, abA2, abB1, abB2;
 #pragma unroll
         for (int w = 0; w < kBitWords; ++w) abA2.w[w] = abB2.w[w] = 0;

@@ -720,10 +720,12 @@ uint32_t bitslice3_tiles_for_c(uint32_t c) {
 
 // One class of trees per launch: tile decode, the class's groups past the tile (bs3_segment), the tuples to the table. The mixed
 // batches' single launch over several classes is count_bitslice3_fused_kernel (qs_count_fused.hip).
-// LATE: the step order (bs3_segment) -- the register budget, and with it the occupancy, is a property of the instance.
-template <int B, int MODE, bool LATE> constexpr int bs3_kernel_waves() { return LATE ? bs3_late_waves<B, MODE>() : bs3_waves<B, MODE>(); }
-template <int B, int MODE, typename CT, bool LATE = false>
-__global__ __launch_bounds__(kCountThreads) __attribute__((amdgpu_waves_per_eu(bs3_kernel_waves<B, MODE, LATE>(), bs3_kernel_waves<B, MODE, LATE>()))) void count_bitslice3_kernel(const uint4 *__restrict__ P, uint32_t npairs,
+// ORD: the step order (bs3_segment) -- the register budget, and with it the occupancy, is a property of the instance.
+template <int B, int MODE, int ORD> constexpr int bs3_kernel_waves() {
+    return ORD == kOrdSix ? bs3_six_waves<B, MODE>() : ORD == kOrdLate ? bs3_late_waves<B, MODE>() : bs3_waves<B, MODE>();
+}
+template <int B, int MODE, typename CT, int ORD = kOrdPrefetch>
+__global__ __launch_bounds__(kCountThreads) __attribute__((amdgpu_waves_per_eu(bs3_kernel_waves<B, MODE, ORD>(), bs3_kernel_waves<B, MODE, ORD>()))) void count_bitslice3_kernel(const uint4 *__restrict__ P, uint32_t npairs,
                                                                         uint32_t n_groups, uint32_t m_trees,
                                                                         uint32_t d_start, uint32_t d_hi, uint64_t rank_lo,
                                                                         uint32_t n_dblk, uint32_t total_tiles,
@@ -733,15 +735,23 @@ __global__ __launch_bounds__(kCountThreads) __attribute__((amdgpu_waves_per_eu(b
                                                                         uint32_t *__restrict__ overflow_flag, uint32_t overwrite,
                                                                         uint32_t xcd_remap, uint32_t *__restrict__ wire,
                                                                         const uint32_t *__restrict__ perm) {
-    __shared__ uint4 stage_all[kWavesPerBlock][Bs3Layout<B, MODE>::kLdsUint4];
+    // the dma order keeps ONE image per wave and, in an array of its own, the raw area its loads write (two images and
+    // the raw area, 7.2 KB per wave, do not fit six waves per SIMD: 160 KB / 24 waves = 6.8 KB; one image and the raw area take 4.3 KB)
+    constexpr bool DMA = ORD == kOrdSix && QS_SIX_DMA;
+    __shared__ uint4 stage_all[kWavesPerBlock][DMA ? Bs3Layout<B, MODE>::kImg : Bs3Layout<B, MODE>::kLdsUint4];
+    uint4 *raw = nullptr;
     Bs3Tile t;
     if (!bs3_decode_tile(t, d_start, d_hi, n_dblk, total_tiles, dprefix, cprefix, xcd_remap, perm)) return;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+    if constexpr (DMA) {
+        __shared__ uint4 raw_all[kWavesPerBlock][kDmaRaw];
+        raw = raw_all[wave];
+    }
     // counters per d slot (see bs3_segment)
     uint32_t x0[kDB], x1[kDB], y0[kDB], y1[kDB], z0[kDB], z1[kDB];
 #pragma unroll
     for (int j = 0; j < kDB; ++j) x0[j] = x1[j] = y0[j] = y1[j] = z0[j] = z1[j] = 0;
-    bs3_segment<B, MODE, -1, LATE>(t, P, npairs, n_groups, xcd_remap, stage_all[wave], x0, x1, y0, y1, z0, z1);
+    bs3_segment<B, MODE, -1, ORD>(t, P, npairs, n_groups, xcd_remap, stage_all[wave], x0, x1, y0, y1, z0, z1, raw);
     constexpr int THIRD = MODE == MODE_BINARY_FULL ? 0 : MODE == MODE_BINARY_PARTIAL ? 1 : 2;
     bs3_store<CT, THIRD>(t, rank_lo, table, overflow_flag, overwrite, m_trees, MODE == MODE_BINARY_FULL ? wire : nullptr, x0, x1, y0, y1, z0, z1);
 }
@@ -970,12 +980,17 @@ int bitslice3_late_waves(int mode, int depth_bits) {
     const int b = depth_bits <= 4 ? 4 : depth_bits;
     return b == 4 ? late_waves_bf<4>() : b == 5 ? late_waves_bf<5>() : b == 6 ? late_waves_bf<6>() : 0;
 }
+// the same of the six-wave instance (kOrdSix), and the name of its order in the variant string
+int bitslice3_six_waves(int mode, int depth_bits) { return (mode == MODE_BINARY_FULL && depth_bits <= 4) ? bs3_six_waves<4, MODE_BINARY_FULL>() : 0; }
+const char *bitslice3_six_name() { return QS_SIX_DMA ? "dma" : "late"; }
 
 hipError_t launch_count_bitslice3(hipStream_t s, const CountGeometry &g_in, const void *panel, int depth_bits, int mode,
                                   uint32_t n_groups, uint32_t m_trees, void *table, int count_bits, uint32_t *overflow_flag,
-                                  bool overwrite, uint32_t *wire, bool late) {
+                                  bool overwrite, uint32_t *wire, int order) {
     if (g_in.total_tiles == 0 || n_groups == 0) return hipSuccess;
-    if (late && !bitslice3_late_waves(mode, depth_bits)) return hipErrorInvalidValue;
+    if (order == kOrdLate && !bitslice3_late_waves(mode, depth_bits)) return hipErrorInvalidValue;
+    if (order == kOrdSix && !bitslice3_six_waves(mode, depth_bits)) return hipErrorInvalidValue;
+    if (order < kOrdPrefetch || order > kOrdSix) return hipErrorInvalidValue;
     const uint32_t npairs = (uint32_t)binom2(g_in.n);
     CountGeometry g = g_in;
     // (count_bitslice4_kernel carries at most 7 planes per element: deeper classes take the plain kernel over g.perm with all tiles)
@@ -1003,14 +1018,19 @@ hipError_t launch_count_bitslice3(hipStream_t s, const CountGeometry &g_in, cons
         if (g.total_tiles == 0) return hipSuccess;
     }
     dim3 grid((g.total_tiles + kWavesPerBlock - 1) / kWavesPerBlock), block(kCountThreads);
-#define QS_BS3X(BB, MM, CT, LATE)                                                                                   \
-    hipLaunchKernelGGL((count_bitslice3_kernel<BB, MM, CT, LATE>), grid, block, 0, s, (const uint4 *)panel, npairs, n_groups, \
+#define QS_BS3X(BB, MM, CT, ORD)                                                                                    \
+    hipLaunchKernelGGL((count_bitslice3_kernel<BB, MM, CT, ORD>), grid, block, 0, s, (const uint4 *)panel, npairs, n_groups, \
                        m_trees, g.d_lo, g.d_hi, g.rank_lo, g.n_dblk, g.total_tiles, g.dprefix, g.cprefix,           \
                        (CT *)table, overflow_flag, overwrite ? 1u : 0u, g.n >= 200 ? (((kSyncModes >> (MM)) & 1u) ? 3u : 1u) : 0u /* bit 0: XCD remap, bit 1: waves of a workgroup in step (QS_SYNC_MODES) */, wire, g.perm)
-#define QS_BS3(BB, MM, CT) QS_BS3X(BB, MM, CT, false)
+#define QS_BS3(BB, MM, CT) QS_BS3X(BB, MM, CT, kOrdPrefetch)
+    // the six-wave instance (binary_full, 4 depth bits): the same launch again
+    if (order == kOrdSix) {
+        if (count_bits == 32) QS_BS3X(4, MODE_BINARY_FULL, uint32_t, kOrdSix); else QS_BS3X(4, MODE_BINARY_FULL, uint16_t, kOrdSix);
+        return hipGetLastError();
+    }
     // the late-load instances (binary_full, the depth bits of bs3_late_waves): the same launch, the other step order
-    if (late) {
-#define QS_BS3L(BB, CT) bs3_if_late<BB>([&](auto b_tag) { QS_BS3X(decltype(b_tag)::value, MODE_BINARY_FULL, CT, true); })
+    if (order == kOrdLate) {
+#define QS_BS3L(BB, CT) bs3_if_late<BB>([&](auto b_tag) { QS_BS3X(decltype(b_tag)::value, MODE_BINARY_FULL, CT, kOrdLate); })
 #define QS_BS3L_B(CT)                                                                                               \
     do {                                                                                                            \
         if (depth_bits <= 4) QS_BS3L(4, CT);                                                                        \

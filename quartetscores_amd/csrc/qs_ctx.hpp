@@ -100,7 +100,9 @@ struct qs_ctx {
     uint32_t tune_fix_split_at = 0;          // QS_TUNE_FIX_SPLIT_AT (tests): d_mid of every split, 0 = planned
     uint32_t last_split = 0, last_splits = 0; // qs_last_count_split: d_mid of the last split slice of the last count, and how many there were
     uint32_t tune_step_order = 0;            // QS_TUNE_STEP_ORDER: 0 = automatic, 1 = prefetch, 2 = late loads (binary_full instances that have a late variant)
-    uint32_t last_late_waves = 0;            // waves per SIMD of the late-load instance the last count ran (variant segment /late<w>); 0 = none did
+    uint32_t tune_stage_six = 0;             // QS_TUNE_STAGE_SIX: 0 = automatic, 1 = the instances QS_TUNE_STEP_ORDER selects, 2 = the six-wave instance wherever it exists
+    uint32_t last_six_waves = 0;             // waves per SIMD of the six-wave instance the last count ran (variant segment /dma<w> or /late<w>); 0 = none did
+    uint32_t last_late_waves = 0;           // waves per SIMD of the late-load instance the last count ran (variant segment /late<w>); 0 = none did
     // qs_set_tuning
     uint64_t tune_slice_bytes = 0; // 0 = automatic
     uint32_t tune_gather_impl = 0; // QS_IMPL_*

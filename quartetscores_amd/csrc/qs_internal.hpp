@@ -115,9 +115,12 @@ hipError_t launch_build_bitpanel(hipStream_t s, const DeviceBatch &b, uint32_t n
 hipError_t launch_count_bitslice3(hipStream_t s, const CountGeometry &g, const void *panel, int depth_bits, int mode,
                                   uint32_t n_groups, uint32_t m_trees, void *table, int count_bits, uint32_t *overflow_flag,
                                   bool overwrite, uint32_t *wire, // wire != NULL (binary_full only): one word n0 | n1 << 16 per tuple instead of the table
-                                  bool late = false);             // the late-load instance of the class (bitslice3_late_waves != 0) instead of the prefetch one
+                                  int order = 0);                 // step order of the instance: 0 = prefetch, 1 = late loads (bitslice3_late_waves != 0), 2 = the six-wave instance (bitslice3_six_waves != 0)
 // waves per SIMD of the late-load instance of (mode, depth bits); 0 = the class has none
 int bitslice3_late_waves(int mode, int depth_bits);
+// ... and of the six-wave instance, whose order ("dma" or "late") names it in the variant string
+int bitslice3_six_waves(int mode, int depth_bits);
+const char *bitslice3_six_name();
 // the classes of a mixed batch that share their depth bits in ONE launch (qs_count_fused.hip); seg_* are indexed by CountMode, a mode
 // without trees in this launch has seg_groups = 0
 constexpr int kFusedMaxBits = 7;
