@@ -21,6 +21,7 @@
  *   qs_tree_pair_agreement        replaces nothing in the reference (it never compares the evaluation trees with each other)
  *   qs_taxon_support              replaces nothing in the reference (the nearest is printRawQICScores, :612-680: one text
  *                                 line per quartet, which a user would reduce per taxon on the host)
+ *   qs_taxon_pair_support         replaces nothing in the reference (it has no output per pair of taxa)
  *   qs_group_check /              replace nothing in the reference; the nearest is the metaquartet sum of processNodePair
  *   qs_group_support              (QuartetScoreComputer.hpp:379-472), which knows only the four subtrees beside a node pair of the tree
  *   qs_taxon_placement /          replace nothing in the reference (it never asks where the evaluation trees would put a taxon; the
@@ -417,6 +418,28 @@ int qs_tree_pair_agreement(qs_ctx *ctx, const qs_device_batch *rows, uint32_t r0
  * QS_TUNE_TABLE_TREES -- if known, else the largest count a cell holds) exceeds 63 bits; QS_ERR_UNSUPPORTED = more than 3413 taxa
  * (table-shard contexts only; a whole table ends at 2259). Asynchronous on the context's stream. */
 int qs_taxon_support(qs_ctx *ctx, const qs_ref_tree *ref, int64_t *dst_device);
+
+/* Quartet support of taxon pairs from the count table: which taxon pulls which, against the reference tree. For an ordered pair
+ * (x, j), x != j, of lookup ids, over the C(n_taxa-2,2) 4-sets {x,j,k,l} of the table: t = n(xj|kl), the count of the topology that
+ * puts x and j together, and s = the tuple sum. The reference's topology of the 4-set is decided as in qs_score / qs_taxon_support
+ * (unresolved under a multifurcation): class rt = the reference shows xj|kl, class ra = it shows one of the two other resolutions,
+ * neither = unresolved. Eight exact words per pair:
+ *   k = 0 n_rt  4-sets of class rt       k = 4 T_ra   sum of t over ra
+ *   k = 1 n_ra  4-sets of class ra       k = 5 S_ra   sum of s over ra
+ *   k = 2 T_rt  sum of t over rt         k = 6 T_all  sum of t over all 4-sets
+ *   k = 3 S_rt  sum of s over rt         k = 7 S_all  sum of s over all 4-sets
+ * The matrix is symmetric in (x, j), its diagonal is zero, and row x adds up to the words of qs_taxon_support for x.
+ * taxa = host array of n_list distinct lookup ids (lent for the call), or NULL = all taxa in id order (n_list must be n_taxa then).
+ * dst_device (caller-owned device memory, 8-byte aligned, [n_list][n_taxa][8] words) is OVERWRITTEN, one row per list entry in list
+ * order. Exact integers, independent of grid, order and repetition. One gather over the C(n_taxa-1,3) tuples that hold each listed
+ * taxon (the walks of qs_taxon_placement); changes neither the table nor trees-counted nor a pending score log; a scoring view is not
+ * looked at. The reference tree is checked and uploaded as by qs_score (cached per context).
+ * Errors: QS_ERR_STATE = no table; QS_ERR_ARG = NULL / misaligned dst, an id >= n_taxa or listed twice, n_list = 0 or > n_taxa, malformed
+ * reference, n_taxa differs from the context's, ids not in depth-first order; QS_ERR_UNSUPPORTED = a table-shard context (whole tables
+ * only), or more than 2560 taxa (the accumulators of a workgroup, n_taxa x 8 words, live in LDS; a whole table ends at 2259). There is
+ * no overflow code: no word can leave 63 bits, C(4094,2) x 2^32 < 2^56. Asynchronous on the context's stream. The reference has no
+ * output per pair of taxa: this replaces nothing there. */
+int qs_taxon_pair_support(qs_ctx *ctx, const qs_ref_tree *ref, const uint16_t *taxa, uint32_t n_list, int64_t *dst_device);
 
 /* Quartet support of user-defined taxon groups from the count table: how often do the evaluation trees show each resolution around a
  * branch the caller names -- whether or not any reference tree has it. Replaces nothing in the reference; the nearest is the metaquartet

@@ -42,7 +42,7 @@ EXPORTS = [
     "qs_score_plan", "qs_last_score_ms", "qs_prepare", "qs_table_pack32x2", "qs_unpack32x2", "qs_last_score_log", "qs_last_score_estimate", "qs_score_prepare",
     "qs_sum_words", "qs_issue_probe", "qs_last_count_fix_ms", "qs_batch_clamp_info", "qs_depth_clamp_plan", "qs_score_check", "qs_last_count_events", "qs_class_plan", "qs_shard_bounds",
     "qs_table_remap", "qs_tree_agreement", "qs_taxon_support", "qs_table_restrict", "qs_taxon_placement", "qs_placement_scores", "qs_clade_placement",
-    "qs_last_count_split", "qs_fix_overlap_plan", "qs_group_check", "qs_group_support", "qs_tree_pair_agreement",
+    "qs_last_count_split", "qs_fix_overlap_plan", "qs_group_check", "qs_group_support", "qs_tree_pair_agreement", "qs_taxon_pair_support",
 ]
 
 
@@ -120,6 +120,8 @@ def load():
     L.qs_tree_pair_agreement.argtypes = [vp, vp, u32, u32, vp, u32, u32, u32, vp]
     L.qs_taxon_support.restype = i32
     L.qs_taxon_support.argtypes = [vp, vp, vp]
+    L.qs_taxon_pair_support.restype = i32
+    L.qs_taxon_pair_support.argtypes = [vp, vp, vp, u32, vp]
     L.qs_taxon_placement.restype = i32
     L.qs_taxon_placement.argtypes = [vp, vp, vp, u32, vp]
     L.qs_placement_scores.restype = i32

@@ -21,6 +21,8 @@
 // --test-groups SPEC FILE writes how often the evaluation trees show each of the three resolutions around branches the user names as
 // taxon groups -- four groups S1 S2 | S3 S4 or a bipartition S1 | S2 --, whether or not the -r tree has them, from the same count
 // table (qs_group_check, qs_group_support).
+// --taxon-pairs FILE [--taxon-pairs-only NAMES] writes, per pair of taxa of the -r tree, how often the evaluation trees put the two
+// together against the other two taxa of a 4-set, beside what the -r tree shows for the same 4-sets (qs_taxon_pair_support).
 #include "QuartetScoreComputer.hpp"
 #include "multi_gpu.hpp"
 #include "table_shards.hpp"
@@ -79,6 +81,9 @@ struct Args {
     std::string place_taxa; // --place-taxa FILE: quartet placement of the taxa of -r from the count table (TSV)
     std::string place_only; // --place-only NAMES: a file of the taxon labels to place (default: all)
     std::vector<uint16_t> place_ids;   // the lookup ids to place, ascending (check_place_taxa)
+    std::string taxon_pairs;      // --taxon-pairs FILE: quartet support of the taxon pairs of -r from the count table (TSV)
+    std::string taxon_pairs_only; // --taxon-pairs-only NAMES: a file of the taxon labels whose pairs are written (default: all)
+    std::vector<uint16_t> pair_ids;    // the lookup ids whose rows are computed, ascending (check_taxon_pairs)
     std::string place_clades;      // --place-clades FILE: quartet placement of the clades of -r from the count table (TSV)
     std::string place_clades_only; // --place-clades-only SPEC: a file of the clades to place, one per line (default: every eligible inner clade)
     std::vector<uint32_t> place_nodes; // the nodes to place, in output order (check_place_clades)
@@ -195,7 +200,19 @@ void usage(std::ostream &os) {
           "                  discordant counts into q2 and q3 follows the order of the taxa in the -r tree and means nothing (only\n"
           "                  q2 + q3 does), and qpic is nan. The groups need not be clades of any tree; one more read of the table on the\n"
           "                  device per eight hypotheses; one GPU with the whole table (not with --gpus / --table-shards); works with\n"
-          "                  --load-table and beside every other output\n";
+          "                  --load-table and beside every other output\n"
+          "   --taxon-pairs F  write, per pair of taxa of the -r tree, how the evaluation trees pair the two to F (TSV, one line per pair\n"
+          "                  a < b of lookup ids, row by row, after a header: a b name_a name_b quartets ref_together ref_apart together\n"
+          "                  apart affinity kept joined). Over the quartets = C(n-2,2) 4-sets that hold both taxa: ref_together /\n"
+          "                  ref_apart = 4-sets in which the -r tree puts the two together / resolves them apart; together / apart = how\n"
+          "                  often the evaluation trees show them together / show anything else; affinity = together / (together + apart);\n"
+          "                  kept = the same ratio over the ref_together 4-sets, joined = over the ref_apart ones (nan where there is\n"
+          "                  none). A pair whose joined stands out attracts each other against the -r tree (introgression, paralogy,\n"
+          "                  long-branch attraction, a misplaced pair); the matrix is the quartet neighbourliness of the taxa. One gather\n"
+          "                  over the table per taxon; one GPU with the whole table (not with --gpus / --table-shards); works with\n"
+          "                  --load-table and beside every other output\n"
+          "   --taxon-pairs-only NAMES  with --taxon-pairs: write only the pairs with a taxon listed in NAMES (one label per line, as for\n"
+          "                  --place-only)\n";
 }
 
 // returns 0 ok, 1 error (message printed like the reference prints TCLAP::ArgException), 2 exit quietly
@@ -270,6 +287,8 @@ int parse(int argc, char **argv, Args &a) {
         else if (f == "--tree-distances") { if (!(v = need(i, "--tree-distances"))) return 1; a.tree_distances = v; }
         else if (f == "--per-taxon") { if (!(v = need(i, "--per-taxon"))) return 1; a.per_taxon = v; }
         else if (f == "--place-taxa") { if (!(v = need(i, "--place-taxa"))) return 1; a.place_taxa = v; }
+        else if (f == "--taxon-pairs") { if (!(v = need(i, "--taxon-pairs"))) return 1; a.taxon_pairs = v; }
+        else if (f == "--taxon-pairs-only") { if (!(v = need(i, "--taxon-pairs-only"))) return 1; a.taxon_pairs_only = v; }
         else if (f == "--place-only") { if (!(v = need(i, "--place-only"))) return 1; a.place_only = v; }
         else if (f == "--place-clades") { if (!(v = need(i, "--place-clades"))) return 1; a.place_clades = v; }
         else if (f == "--place-clades-only") { if (!(v = need(i, "--place-clades-only"))) return 1; a.place_clades_only = v; }
@@ -418,7 +437,7 @@ void check_per_tree(const Args &a) {
     if (a.per_tree.empty()) return;
     if (a.gpus > 0 || a.table_shards >= 0 || !a.dev.load_table.empty())
         throw std::runtime_error("--per-tree needs the evaluation trees counted on one GPU: omit --gpus / --table-shards / --load-table");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_taxon};
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_taxon, a.taxon_pairs};
     for (const AlsoRef &x : a.also) others.insert(x.out);
     for (const WithoutTaxa &x : a.without) others.insert(x.out);
     if (others.count(a.per_tree)) throw std::runtime_error("--per-tree: " + a.per_tree + " is also another output file");
@@ -430,7 +449,7 @@ void check_tree_distances(const Args &a) {
     if (a.tree_distances.empty()) return;
     if (a.gpus > 0 || a.table_shards >= 0 || !a.dev.load_table.empty())
         throw std::runtime_error("--tree-distances needs the evaluation trees counted on one GPU: omit --gpus / --table-shards / --load-table");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.place_clades, a.test_groups};
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.place_clades, a.test_groups, a.taxon_pairs};
     for (const AlsoRef &x : a.also) others.insert(x.out);
     for (const WithoutTaxa &x : a.without) others.insert(x.out);
     if (others.count(a.tree_distances)) throw std::runtime_error("--tree-distances: " + a.tree_distances + " is also another output file");
@@ -484,7 +503,7 @@ void check_per_taxon(const Args &a) {
     if (a.per_taxon.empty()) return;
     if (a.gpus > 0 || a.table_shards >= 0)
         throw std::runtime_error("--per-taxon needs the whole count table on one GPU: omit --gpus / --table-shards");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree};
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.taxon_pairs};
     for (const AlsoRef &x : a.also) others.insert(x.out);
     for (const WithoutTaxa &x : a.without) others.insert(x.out);
     if (others.count(a.per_taxon)) throw std::runtime_error("--per-taxon: " + a.per_taxon + " is also another output file");
@@ -552,7 +571,7 @@ void check_place_taxa(Args &a) {
     }
     if (a.gpus > 0 || a.table_shards >= 0)
         throw std::runtime_error("--place-taxa needs the whole count table on one GPU: omit --gpus / --table-shards");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon};
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.taxon_pairs};
     for (const AlsoRef &x : a.also) others.insert(x.out);
     for (const WithoutTaxa &x : a.without) others.insert(x.out);
     if (others.count(a.place_taxa)) throw std::runtime_error("--place-taxa: " + a.place_taxa + " is also another output file");
@@ -635,6 +654,73 @@ void write_place_taxa(qs_ctx *ctx, const RefFlat &ref, int device, const std::st
     if (!f) throw std::runtime_error("cannot write " + path);
 }
 
+// --taxon-pairs: refused before the device is touched where the whole table is not on one GPU, where FILE exists or is another output,
+// and where --taxon-pairs-only names a label the -r tree lacks; leaves the lookup ids whose rows are computed in a.pair_ids
+void check_taxon_pairs(Args &a) {
+    if (a.taxon_pairs.empty()) {
+        if (!a.taxon_pairs_only.empty()) throw std::runtime_error("--taxon-pairs-only needs --taxon-pairs FILE");
+        return;
+    }
+    if (a.gpus > 0 || a.table_shards >= 0)
+        throw std::runtime_error("--taxon-pairs needs the whole count table on one GPU: omit --gpus / --table-shards");
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.place_clades, a.test_groups, a.tree_distances};
+    for (const AlsoRef &x : a.also) others.insert(x.out);
+    for (const WithoutTaxa &x : a.without) others.insert(x.out);
+    if (others.count(a.taxon_pairs)) throw std::runtime_error("--taxon-pairs: " + a.taxon_pairs + " is also another output file");
+    if (std::ifstream(a.taxon_pairs).good()) throw std::runtime_error("--taxon-pairs: the output file " + a.taxon_pairs + " already exists");
+    Tree primary;
+    {
+        const std::string text = slurp(a.ref);
+        NewickReader rr(text);
+        if (!rr.next(primary)) throw std::runtime_error("empty reference tree file");
+    }
+    const RefFlat rf = flatten_reference(primary);
+    std::set<uint16_t> ids;
+    if (a.taxon_pairs_only.empty()) {
+        for (size_t i = 0; i < rf.names.size(); ++i) ids.insert((uint16_t)i);
+    } else {
+        for (const std::string &name : read_taxon_names(a.taxon_pairs_only, rf, a.ref, "--taxon-pairs-only " + a.taxon_pairs_only + ": "))
+            ids.insert((uint16_t)rf.name_to_id.at(name));
+    }
+    a.pair_ids.assign(ids.begin(), ids.end());
+}
+
+// --taxon-pairs: one qs_taxon_pair_support over the counted (or loaded) table for the listed taxa, their rows of n x 8 words downloaded,
+// one TSV line per pair a < b with a listed taxon (tests/taxon_pair_model.py defines the columns; the matrix is symmetric: a pair's
+// words come from the row of whichever of the two is listed)
+void write_taxon_pairs(qs_ctx *ctx, const RefFlat &ref, int device, const std::string &path, const std::vector<uint16_t> &ids) {
+    const size_t n = ref.names.size(), L = ids.size();
+    const qs_ref_tree rt = ref_view(ref);
+    qs::DevBuf<int64_t> dev;
+    if (hipSetDevice(device) != hipSuccess || dev.reserve(L * n * 8 * 8, nullptr) != hipSuccess) throw std::runtime_error("--taxon-pairs: Insufficient memory!");
+    if (qs_taxon_pair_support(ctx, &rt, ids.data(), (uint32_t)L, dev.get()) != QS_OK || qs_sync(ctx) != QS_OK)
+        throw std::runtime_error(std::string("--taxon-pairs: ") + qs_last_error(ctx));
+    std::vector<int64_t> w(L * n * 8);
+    if (hipMemcpy(w.data(), dev.get(), w.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("--taxon-pairs: download failed");
+    std::vector<int64_t> row_of(n, -1);
+    for (size_t k = 0; k < L; ++k) row_of[ids[k]] = (int64_t)k;
+    std::ofstream f(path);
+    if (!f) throw std::runtime_error("cannot write " + path);
+    f << "a\tb\tname_a\tname_b\tquartets\tref_together\tref_apart\ttogether\tapart\taffinity\tkept\tjoined\n";
+    const uint64_t quartets = n < 4 ? 0 : (uint64_t)(n - 2) * (n - 3) / 2;
+    auto ratio = [](int64_t num, int64_t den, char (&buf)[64]) {   // (as --per-taxon's concordance)
+        if (den) std::snprintf(buf, sizeof buf, "%.6f", (double)num / (double)den);
+        else std::snprintf(buf, sizeof buf, "nan");
+    };
+    char affinity[64], kept[64], joined[64];
+    for (size_t a = 0; a < n; ++a)
+        for (size_t b = a + 1; b < n; ++b) {
+            if (row_of[a] < 0 && row_of[b] < 0) continue;
+            const int64_t *v = row_of[a] >= 0 ? &w[((size_t)row_of[a] * n + b) * 8] : &w[((size_t)row_of[b] * n + a) * 8];
+            ratio(v[6], v[7], affinity);
+            ratio(v[2], v[3], kept);
+            ratio(v[4], v[5], joined);
+            f << a << '\t' << b << '\t' << ref.names[a] << '\t' << ref.names[b] << '\t' << quartets << '\t' << v[0] << '\t' << v[1] << '\t' << v[6] << '\t'
+              << (v[7] - v[6]) << '\t' << affinity << '\t' << kept << '\t' << joined << '\n';
+        }
+    if (!f) throw std::runtime_error("cannot write " + path);
+}
+
 // --place-clades: refused before the device is touched where the whole table is not on one GPU, where FILE exists or is another output,
 // and where a line of --place-clades-only names a label the -r tree lacks, the whole tree, a clade with fewer than three taxa outside it
 // or a clade an earlier line names; leaves the nodes to place in a.place_nodes
@@ -645,7 +731,7 @@ void check_place_clades(Args &a) {
     }
     if (a.gpus > 0 || a.table_shards >= 0)
         throw std::runtime_error("--place-clades needs the whole count table on one GPU: omit --gpus / --table-shards");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa};
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.taxon_pairs};
     for (const AlsoRef &x : a.also) others.insert(x.out);
     for (const WithoutTaxa &x : a.without) others.insert(x.out);
     if (others.count(a.place_clades)) throw std::runtime_error("--place-clades: " + a.place_clades + " is also another output file");
@@ -816,7 +902,7 @@ void check_test_groups(Args &a) {
     if (a.test_groups.empty()) return;
     if (a.gpus > 0 || a.table_shards >= 0)
         throw std::runtime_error("--test-groups needs the whole count table on one GPU: omit --gpus / --table-shards");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.place_clades};
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.place_clades, a.taxon_pairs};
     for (const AlsoRef &x : a.also) others.insert(x.out);
     for (const WithoutTaxa &x : a.without) others.insert(x.out);
     if (others.count(a.test_groups)) throw std::runtime_error("--test-groups: " + a.test_groups + " is also another output file");
@@ -1025,6 +1111,7 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
     if (!a.place_taxa.empty()) write_place_taxa(qsc.context(), qsc.reference(), a.dev.device, a.place_taxa, a.place_ids);
     if (!a.place_clades.empty()) write_place_clades(qsc.context(), qsc.reference(), a.dev.device, a.place_clades, a.place_nodes);
     if (!a.test_groups.empty()) write_test_groups(qsc.context(), a.dev.device, a);
+    if (!a.taxon_pairs.empty()) write_taxon_pairs(qsc.context(), qsc.reference(), a.dev.device, a.taxon_pairs, a.pair_ids);
     if (!a.also.empty() || !a.without.empty()) {   // the primary tree's output first, exactly as without --also-ref / --without-taxa
         write_annotated(referenceTree, a.out, lqic, qpic, eqpic);
         score_also_refs(a, qsc.context(), qsc.reference(), also_table);
@@ -1057,6 +1144,7 @@ int main(int argc, char *argv[]) {
         check_place_taxa(a);
         check_place_clades(a);
         check_test_groups(a);
+        check_taxon_pairs(a);
     } catch (const std::exception &e) {
         std::cerr << "ERROR: " << e.what() << std::endl;
         return 1;

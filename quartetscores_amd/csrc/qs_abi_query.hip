@@ -1,6 +1,6 @@
-// qs_abi_query.hip -- what reads a finished table and is not the score: per-taxon support, taxon and clade placement, per-tree
+// qs_abi_query.hip -- what reads a finished table and is not the score: per-taxon and per-pair support, taxon and clade placement, per-tree
 // agreement (against a reference tree), the agreement of the evaluation trees with each other and the support of taxon groups (against
-// none). Host code only; the kernels are in qs_taxon.hip, qs_place.hip, qs_place_clade.hip, qs_agree.hip, qs_agree_pairs.hip and
+// none). Host code only; the kernels are in qs_taxon.hip, qs_taxon_pairs.hip, qs_place.hip, qs_place_clade.hip, qs_agree.hip, qs_agree_pairs.hip and
 // qs_groups.hip.
 #include "qs_ctx.hpp"
 #include "qs_plan.hpp"
@@ -133,6 +133,40 @@ static int ensure_place_ref(qs_ctx *c, const RefHost &R) {
     return QS_OK;
 }
 
+// qs_taxon_placement, qs_taxon_pair_support: the caller's list (NULL = all taxa in id order) checked and copied
+static int check_taxon_list(qs_ctx *c, const char *who, const uint16_t *taxa, uint32_t n_list, std::vector<uint16_t> &list) {
+    const std::string w(who);
+    if (taxa ? n_list == 0 || n_list > c->n : n_list != c->n) return fail(c, QS_ERR_ARG, w + (taxa ? ": the list needs 1 .. n_taxa entries" : ": n_list must be n_taxa when taxa is NULL"));
+    list.resize(n_list);
+    std::vector<uint8_t> seen(c->n, 0);
+    for (uint32_t i = 0; i < n_list; ++i) {
+        const uint32_t x = taxa ? taxa[i] : i;
+        if (x >= c->n) return fail(c, QS_ERR_ARG, w + ": taxon id out of range");
+        if (seen[x]) return fail(c, QS_ERR_ARG, w + ": taxon id " + std::to_string(x) + " is listed twice");
+        seen[x] = 1; list[i] = (uint16_t)x;
+    }
+    return QS_OK;
+}
+
+// ... and the walks of an n-taxon table and that list on the device
+static int ensure_place_walks(qs_ctx *c, const std::vector<uint16_t> &list) {
+    if (!c->place_tasks_dev) {
+        // a walk = (middle id q, 64 consecutive largest ids): q steps; the long ones first
+        c->place_tasks.clear();
+        for (uint32_t q = c->n - 2; q >= 1; --q)
+            for (uint32_t g = 0; q + 1 + g * kWave < c->n; ++g) c->place_tasks.push_back(q | g << 16);
+        QS_HIP(c, c->place_tasks_dev.reserve(c->place_tasks.size() * 4, nullptr));
+        QS_HIP(c, hipMemcpyAsync(c->place_tasks_dev.get(), c->place_tasks.data(), c->place_tasks.size() * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    if (list != c->place_taxa || !c->place_taxa_dev) {
+        QS_HIP(c, hipStreamSynchronize(c->stream));   // (an earlier call's kernel and upload may still read the old list)
+        c->place_taxa = list;
+        QS_HIP(c, c->place_taxa_dev.reserve((size_t)c->n * 2, nullptr));
+        QS_HIP(c, hipMemcpyAsync(c->place_taxa_dev.get(), c->place_taxa.data(), list.size() * 2, hipMemcpyHostToDevice, c->stream));
+    }
+    return QS_OK;
+}
+
 // Link sums of the quartet placement of the listed taxa (qs_place.hip). The reference never asks where the evaluation trees would
 // put a taxon: this replaces nothing there.
 extern "C" int qs_taxon_placement(qs_ctx *c, const qs_ref_tree *ref, const uint16_t *taxa, uint32_t n_list, int64_t *dst_device) {
@@ -146,17 +180,8 @@ extern "C" int qs_taxon_placement(qs_ctx *c, const qs_ref_tree *ref, const uint1
     if (per_taxon && max_count > (uint64_t)INT64_MAX / per_taxon)
         return fail(c, QS_ERR_OVERFLOW, "qs_taxon_placement: C(n-1,3) x the largest possible count exceeds 63 bits");
     if (c->d_lo != 0 || c->d_hi != c->n) return fail(c, QS_ERR_UNSUPPORTED, "qs_taxon_placement: a table-shard context (the walks of a taxon cross every shard: use a whole-table one)");
-    if (taxa ? n_list == 0 || n_list > c->n : n_list != c->n) return fail(c, QS_ERR_ARG, taxa ? "qs_taxon_placement: the list needs 1 .. n_taxa entries" : "qs_taxon_placement: n_list must be n_taxa when taxa is NULL");
-    std::vector<uint16_t> list(n_list);
-    {
-        std::vector<uint8_t> seen(c->n, 0);
-        for (uint32_t i = 0; i < n_list; ++i) {
-            const uint32_t x = taxa ? taxa[i] : i;
-            if (x >= c->n) return fail(c, QS_ERR_ARG, "qs_taxon_placement: taxon id out of range");
-            if (seen[x]) return fail(c, QS_ERR_ARG, "qs_taxon_placement: taxon id " + std::to_string(x) + " is listed twice");
-            seen[x] = 1; list[i] = (uint16_t)x;
-        }
-    }
+    std::vector<uint16_t> list;
+    if (int rc = check_taxon_list(c, "qs_taxon_placement", taxa, n_list, list)) return rc;
     QS_HIP(c, hipSetDevice(c->device));
     const RefHost *Rp = nullptr;
     if (int rc = get_ref(c, ref, true, &Rp)) return rc;
@@ -164,20 +189,7 @@ extern "C" int qs_taxon_placement(qs_ctx *c, const qs_ref_tree *ref, const uint1
         return fail(c, QS_ERR_UNSUPPORTED, "qs_taxon_placement: more than 10240 nodes (the link sums of a workgroup live in LDS)");
     if (int rc = ensure_place_ref(c, *Rp)) return rc;
     if (int rc = ensure_n_cu(c)) return rc;
-    if (!c->place_tasks_dev) {
-        // a walk = (middle id q, 64 consecutive largest ids): q steps; the long ones first
-        c->place_tasks.clear();
-        for (uint32_t q = c->n - 2; q >= 1; --q)
-            for (uint32_t g = 0; q + 1 + g * kWave < c->n; ++g) c->place_tasks.push_back(q | g << 16);
-        QS_HIP(c, c->place_tasks_dev.reserve(c->place_tasks.size() * 4, nullptr));
-        QS_HIP(c, hipMemcpyAsync(c->place_tasks_dev.get(), c->place_tasks.data(), c->place_tasks.size() * 4, hipMemcpyHostToDevice, c->stream));
-    }
-    if (list != c->place_taxa || !c->place_taxa_dev) {
-        QS_HIP(c, hipStreamSynchronize(c->stream));   // (an earlier call's kernel and upload may still read the old list)
-        c->place_taxa = list;
-        QS_HIP(c, c->place_taxa_dev.reserve((size_t)c->n * 2, nullptr));
-        QS_HIP(c, hipMemcpyAsync(c->place_taxa_dev.get(), c->place_taxa.data(), (size_t)n_list * 2, hipMemcpyHostToDevice, c->stream));
-    }
+    if (int rc = ensure_place_walks(c, list)) return rc;
     PlaceDevice pd;
     pd.ref_lca = c->ref_lca_dev.get(); pd.inner_node = c->place_node_dev.get(); pd.tasks = c->place_tasks_dev.get();
     pd.child = c->place_child_dev.get(); pd.next = c->place_next_dev.get(); pd.taxa = c->place_taxa_dev.get();
@@ -188,6 +200,35 @@ extern "C" int qs_taxon_placement(qs_ctx *c, const qs_ref_tree *ref, const uint1
     // (qs_create's cap today; the LDS limit alone would allow more)
     const bool wide = max_count >= (1ull << 32) / 4096 || c->n > 4096;
     QS_HIP(c, launch_taxon_placement(c->stream, pd, n_list, wide, c->n_cu, reinterpret_cast<unsigned long long *>(dst_device)));
+    return QS_OK;   // asynchronous on the context's stream
+}
+
+// The eight words of every pair (listed taxon, other taxon) over the 4-sets that hold both (qs_taxon_pairs.hip). The reference has no
+// output per pair of taxa: this replaces nothing there.
+extern "C" int qs_taxon_pair_support(qs_ctx *c, const qs_ref_tree *ref, const uint16_t *taxa, uint32_t n_list, int64_t *dst_device) {
+    if (!c) return QS_ERR_ARG;
+    if (!dst_device) return fail(c, QS_ERR_ARG, "qs_taxon_pair_support: NULL argument");
+    if (reinterpret_cast<uintptr_t>(dst_device) % 8) return fail(c, QS_ERR_ARG, "qs_taxon_pair_support: dst_device is not 8-byte aligned");
+    if (!c->table) return fail(c, QS_ERR_STATE, "qs_taxon_pair_support: no table");
+    if (taxon_pairs_lds_bytes(c->n) > 160u * 1024u) return fail(c, QS_ERR_UNSUPPORTED, "qs_taxon_pair_support: more than 2560 taxa (the accumulators of a workgroup live in LDS)");
+    if (c->d_lo != 0 || c->d_hi != c->n) return fail(c, QS_ERR_UNSUPPORTED, "qs_taxon_pair_support: a table-shard context (the walks of a taxon cross every shard: use a whole-table one)");
+    std::vector<uint16_t> list;
+    if (int rc = check_taxon_list(c, "qs_taxon_pair_support", taxa, n_list, list)) return rc;
+    // (a word is at most C(n-2,2) x 3 x (largest count) < 2^23 x 2^34: no overflow to refuse)
+    const uint64_t max_count = table_max_count(c);
+    QS_HIP(c, hipSetDevice(c->device));
+    const RefHost *Rp = nullptr;
+    if (int rc = get_ref(c, ref, true, &Rp)) return rc;
+    if (int rc = ensure_n_cu(c)) return rc;
+    if (int rc = ensure_place_walks(c, list)) return rc;
+    PairDevice pd;
+    pd.ref_lca = c->ref_lca_dev.get(); pd.tasks = c->place_tasks_dev.get(); pd.taxa = c->place_taxa_dev.get();
+    pd.n = c->n; pd.n_tasks = (uint32_t)c->place_tasks.size();
+    pd.table = c->table; pd.count_bits = (int)c->count_bits;   // the context's own table, not a scoring view
+    QS_HIP(c, hipMemsetAsync(dst_device, 0, (size_t)n_list * c->n * kPairFields * 8, c->stream));
+    // 32-bit partial sums: a walk has q < 4096 steps of up to three counts each
+    const bool wide = max_count >= (1ull << 32) / (4096 * 3);
+    QS_HIP(c, launch_taxon_pairs(c->stream, pd, n_list, wide, c->n_cu, reinterpret_cast<unsigned long long *>(dst_device)));
     return QS_OK;   // asynchronous on the context's stream
 }
 

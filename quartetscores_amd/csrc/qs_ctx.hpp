@@ -171,7 +171,7 @@ struct qs_ctx {
     // qs_tree_pair_agreement: the position maps and node orders of the last call's row trees (tree_pairs_work_words; grown, never shrunk)
     DevBuf<uint16_t> pair_pos;
     // qs_taxon_placement: the cached reference tree's link lookups (dropped with ref_lca_dev), the walks of an n-taxon table and
-    // the list of the last call; the host copies stay until the uploads on `stream` have read them
+    // the list of the last call (both shared with qs_taxon_pair_support); the host copies stay until the uploads on `stream` have read them
     std::vector<uint16_t> place_child, place_next, place_taxa;
     std::vector<uint32_t> place_tasks;
     DevBuf<uint16_t> place_child_dev, place_next_dev, place_taxa_dev;

@@ -193,6 +193,19 @@ struct PlaceDevice {
 constexpr int kPlaceWaves = 4;
 size_t place_lds_bytes(uint32_t n_nodes);
 hipError_t launch_taxon_placement(hipStream_t s, const PlaceDevice &pd, uint32_t n_list, bool wide, int n_cu, unsigned long long *dst);
+// qs_taxon_pairs.hip: the eight words of every pair (x, j), x = pd.taxa[0 .. n_list), over the 4-sets that hold both
+// (qs_taxon_pair_support); whole tables only. ref_lca, tasks, taxa as in PlaceDevice (the same walk list); dst = n_list rows of n x 8
+// words, zeroed beforehand; wide: counts may reach 2^32 / (4096 x 3)
+struct PairDevice {
+    const uint32_t *ref_lca, *tasks;
+    const uint16_t *taxa;
+    uint32_t n, n_tasks;
+    const void *table;
+    int count_bits;
+};
+constexpr int kPairFields = 8;    // n_rt, n_ra, T_rt, S_rt, T_ra, S_ra, T_all, S_all
+size_t taxon_pairs_lds_bytes(uint32_t n);
+hipError_t launch_taxon_pairs(hipStream_t s, const PairDevice &pd, uint32_t n_list, bool wide, int n_cu, unsigned long long *dst);
 // qs_place_clade.hip: link sums of the quartet placement of listed clades (qs_clade_placement); whole tables only. ref_lca, inner_node,
 // child, next as in PlaceDevice. tasks = d | group of 64 largest ids << 16 by d ascending, in the numbering of the ids OUTSIDE a clade:
 // the walk of the middle id n_outside - 1 - d (d = 1 ..: the longest walks first), so that the first clades[4 i + 3] entries are the walks

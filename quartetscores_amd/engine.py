@@ -102,6 +102,35 @@ def taxon_columns(counts) -> dict:
     return out
 
 
+TAXON_PAIR_FIELDS = ("n_rt", "n_ra", "T_rt", "S_rt", "T_ra", "S_ra", "T_all", "S_all")
+TAXON_PAIR_COLUMNS = ("a", "b", "name_a", "name_b", "quartets", "ref_together", "ref_apart", "together", "apart", "affinity", "kept", "joined")
+
+
+def taxon_pair_columns(counts, names, taxa=None) -> dict:
+    """The columns of QuartetScores --taxon-pairs from Context.taxon_pair_support: counts (len(taxa), n, 8) int64 in
+    TAXON_PAIR_FIELDS order, names = the n taxa in lookup-id order, taxa = the lookup ids of the rows (None = all, in id order) ->
+    dict in TAXON_PAIR_COLUMNS order with one entry per unordered pair a < b that has a listed taxon, row-major: int64 arrays a, b,
+    quartets = C(n-2,2), ref_together = n_rt, ref_apart = n_ra, together = T_all, apart = S_all - T_all, lists name_a, name_b and the
+    float64 arrays affinity = T_all / S_all, kept = T_rt / S_rt (where the reference pairs them, how often the trees do), joined =
+    T_ra / S_ra (where it separates them, how often the trees pair them anyway); nan where a denominator is 0."""
+    n = len(names)
+    rows = np.arange(n, dtype=np.int64) if taxa is None else np.asarray(taxa, dtype=np.int64).reshape(-1)
+    m = np.asarray(counts, dtype=np.int64).reshape(len(rows), n, 8)
+    row_of = np.full(n, -1, dtype=np.int64)
+    row_of[rows] = np.arange(len(rows))
+    a, b = np.triu_indices(n, 1)                                  # row-major pairs a < b
+    keep = (row_of[a] >= 0) | (row_of[b] >= 0)
+    a, b = a[keep].astype(np.int64), b[keep].astype(np.int64)
+    w = np.where((row_of[a] >= 0)[:, None], m[np.maximum(row_of[a], 0), b], m[np.maximum(row_of[b], 0), a])   # (the matrix is symmetric)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ratio = lambda num, den: np.where(den > 0, num / np.maximum(den, 1), np.nan)
+        out = {"a": a, "b": b, "name_a": [names[i] for i in a], "name_b": [names[i] for i in b],
+               "quartets": np.full(len(a), (n - 2) * (n - 3) // 2 if n >= 4 else 0, dtype=np.int64),
+               "ref_together": w[:, 0], "ref_apart": w[:, 1], "together": w[:, 6], "apart": w[:, 7] - w[:, 6],
+               "affinity": ratio(w[:, 6], w[:, 7]), "kept": ratio(w[:, 2], w[:, 3]), "joined": ratio(w[:, 4], w[:, 5])}
+    return out
+
+
 GROUP_FIELDS = ("quartets", "q1", "q2", "q3", "outvoted", "uninformed")
 GROUP_KINDS = ("quad", "split")
 
@@ -523,6 +552,28 @@ class Context:
         self.sync()
         del keep
         return buf[: n_list * width].cpu().numpy().reshape(n_list, width)
+
+    def taxon_pair_support(self, ref: flatten.RefTree, taxa=None) -> np.ndarray:
+        """qs_taxon_pair_support: per listed taxon x (lookup ids; None = all, in id order) and every taxon j the eight words of
+        TAXON_PAIR_FIELDS over the 4-sets of this context's whole table that hold both, split by what `ref` shows for the 4-set
+        -> int64 (n_list, n, 8); taxon_pair_columns turns them into the CLI's columns. Allocates the device buffer, waits for the
+        result and downloads it."""
+        import torch
+        ids = None
+        if taxa is not None:
+            wide = np.asarray(taxa, dtype=np.int64).reshape(-1)
+            if ((wide < 0) | (wide >= self.n)).any():     # (before the cast to the ABI's 16-bit ids, which would wrap)
+                raise QSError(_lib.QS_ERR_ARG, "taxon_pair_support: taxon id out of range")
+            ids = np.ascontiguousarray(wide, dtype=np.uint16)
+        n_list = self.n if ids is None else len(ids)
+        width = 8 * self.n
+        buf = torch.empty(max(1, n_list * width), dtype=torch.int64, device=f"cuda:{self.device}")
+        s, keep = self._ref_struct(ref)
+        self._chk(self.L.qs_taxon_pair_support(self.h, C.byref(s), None if ids is None else ids.ctypes.data_as(C.c_void_p), n_list,
+                                               C.c_void_p(buf.data_ptr())))
+        self.sync()
+        del keep
+        return buf[: n_list * width].cpu().numpy().reshape(n_list, self.n, 8)
 
     def clade_placement(self, ref: flatten.RefTree, nodes=None) -> np.ndarray:
         """qs_clade_placement: per listed non-root node of `ref` (None = eligible_clades(ref)) the 2 * n_nodes link sums W_C of the
