@@ -22,6 +22,7 @@
  *   qs_taxon_support              replaces nothing in the reference (the nearest is printRawQICScores, :612-680: one text
  *                                 line per quartet, which a user would reduce per taxon on the host)
  *   qs_taxon_pair_support         replaces nothing in the reference (it has no output per pair of taxa)
+ *   qs_branch_taxon_support       replaces nothing in the reference (it never asks what a branch's QP-IC would be without one taxon)
  *   qs_group_check /              replace nothing in the reference; the nearest is the metaquartet sum of processNodePair
  *   qs_group_support              (QuartetScoreComputer.hpp:379-472), which knows only the four subtrees beside a node pair of the tree
  *   qs_taxon_placement /          replace nothing in the reference (it never asks where the evaluation trees would put a taxon; the
@@ -440,6 +441,32 @@ int qs_taxon_support(qs_ctx *ctx, const qs_ref_tree *ref, int64_t *dst_device);
  * no overflow code: no word can leave 63 bits, C(4094,2) x 2^32 < 2^56. Asynchronous on the context's stream. The reference has no
  * output per pair of taxa: this replaces nothing there. */
 int qs_taxon_pair_support(qs_ctx *ctx, const qs_ref_tree *ref, const uint16_t *taxa, uint32_t n_list, int64_t *dst_device);
+
+/* Per-branch quartet sums without each single taxon, from the count table: which taxon drags a branch down. QP-IC of an internode e of
+ * the reference tree is log_score(F1, F2, F3), the sums of (q1, q2, q3) over the 4-sets "around" e: those the reference resolves with
+ * its two junction nodes at the two ends of e, i.e. one taxon behind each of two different links at either end (what processNodePair
+ * sums for an adjacent node pair, QuartetScoreComputer.hpp:379-472). Dropping taxon x removes exactly the 4-sets that hold x, so QP-IC of
+ * e without x is log_score(F(e) - F(e,x)). Four exact words per (x, node v), for the internode between v and its parent:
+ *   k = 0 quartets  4-sets around e that hold x        k = 1..3 F1, F2, F3  sums of (q1, q2, q3) over them
+ * with topology, junctions and the order of (q1, q2, q3) decided as by qs_score without flags. rows_device (caller-owned device memory,
+ * 8-byte aligned, [n_list][n_nodes][4] words) is OVERWRITTEN, one row per list entry in list order; the entries of leaves, of the root
+ * and of edges with a leaf at either end are 0. Under a degree-2 root its two inner children are the ends of ONE internode of the
+ * unrooted tree: its words -- the plain sums over the 4-sets around it, not the sums qs_score keeps for the pairs (root, v) -- stand at
+ * both children, identically. totals_device ([n_nodes][4] words, or NULL) receives the same four words over ALL 4-sets around each
+ * internode: exact 64-bit sums whatever QS_SCORE_QP_WRAP32 / QS_SCORE_QP_EXACT64 says, `quartets` the product over the two ends of the number of pairs of
+ * different links. All rows together add up to four times the totals, the rows of the taxa at one end of an internode to twice them.
+ * taxa = host array of n_list distinct lookup ids (lent for the call), or NULL = all taxa in id order (n_list must be n_taxa then).
+ * Exact integers, independent of grid, order and repetition. Cost: one gather over the C(n_taxa-1,3) tuples that hold each listed taxon
+ * (the walks of qs_taxon_placement) and, for the totals, one streaming read of the table. Changes neither the table nor trees-counted
+ * nor a pending score log; a scoring view is not looked at. The reference tree is checked and uploaded as by qs_score (cached per
+ * context). LQ-IC and EQP-IC are minima over 4-sets and do not decompose this way: not covered.
+ * Errors: QS_ERR_STATE = no table; QS_ERR_ARG = NULL / misaligned rows_device, misaligned totals_device, an id >= n_taxa or listed
+ * twice, n_list = 0 or > n_taxa, malformed reference, n_taxa differs from the context's, ids not in depth-first order; QS_ERR_OVERFLOW =
+ * C(n_taxa-1,3) x (largest possible count) exceeds 63 bits (the bound of qs_taxon_support); QS_ERR_UNSUPPORTED = a table-shard context
+ * (whole tables only), or more than 4551 inner nodes (the sums of a workgroup, 36 bytes per inner node, live in LDS; a whole table ends
+ * at 2259 taxa). Asynchronous on the context's stream. The reference has no such output: this replaces nothing there. */
+int qs_branch_taxon_support(qs_ctx *ctx, const qs_ref_tree *ref, const uint16_t *taxa, uint32_t n_list, int64_t *rows_device,
+                            int64_t *totals_device);
 
 /* Quartet support of user-defined taxon groups from the count table: how often do the evaluation trees show each resolution around a
  * branch the caller names -- whether or not any reference tree has it. Replaces nothing in the reference; the nearest is the metaquartet

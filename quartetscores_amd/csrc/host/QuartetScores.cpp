@@ -23,6 +23,8 @@
 // table (qs_group_check, qs_group_support).
 // --taxon-pairs FILE [--taxon-pairs-only NAMES] writes, per pair of taxa of the -r tree, how often the evaluation trees put the two
 // together against the other two taxa of a 4-set, beside what the -r tree shows for the same 4-sets (qs_taxon_pair_support).
+// --drop-one FILE [--drop-one-only NAMES] writes, per taxon and internode of the -r tree, the internode's QP-IC without that taxon, from
+// the same count table (qs_branch_taxon_support).
 #include "QuartetScoreComputer.hpp"
 #include "multi_gpu.hpp"
 #include "table_shards.hpp"
@@ -84,6 +86,9 @@ struct Args {
     std::string taxon_pairs;      // --taxon-pairs FILE: quartet support of the taxon pairs of -r from the count table (TSV)
     std::string taxon_pairs_only; // --taxon-pairs-only NAMES: a file of the taxon labels whose pairs are written (default: all)
     std::vector<uint16_t> pair_ids;    // the lookup ids whose rows are computed, ascending (check_taxon_pairs)
+    std::string drop_one;         // --drop-one FILE: QP-IC of every internode of -r without each single taxon, from the count table (TSV)
+    std::string drop_one_only;    // --drop-one-only NAMES: a file of the taxon labels to drop (default: all)
+    std::vector<uint16_t> drop_ids;    // the lookup ids whose rows are computed, ascending (check_drop_one)
     std::string place_clades;      // --place-clades FILE: quartet placement of the clades of -r from the count table (TSV)
     std::string place_clades_only; // --place-clades-only SPEC: a file of the clades to place, one per line (default: every eligible inner clade)
     std::vector<uint32_t> place_nodes; // the nodes to place, in output order (check_place_clades)
@@ -212,7 +217,19 @@ void usage(std::ostream &os) {
           "                  over the table per taxon; one GPU with the whole table (not with --gpus / --table-shards); works with\n"
           "                  --load-table and beside every other output\n"
           "   --taxon-pairs-only NAMES  with --taxon-pairs: write only the pairs with a taxon listed in NAMES (one label per line, as for\n"
-          "                  --place-only)\n";
+          "                  --place-only)\n"
+          "   --drop-one F   write, per taxon and internal branch of the -r tree, what the branch's QP-IC would be without that taxon to F\n"
+          "                  (TSV, after a header one line per taxon in id order and branch in node order: taxon name node lo hi group\n"
+          "                  quartets q1 q2 q3 qpic qpic_without delta). [lo, hi) = the lookup ids below the branch, group = the number of\n"
+          "                  taxa in the taxon's subtree beside the branch; quartets q1 q2 q3 = the 4-sets around the branch that hold the\n"
+          "                  taxon and their share of the three sums behind QP-IC; qpic = the branch's QP-IC from exact sums, qpic_without\n"
+          "                  = the same without the 4-sets that hold the taxon (nan where none is left: the taxon is alone beside a\n"
+          "                  branching of degree 3, the branch dissolves with it), delta = qpic_without - qpic: a taxon with a large\n"
+          "                  positive delta drags the branch down. A rooted -r tree's branch through the root is written once. LQ-IC and\n"
+          "                  EQP-IC are minima and have no such decomposition. One gather over the table per taxon and one read of it;\n"
+          "                  one GPU with the whole table (not with --gpus / --table-shards); works with --load-table and beside every\n"
+          "                  other output\n"
+          "   --drop-one-only NAMES  with --drop-one: write only the taxa listed in NAMES (one label per line, as for --place-only)\n";
 }
 
 // returns 0 ok, 1 error (message printed like the reference prints TCLAP::ArgException), 2 exit quietly
@@ -289,6 +306,8 @@ int parse(int argc, char **argv, Args &a) {
         else if (f == "--place-taxa") { if (!(v = need(i, "--place-taxa"))) return 1; a.place_taxa = v; }
         else if (f == "--taxon-pairs") { if (!(v = need(i, "--taxon-pairs"))) return 1; a.taxon_pairs = v; }
         else if (f == "--taxon-pairs-only") { if (!(v = need(i, "--taxon-pairs-only"))) return 1; a.taxon_pairs_only = v; }
+        else if (f == "--drop-one") { if (!(v = need(i, "--drop-one"))) return 1; a.drop_one = v; }
+        else if (f == "--drop-one-only") { if (!(v = need(i, "--drop-one-only"))) return 1; a.drop_one_only = v; }
         else if (f == "--place-only") { if (!(v = need(i, "--place-only"))) return 1; a.place_only = v; }
         else if (f == "--place-clades") { if (!(v = need(i, "--place-clades"))) return 1; a.place_clades = v; }
         else if (f == "--place-clades-only") { if (!(v = need(i, "--place-clades-only"))) return 1; a.place_clades_only = v; }
@@ -437,7 +456,7 @@ void check_per_tree(const Args &a) {
     if (a.per_tree.empty()) return;
     if (a.gpus > 0 || a.table_shards >= 0 || !a.dev.load_table.empty())
         throw std::runtime_error("--per-tree needs the evaluation trees counted on one GPU: omit --gpus / --table-shards / --load-table");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_taxon, a.taxon_pairs};
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_taxon, a.taxon_pairs, a.drop_one};
     for (const AlsoRef &x : a.also) others.insert(x.out);
     for (const WithoutTaxa &x : a.without) others.insert(x.out);
     if (others.count(a.per_tree)) throw std::runtime_error("--per-tree: " + a.per_tree + " is also another output file");
@@ -449,7 +468,7 @@ void check_tree_distances(const Args &a) {
     if (a.tree_distances.empty()) return;
     if (a.gpus > 0 || a.table_shards >= 0 || !a.dev.load_table.empty())
         throw std::runtime_error("--tree-distances needs the evaluation trees counted on one GPU: omit --gpus / --table-shards / --load-table");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.place_clades, a.test_groups, a.taxon_pairs};
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.place_clades, a.test_groups, a.taxon_pairs, a.drop_one};
     for (const AlsoRef &x : a.also) others.insert(x.out);
     for (const WithoutTaxa &x : a.without) others.insert(x.out);
     if (others.count(a.tree_distances)) throw std::runtime_error("--tree-distances: " + a.tree_distances + " is also another output file");
@@ -503,7 +522,7 @@ void check_per_taxon(const Args &a) {
     if (a.per_taxon.empty()) return;
     if (a.gpus > 0 || a.table_shards >= 0)
         throw std::runtime_error("--per-taxon needs the whole count table on one GPU: omit --gpus / --table-shards");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.taxon_pairs};
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.taxon_pairs, a.drop_one};
     for (const AlsoRef &x : a.also) others.insert(x.out);
     for (const WithoutTaxa &x : a.without) others.insert(x.out);
     if (others.count(a.per_taxon)) throw std::runtime_error("--per-taxon: " + a.per_taxon + " is also another output file");
@@ -571,7 +590,7 @@ void check_place_taxa(Args &a) {
     }
     if (a.gpus > 0 || a.table_shards >= 0)
         throw std::runtime_error("--place-taxa needs the whole count table on one GPU: omit --gpus / --table-shards");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.taxon_pairs};
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.taxon_pairs, a.drop_one};
     for (const AlsoRef &x : a.also) others.insert(x.out);
     for (const WithoutTaxa &x : a.without) others.insert(x.out);
     if (others.count(a.place_taxa)) throw std::runtime_error("--place-taxa: " + a.place_taxa + " is also another output file");
@@ -663,7 +682,7 @@ void check_taxon_pairs(Args &a) {
     }
     if (a.gpus > 0 || a.table_shards >= 0)
         throw std::runtime_error("--taxon-pairs needs the whole count table on one GPU: omit --gpus / --table-shards");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.place_clades, a.test_groups, a.tree_distances};
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.place_clades, a.test_groups, a.tree_distances, a.drop_one};
     for (const AlsoRef &x : a.also) others.insert(x.out);
     for (const WithoutTaxa &x : a.without) others.insert(x.out);
     if (others.count(a.taxon_pairs)) throw std::runtime_error("--taxon-pairs: " + a.taxon_pairs + " is also another output file");
@@ -721,6 +740,104 @@ void write_taxon_pairs(qs_ctx *ctx, const RefFlat &ref, int device, const std::s
     if (!f) throw std::runtime_error("cannot write " + path);
 }
 
+// --drop-one: refused before the device is touched where the whole table is not on one GPU, where FILE exists or is another output,
+// and where --drop-one-only names a label the -r tree lacks; leaves the lookup ids whose rows are computed in a.drop_ids
+void check_drop_one(Args &a) {
+    if (a.drop_one.empty()) {
+        if (!a.drop_one_only.empty()) throw std::runtime_error("--drop-one-only needs --drop-one FILE");
+        return;
+    }
+    if (a.gpus > 0 || a.table_shards >= 0)
+        throw std::runtime_error("--drop-one needs the whole count table on one GPU: omit --gpus / --table-shards");
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.place_clades, a.test_groups, a.tree_distances, a.taxon_pairs};
+    for (const AlsoRef &x : a.also) others.insert(x.out);
+    for (const WithoutTaxa &x : a.without) others.insert(x.out);
+    if (others.count(a.drop_one)) throw std::runtime_error("--drop-one: " + a.drop_one + " is also another output file");
+    if (std::ifstream(a.drop_one).good()) throw std::runtime_error("--drop-one: the output file " + a.drop_one + " already exists");
+    Tree primary;
+    {
+        const std::string text = slurp(a.ref);
+        NewickReader rr(text);
+        if (!rr.next(primary)) throw std::runtime_error("empty reference tree file");
+    }
+    const RefFlat rf = flatten_reference(primary);
+    std::set<uint16_t> ids;
+    if (a.drop_one_only.empty()) {
+        for (size_t i = 0; i < rf.names.size(); ++i) ids.insert((uint16_t)i);
+    } else {
+        for (const std::string &name : read_taxon_names(a.drop_one_only, rf, a.ref, "--drop-one-only " + a.drop_one_only + ": "))
+            ids.insert((uint16_t)rf.name_to_id.at(name));
+    }
+    a.drop_ids.assign(ids.begin(), ids.end());
+}
+
+// --drop-one: one qs_branch_taxon_support over the counted (or loaded) table for the listed taxa, their rows of n_nodes x 4 words and
+// the totals downloaded, one TSV line per taxon and internode (tests/branch_taxon_model.py defines the columns; the internode through a
+// degree-2 root once, at the child that holds lookup id 0)
+void write_drop_one(qs_ctx *ctx, const RefFlat &ref, int device, const std::string &path, const std::vector<uint16_t> &ids) {
+    const size_t n = ref.names.size(), N = ref.parent.size(), L = ids.size();
+    const qs_ref_tree rt = ref_view(ref);
+    qs::DevBuf<int64_t> dev;
+    if (hipSetDevice(device) != hipSuccess || dev.reserve((L + 1) * N * 4 * 8, nullptr) != hipSuccess) throw std::runtime_error("--drop-one: Insufficient memory!");
+    if (qs_branch_taxon_support(ctx, &rt, ids.data(), (uint32_t)L, dev.get(), dev.get() + L * N * 4) != QS_OK || qs_sync(ctx) != QS_OK)
+        throw std::runtime_error(std::string("--drop-one: ") + qs_last_error(ctx));
+    std::vector<int64_t> w((L + 1) * N * 4);
+    if (hipMemcpy(w.data(), dev.get(), w.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("--drop-one: download failed");
+    const int64_t *totals = w.data() + L * N * 4;
+    // the id interval below every node, its children in id order, the internodes (child node, other end)
+    std::vector<size_t> lo(N, n), hi(N, 0);
+    for (size_t i = 0; i < n; ++i)
+        for (int64_t v = ref.leaf_node[i]; v >= 0; v = ref.parent[(size_t)v]) { lo[(size_t)v] = std::min(lo[(size_t)v], i); hi[(size_t)v] = std::max(hi[(size_t)v], i + 1); }
+    std::vector<std::vector<size_t>> kids(N);
+    size_t root = 0;
+    for (size_t v = 0; v < N; ++v) {
+        if (ref.parent[v] >= 0) kids[(size_t)ref.parent[v]].push_back(v);
+        else root = v;
+    }
+    for (auto &k : kids) std::sort(k.begin(), k.end(), [&](size_t x, size_t y) { return lo[x] < lo[y]; });
+    struct Edge { size_t v, w; bool through_root; };
+    std::vector<Edge> edges;
+    for (size_t v = 0; v < N; ++v) {
+        if (v == root || kids[v].empty()) continue;
+        const size_t u = (size_t)ref.parent[v];
+        if (u == root && kids[u].size() == 2) {
+            const size_t o = kids[u][0] == v ? kids[u][1] : kids[u][0];
+            if (!kids[o].empty() && v == kids[u][0]) edges.push_back({v, o, true});
+        } else edges.push_back({v, u, false});
+    }
+    // taxa in x's link at the node `end`, whose link towards `away` (N = none) is the edge itself
+    auto link_size = [&](size_t end, size_t x, size_t away) {
+        for (size_t k : kids[end])
+            if (k != away && lo[k] <= x && x < hi[k]) return hi[k] - lo[k];
+        return n - (hi[end] - lo[end]);   // the parent's side
+    };
+    std::ofstream f(path);
+    if (!f) throw std::runtime_error("cannot write " + path);
+    f << "taxon\tname\tnode\tlo\thi\tgroup\tquartets\tq1\tq2\tq3\tqpic\tqpic_without\tdelta\n";
+    char qpic[64], without[64], delta[64];
+    for (size_t k = 0; k < L; ++k) {
+        const size_t x = ids[k];
+        for (const Edge &e : edges) {
+            const int64_t *r = &w[(k * N + e.v) * 4], *t = totals + e.v * 4;
+            const bool below = lo[e.v] <= x && x < hi[e.v];
+            const size_t group = below ? link_size(e.v, x, N) : e.through_root ? link_size(e.w, x, N) : link_size(e.w, x, e.v);
+            const double full = raw_log_score((size_t)t[1], (size_t)t[2], (size_t)t[3]);
+            std::snprintf(qpic, sizeof qpic, "%.6f", full);
+            if (t[0] - r[0] > 0) {
+                const double rest = raw_log_score((size_t)(t[1] - r[1]), (size_t)(t[2] - r[2]), (size_t)(t[3] - r[3]));
+                std::snprintf(without, sizeof without, "%.6f", rest);
+                std::snprintf(delta, sizeof delta, "%.6f", rest - full);
+            } else {
+                std::snprintf(without, sizeof without, "nan");
+                std::snprintf(delta, sizeof delta, "nan");
+            }
+            f << x << '\t' << ref.names[x] << '\t' << e.v << '\t' << lo[e.v] << '\t' << hi[e.v] << '\t' << group << '\t' << r[0] << '\t' << r[1] << '\t'
+              << r[2] << '\t' << r[3] << '\t' << qpic << '\t' << without << '\t' << delta << '\n';
+        }
+    }
+    if (!f) throw std::runtime_error("cannot write " + path);
+}
+
 // --place-clades: refused before the device is touched where the whole table is not on one GPU, where FILE exists or is another output,
 // and where a line of --place-clades-only names a label the -r tree lacks, the whole tree, a clade with fewer than three taxa outside it
 // or a clade an earlier line names; leaves the nodes to place in a.place_nodes
@@ -731,7 +848,7 @@ void check_place_clades(Args &a) {
     }
     if (a.gpus > 0 || a.table_shards >= 0)
         throw std::runtime_error("--place-clades needs the whole count table on one GPU: omit --gpus / --table-shards");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.taxon_pairs};
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.taxon_pairs, a.drop_one};
     for (const AlsoRef &x : a.also) others.insert(x.out);
     for (const WithoutTaxa &x : a.without) others.insert(x.out);
     if (others.count(a.place_clades)) throw std::runtime_error("--place-clades: " + a.place_clades + " is also another output file");
@@ -902,7 +1019,7 @@ void check_test_groups(Args &a) {
     if (a.test_groups.empty()) return;
     if (a.gpus > 0 || a.table_shards >= 0)
         throw std::runtime_error("--test-groups needs the whole count table on one GPU: omit --gpus / --table-shards");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.place_clades, a.taxon_pairs};
+    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.place_clades, a.taxon_pairs, a.drop_one};
     for (const AlsoRef &x : a.also) others.insert(x.out);
     for (const WithoutTaxa &x : a.without) others.insert(x.out);
     if (others.count(a.test_groups)) throw std::runtime_error("--test-groups: " + a.test_groups + " is also another output file");
@@ -1112,6 +1229,7 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
     if (!a.place_clades.empty()) write_place_clades(qsc.context(), qsc.reference(), a.dev.device, a.place_clades, a.place_nodes);
     if (!a.test_groups.empty()) write_test_groups(qsc.context(), a.dev.device, a);
     if (!a.taxon_pairs.empty()) write_taxon_pairs(qsc.context(), qsc.reference(), a.dev.device, a.taxon_pairs, a.pair_ids);
+    if (!a.drop_one.empty()) write_drop_one(qsc.context(), qsc.reference(), a.dev.device, a.drop_one, a.drop_ids);
     if (!a.also.empty() || !a.without.empty()) {   // the primary tree's output first, exactly as without --also-ref / --without-taxa
         write_annotated(referenceTree, a.out, lqic, qpic, eqpic);
         score_also_refs(a, qsc.context(), qsc.reference(), also_table);
@@ -1145,6 +1263,7 @@ int main(int argc, char *argv[]) {
         check_place_clades(a);
         check_test_groups(a);
         check_taxon_pairs(a);
+        check_drop_one(a);
     } catch (const std::exception &e) {
         std::cerr << "ERROR: " << e.what() << std::endl;
         return 1;

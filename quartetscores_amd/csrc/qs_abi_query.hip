@@ -1,6 +1,6 @@
-// qs_abi_query.hip -- what reads a finished table and is not the score: per-taxon and per-pair support, taxon and clade placement, per-tree
+// qs_abi_query.hip -- what reads a finished table and is not the score: per-taxon, per-pair and per-branch-and-taxon support, taxon and clade placement, per-tree
 // agreement (against a reference tree), the agreement of the evaluation trees with each other and the support of taxon groups (against
-// none). Host code only; the kernels are in qs_taxon.hip, qs_taxon_pairs.hip, qs_place.hip, qs_place_clade.hip, qs_agree.hip, qs_agree_pairs.hip and
+// none). Host code only; the kernels are in qs_taxon.hip, qs_taxon_pairs.hip, qs_branch_taxa.hip, qs_place.hip, qs_place_clade.hip, qs_agree.hip, qs_agree_pairs.hip and
 // qs_groups.hip.
 #include "qs_ctx.hpp"
 #include "qs_plan.hpp"
@@ -229,6 +229,122 @@ extern "C" int qs_taxon_pair_support(qs_ctx *c, const qs_ref_tree *ref, const ui
     // 32-bit partial sums: a walk has q < 4096 steps of up to three counts each
     const bool wide = max_count >= (1ull << 32) / (4096 * 3);
     QS_HIP(c, launch_taxon_pairs(c->stream, pd, n_list, wide, c->n_cu, reinterpret_cast<unsigned long long *>(dst_device)));
+    return QS_OK;   // asynchronous on the context's stream
+}
+
+// qs_branch_taxon_support: the internodes of the cached reference tree on the device, beside its LCA matrix
+static int ensure_branch_ref(qs_ctx *c, const RefHost &R) {
+    if (c->branch_next_dev) return QS_OK;
+    const uint32_t n = R.n, N = R.n_nodes, NI = R.n_inner, none = 0xFFFFFFFFu;
+    // next[i][p]: the end of the run of p over which lca(p,i) stays the same, on either side of the diagonal (a run ends in front of i
+    // and behind it: the sorted order of a 4-set changes there)
+    c->branch_next.assign((size_t)n * n, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+        const size_t o = (size_t)i * n;
+        c->branch_next[o + n - 1] = (uint16_t)n;
+        for (uint32_t p = n - 1; p-- > 0;)
+            c->branch_next[o + p] = (R.lca[o + p] != R.lca[o + p + 1] || p == i || p + 1 == i) ? (uint16_t)(p + 1) : c->branch_next[o + p + 1];
+    }
+    // the internode above a node v: both ends inner nodes; under a degree-2 root its two inner children are the ends of one
+    std::vector<std::vector<uint32_t>> kids(N);
+    for (uint32_t v = 0; v < N; ++v)
+        if (R.parent[v] >= 0) kids[(uint32_t)R.parent[v]].push_back(v);
+    for (auto &k : kids) std::sort(k.begin(), k.end(), [&](uint32_t a, uint32_t b) { return R.leaf_lo[a] < R.leaf_lo[b]; });
+    auto pairs_of_links = [&](uint32_t v, uint32_t without, bool up) {   // sum over two different links of v of the product of their sizes
+        uint64_t s = 0, s2 = 0;
+        for (uint32_t k : kids[v]) if (k != without) { s += R.leaf_cnt[k]; s2 += (uint64_t)R.leaf_cnt[k] * R.leaf_cnt[k]; }
+        if (up && R.parent[v] >= 0) { const uint64_t o = n - R.leaf_cnt[v]; s += o; s2 += o * o; }
+        return (s * s - s2) / 2;
+    };
+    c->branch_words.assign((size_t)2 * NI + N, none);
+    uint32_t *par = c->branch_words.data(), *node = par + NI, *edge_key = node + NI;
+    c->branch_quartets.assign(N, 0);
+    c->branch_dup_from = none; c->branch_dup_to = 0;
+    for (uint32_t j = 0; j < NI; ++j) node[j] = R.inner_node[j];
+    const bool merged = R.root_deg2 && R.nchild[kids[R.root][0]] > 0 && R.nchild[kids[R.root][1]] > 0;
+    for (uint32_t v = 0; v < N; ++v) {
+        if (R.nchild[v] == 0 || R.parent[v] < 0) continue;
+        const uint32_t u = (uint32_t)R.parent[v];
+        uint32_t w = u;                    // the other end
+        uint64_t there;                    // pairs of links at the other end
+        if (u == R.root && R.root_deg2) {
+            if (!merged) continue;
+            w = kids[u][0] == v ? kids[u][1] : kids[u][0];
+            there = pairs_of_links(w, none, false);
+            if (v == kids[u][1]) { par[R.inner_id[v]] = R.inner_id[w]; c->branch_dup_from = R.inner_id[v]; c->branch_dup_to = w; }
+        } else {
+            there = pairs_of_links(u, v, true);
+            par[R.inner_id[v]] = R.inner_id[u];
+        }
+        const uint32_t iv = R.inner_id[v], iw = R.inner_id[w];
+        edge_key[v] = std::min(iv, iw) * NI + std::max(iv, iw);
+        c->branch_quartets[v] = pairs_of_links(v, none, false) * there;
+    }
+    DevBuf<uint16_t> next; DevBuf<uint32_t> words; DevBuf<unsigned long long> quartets;
+    QS_HIP(c, next.reserve(c->branch_next.size() * 2, nullptr));
+    QS_HIP(c, words.reserve(c->branch_words.size() * 4, nullptr));
+    QS_HIP(c, quartets.reserve(c->branch_quartets.size() * 8, nullptr));
+    QS_HIP(c, hipMemcpyAsync(next.get(), c->branch_next.data(), c->branch_next.size() * 2, hipMemcpyHostToDevice, c->stream));
+    QS_HIP(c, hipMemcpyAsync(words.get(), c->branch_words.data(), c->branch_words.size() * 4, hipMemcpyHostToDevice, c->stream));
+    QS_HIP(c, hipMemcpyAsync(quartets.get(), c->branch_quartets.data(), c->branch_quartets.size() * 8, hipMemcpyHostToDevice, c->stream));
+    c->branch_next_dev = std::move(next); c->branch_words_dev = std::move(words); c->branch_quartets_dev = std::move(quartets);
+    return QS_OK;
+}
+
+// The four words (4-sets, F1, F2, F3) of every internode of the reference tree over the 4-sets around it that hold a listed taxon
+// (qs_branch_taxa.hip), and over all 4-sets around it (the adjacent node pairs of one score pass 1 over the context's own table). The
+// reference never asks what a branch's support would be without one taxon: this replaces nothing there.
+extern "C" int qs_branch_taxon_support(qs_ctx *c, const qs_ref_tree *ref, const uint16_t *taxa, uint32_t n_list, int64_t *rows_device,
+                                       int64_t *totals_device) {
+    if (!c) return QS_ERR_ARG;
+    if (!rows_device) return fail(c, QS_ERR_ARG, "qs_branch_taxon_support: NULL argument");
+    if (reinterpret_cast<uintptr_t>(rows_device) % 8 || reinterpret_cast<uintptr_t>(totals_device) % 8)
+        return fail(c, QS_ERR_ARG, "qs_branch_taxon_support: rows_device / totals_device is not 8-byte aligned");
+    if (!c->table) return fail(c, QS_ERR_STATE, "qs_branch_taxon_support: no table");
+    // every sum is at most C(n-1,3) x (largest count), a total C(n,4) x it: the bound of qs_taxon_support
+    const uint64_t max_count = table_max_count(c);
+    const uint64_t per_taxon = c->n >= 4 ? (uint64_t)(c->n - 1) * (c->n - 2) / 2 * (c->n - 3) / 3 : 0;
+    if (per_taxon && max_count > (uint64_t)INT64_MAX / per_taxon)
+        return fail(c, QS_ERR_OVERFLOW, "qs_branch_taxon_support: C(n-1,3) x the largest possible count exceeds 63 bits");
+    if (c->d_lo != 0 || c->d_hi != c->n) return fail(c, QS_ERR_UNSUPPORTED, "qs_branch_taxon_support: a table-shard context (the walks of a taxon cross every shard: use a whole-table one)");
+    std::vector<uint16_t> list;
+    if (int rc = check_taxon_list(c, "qs_branch_taxon_support", taxa, n_list, list)) return rc;
+    QS_HIP(c, hipSetDevice(c->device));
+    const RefHost *Rp = nullptr;
+    if (int rc = get_ref(c, ref, true, &Rp)) return rc;
+    if (branch_taxa_lds_bytes(Rp->n_inner) > 160u * 1024u)
+        return fail(c, QS_ERR_UNSUPPORTED, "qs_branch_taxon_support: more than 4551 inner nodes (the sums of a workgroup live in LDS)");
+    if (int rc = ensure_branch_ref(c, *Rp)) return rc;
+    if (int rc = ensure_n_cu(c)) return rc;
+    if (int rc = ensure_place_walks(c, list)) return rc;
+    const uint32_t NI = Rp->n_inner, N = Rp->n_nodes;
+    BranchDevice bd;
+    bd.ref_lca = c->ref_lca_dev.get(); bd.tasks = c->place_tasks_dev.get(); bd.taxa = c->place_taxa_dev.get();
+    bd.par = c->branch_words_dev.get(); bd.inner_node = bd.par + NI; bd.next = c->branch_next_dev.get();
+    bd.n = c->n; bd.n_nodes = N; bd.n_inner = NI; bd.n_tasks = (uint32_t)c->place_tasks.size();
+    bd.dup_from = c->branch_dup_from; bd.dup_to = c->branch_dup_to;
+    bd.frame = Rp->bifurcating ? 0 : 1;   // (fill_score_device: the order of (q1,q2,q3) qs_score uses without flags)
+    bd.table = c->table; bd.count_bits = (int)c->count_bits;   // the context's own table, not a scoring view
+    QS_HIP(c, hipMemsetAsync(rows_device, 0, (size_t)n_list * N * kBranchWords * 8, c->stream));
+    const bool wide = max_count >= (1ull << 32) / 4096 || c->n > 4096;   // the rule of qs_taxon_placement
+    QS_HIP(c, launch_branch_taxa(c->stream, bd, n_list, wide, c->n_cu, reinterpret_cast<unsigned long long *>(rows_device)));
+    if (totals_device) {
+        // one streaming read: the exact 64-bit sums per node pair of a plain pass 1 (no candidate log, no view, no sums of the pairs
+        // (degree-2 root, v)) into a buffer of this call's own; the adjacent pairs are the internodes
+        const size_t np = (size_t)NI * NI;
+        QS_HIP(c, c->branch_sums.reserve(np * 4 * 8, &c->stream));
+        unsigned long long *sums = c->branch_sums.get();
+        QS_HIP(c, hipMemsetAsync(sums, 0, np * 3 * 8, c->stream));
+        QS_HIP(c, hipMemsetAsync(sums + np * 3, 0x7F, np * 8, c->stream));
+        if (int rc = ensure_score_tables(c)) return rc;
+        ScoreDevice sd;
+        fill_score_device(c, *Rp, c->ref_lca_dev.get(), sd);
+        sd.rank_lo = c->rank_lo; sd.n_tuples = c->n_tuples; sd.table = c->table; sd.count_bits = (int)c->count_bits;
+        sd.pair_sums = sums; sd.pair_min = reinterpret_cast<long long *>(sums + np * 3);
+        if (int rc = ensure_bundle_plan(c, sd, 1)) return rc;
+        QS_HIP(c, launch_score_pass1(c->stream, sd, c->tune_score_kernel, c->n_cu, c->bundle[0].part_lo, c->bundle[0].part_n, c->bundle[0].n_parts, c->tune_score_tol));
+        QS_HIP(c, launch_branch_totals(c->stream, sums, bd.inner_node + NI, c->branch_quartets_dev.get(), N, reinterpret_cast<unsigned long long *>(totals_device)));
+    }
     return QS_OK;   // asynchronous on the context's stream
 }
 

@@ -169,6 +169,7 @@ int qs::get_ref(qs_ctx *c, const qs_ref_tree *ref, bool want_dev, const RefHost 
         fresh->leaf_node_in.assign(ref->leaf_node, ref->leaf_node + ref->n_taxa);
         if (c->ref_lca_dev) { (void)hipStreamSynchronize(c->stream); c->ref_lca_dev.reset(); c->ref_next_dev.reset(); c->root_pairs_dev.reset(); }
         if (c->place_child_dev) { (void)hipStreamSynchronize(c->stream); c->place_child_dev.reset(); c->place_next_dev.reset(); c->place_node_dev.reset(); }
+        if (c->branch_next_dev) { (void)hipStreamSynchronize(c->stream); c->branch_next_dev.reset(); c->branch_words_dev.reset(); c->branch_quartets_dev.reset(); }
         c->ref_cache = std::move(fresh);
         R = c->ref_cache.get();
         c->log_valid = false;
@@ -195,7 +196,7 @@ int qs::get_ref(qs_ctx *c, const qs_ref_tree *ref, bool want_dev, const RefHost 
 // log(k) and 1/k for the integer arguments of the device QIC: every count and every tuple sum is at most the
 // number of trees counted. Unknown (uploaded / attached tables, reduce-scattered shards): 65536 entries, larger
 // values take the kernel's slow path.
-static int ensure_score_tables(qs_ctx *c) {
+int qs::ensure_score_tables(qs_ctx *c) {
     // every count and every tuple sum is at most the number of trees behind the table: what this context counted, or what
     // the caller says stands behind a reduced / uploaded / viewed table (QS_TUNE_TABLE_TREES)
     const uint64_t want64 = std::min<uint64_t>(std::max<uint64_t>(std::max(c->trees_counted, c->table_trees_hint) + 1, 65536), 1ull << 20);

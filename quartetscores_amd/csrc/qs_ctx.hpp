@@ -176,6 +176,17 @@ struct qs_ctx {
     std::vector<uint32_t> place_tasks;
     DevBuf<uint16_t> place_child_dev, place_next_dev, place_taxa_dev;
     DevBuf<uint32_t> place_node_dev, place_tasks_dev;
+    // qs_branch_taxon_support: the cached reference tree's run ends on both sides of the diagonal, its words (par | inner_node | edge_key,
+    // BranchDevice) and the internodes' numbers of 4-sets (dropped with ref_lca_dev), kept like the lists above; the node-pair sums and
+    // minima of the score pass 1 behind the totals (grown, never shrunk)
+    std::vector<uint16_t> branch_next;
+    std::vector<uint32_t> branch_words;
+    std::vector<unsigned long long> branch_quartets;
+    DevBuf<uint16_t> branch_next_dev;
+    DevBuf<uint32_t> branch_words_dev;
+    DevBuf<unsigned long long> branch_quartets_dev;
+    uint32_t branch_dup_from = 0xFFFFFFFFu, branch_dup_to = 0;
+    DevBuf<unsigned long long> branch_sums;
     // qs_clade_placement: the walks in the numbering of the ids outside a clade (one list for every clade size) and the last call's
     // clades and workgroups, kept like the lists above
     std::vector<uint32_t> clade_tasks, clade_list;
@@ -216,6 +227,7 @@ hipError_t mark(qs_ctx *c, int kind, const hipStream_t *on = nullptr, uint32_t f
 int build_ref_shape(qs_ctx *c, const qs_ref_tree *ref, RefHost &R);
 int get_ref(qs_ctx *c, const qs_ref_tree *ref, bool want_dev, const RefHost **out);
 void fill_score_device(const qs_ctx *c, const RefHost &R, const uint32_t *lca_dev, ScoreDevice &sd);
+int ensure_score_tables(qs_ctx *c);          // the log table of the device QIC for the trees behind c's table
 int ensure_bundle_plan(qs_ctx *c, ScoreDevice &sd, int pass);
 
 }  // namespace qs

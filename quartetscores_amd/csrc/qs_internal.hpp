@@ -206,6 +206,27 @@ struct PairDevice {
 constexpr int kPairFields = 8;    // n_rt, n_ra, T_rt, S_rt, T_ra, S_ra, T_all, S_all
 size_t taxon_pairs_lds_bytes(uint32_t n);
 hipError_t launch_taxon_pairs(hipStream_t s, const PairDevice &pd, uint32_t n_list, bool wide, int n_cu, unsigned long long *dst);
+// qs_branch_taxa.hip: per listed taxon x = bd.taxa[0 .. n_list) and internode the four words over the 4-sets around the internode
+// that hold x (qs_branch_taxon_support); whole tables only. ref_lca, tasks, taxa, inner_node as in PlaceDevice. par[j] = compact inner
+// id of the parent of inner node j (none: all ones); under a degree-2 root with two inner children par[second] = first, dup_from =
+// the second's inner id and dup_to = the first's node (else dup_from = all ones). next[i][p] = the first p' > p at which lca(p',i)
+// differs or p' - 1 or p' is i (n if none): run ends on both sides of the diagonal. frame as in ScoreDevice. dst = n_list rows of
+// n_nodes x 4 words, zeroed beforehand; wide: counts may reach 2^32 / 4096
+struct BranchDevice {
+    const uint32_t *ref_lca, *inner_node, *tasks, *par;
+    const uint16_t *next, *taxa;
+    uint32_t n, n_nodes, n_inner, n_tasks, dup_from, dup_to;
+    int frame;
+    const void *table;
+    int count_bits;
+};
+constexpr int kBranchWords = 4;   // quartets, F1, F2, F3
+size_t branch_taxa_lds_bytes(uint32_t n_inner);
+hipError_t launch_branch_taxa(hipStream_t s, const BranchDevice &bd, uint32_t n_list, bool wide, int n_cu, unsigned long long *dst);
+// ... and the same words over ALL 4-sets around every internode, picked from the node-pair sums of a score pass 1: edge_key[v] = the
+// key of the node pair at the ends of the internode above node v (all ones: none), quartets[v] = its number of 4-sets
+hipError_t launch_branch_totals(hipStream_t s, const unsigned long long *sums, const uint32_t *edge_key, const unsigned long long *quartets,
+                                uint32_t n_nodes, unsigned long long *dst);
 // qs_place_clade.hip: link sums of the quartet placement of listed clades (qs_clade_placement); whole tables only. ref_lca, inner_node,
 // child, next as in PlaceDevice. tasks = d | group of 64 largest ids << 16 by d ascending, in the numbering of the ids OUTSIDE a clade:
 // the walk of the middle id n_outside - 1 - d (d = 1 ..: the longest walks first), so that the first clades[4 i + 3] entries are the walks

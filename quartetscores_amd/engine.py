@@ -131,6 +131,73 @@ def taxon_pair_columns(counts, names, taxa=None) -> dict:
     return out
 
 
+BRANCH_TAXON_FIELDS = ("quartets", "q1", "q2", "q3")
+DROP_ONE_COLUMNS = ("taxon", "name", "node", "lo", "hi", "group", "quartets", "q1", "q2", "q3", "qpic", "qpic_without", "delta")
+
+
+def drop_one_columns(ref: flatten.RefTree, taxa, rows, totals) -> dict:
+    """The columns of QuartetScores --drop-one from Context.branch_taxon_support: rows (len(taxa), n_nodes, 4) and totals (n_nodes, 4)
+    int64 in BRANCH_TAXON_FIELDS order, taxa = the lookup ids of the rows (None = all, in id order) -> dict in DROP_ONE_COLUMNS order
+    with one entry per row's taxon (in the order of taxa) and internode (in node order; under a degree-2 root the edge through the root
+    once, at the child that holds lookup id 0): int64 arrays taxon, node = the edge's child node, [lo, hi) = the lookup ids below it,
+    group = the number of taxa in the taxon's link at its end of the edge, quartets q1 q2 q3 = the row's words, the list name and the
+    float64 arrays qpic = log_score(totals), qpic_without = log_score(totals - row), nan where no 4-set around the edge is left
+    without the taxon (it is alone in its link at an end of degree 3: the edge dissolves), and delta = qpic_without - qpic."""
+    parent = np.asarray(ref.parent, dtype=np.int64)
+    N, n = len(parent), ref.n_taxa
+    ids = np.arange(n, dtype=np.int64) if taxa is None else np.asarray(taxa, dtype=np.int64).reshape(-1)
+    rows = np.asarray(rows, dtype=np.int64).reshape(len(ids), N, 4)
+    totals = np.asarray(totals, dtype=np.int64).reshape(N, 4)
+    lo, hi = np.full(N, n, dtype=np.int64), np.zeros(N, dtype=np.int64)
+    for i in range(n):
+        v = int(ref.leaf_node[i])
+        while v >= 0:
+            lo[v], hi[v] = min(lo[v], i), max(hi[v], i + 1)
+            v = int(parent[v])
+    kids = [sorted(np.nonzero(parent == v)[0].tolist(), key=lambda k: lo[k]) for v in range(N)]
+    root = int(np.nonzero(parent < 0)[0][0])
+
+    def link_size(end, x, away):
+        """taxa in x's link at the node `end`, whose link towards `away` is the edge itself"""
+        for k in kids[end]:
+            if k != away and lo[k] <= x < hi[k]:
+                return int(hi[k] - lo[k])
+        return int(n - (hi[end] - lo[end]))          # the parent's side
+
+    edges = []                                       # (child node, other end)
+    for v in range(N):
+        if v == root or not kids[v]:
+            continue
+        u = int(parent[v])
+        if u == root and len(kids[u]) == 2:
+            w = kids[u][1] if kids[u][0] == v else kids[u][0]
+            if kids[w] and v == kids[u][0]:
+                edges.append((v, w))
+        else:
+            edges.append((v, u))
+    out = {name: [] for name in DROP_ONE_COLUMNS}
+    for k, x in enumerate(ids.tolist()):
+        for v, w in edges:
+            r, t = rows[k, v], totals[v]
+            below = lo[v] <= x < hi[v]
+            if below:
+                group = link_size(v, x, None)
+            elif int(parent[v]) == w:
+                group = link_size(w, x, v)
+            else:                                    # the other child of a degree-2 root
+                group = link_size(w, x, None)
+            left = [int(t[i] - r[i]) for i in range(4)]
+            qpic = log_score(int(t[1]), int(t[2]), int(t[3]))
+            without = log_score(left[1], left[2], left[3]) if left[0] > 0 else math.nan
+            for name, val in zip(DROP_ONE_COLUMNS, (x, ref.names[x], v, int(lo[v]), int(hi[v]), group, int(r[0]), int(r[1]), int(r[2]), int(r[3]),
+                                                    qpic, without, without - qpic)):
+                out[name].append(val)
+    for name in DROP_ONE_COLUMNS:
+        if name != "name":
+            out[name] = np.asarray(out[name], dtype=np.float64 if name in ("qpic", "qpic_without", "delta") else np.int64)
+    return out
+
+
 GROUP_FIELDS = ("quartets", "q1", "q2", "q3", "outvoted", "uninformed")
 GROUP_KINDS = ("quad", "split")
 
@@ -574,6 +641,30 @@ class Context:
         self.sync()
         del keep
         return buf[: n_list * width].cpu().numpy().reshape(n_list, self.n, 8)
+
+    def branch_taxon_support(self, ref: flatten.RefTree, taxa=None):
+        """qs_branch_taxon_support: per listed taxon x (lookup ids; None = all, in id order) and node v of `ref` the four words of
+        BRANCH_TAXON_FIELDS over the 4-sets around the internode above v that hold x, and the same words over all 4-sets around it
+        -> (rows int64 (n_list, n_nodes, 4), totals int64 (n_nodes, 4)); QP-IC of the internode without x is log_score of
+        (totals - rows[x])[1:4], and drop_one_columns turns both into the CLI's columns. Allocates the device buffers, waits for the
+        result and downloads it."""
+        import torch
+        ids = None
+        if taxa is not None:
+            wide = np.asarray(taxa, dtype=np.int64).reshape(-1)
+            if ((wide < 0) | (wide >= self.n)).any():     # (before the cast to the ABI's 16-bit ids, which would wrap)
+                raise QSError(_lib.QS_ERR_ARG, "branch_taxon_support: taxon id out of range")
+            ids = np.ascontiguousarray(wide, dtype=np.uint16)
+        n_list = self.n if ids is None else len(ids)
+        width = 4 * ref.n_nodes
+        buf = torch.empty(max(1, (n_list + 1) * width), dtype=torch.int64, device=f"cuda:{self.device}")
+        s, keep = self._ref_struct(ref)
+        self._chk(self.L.qs_branch_taxon_support(self.h, C.byref(s), None if ids is None else ids.ctypes.data_as(C.c_void_p), n_list,
+                                                 C.c_void_p(buf.data_ptr()), C.c_void_p(buf.data_ptr() + n_list * width * 8)))
+        self.sync()
+        del keep
+        host = buf[: (n_list + 1) * width].cpu().numpy()
+        return host[: n_list * width].reshape(n_list, ref.n_nodes, 4), host[n_list * width:].reshape(ref.n_nodes, 4)
 
     def clade_placement(self, ref: flatten.RefTree, nodes=None) -> np.ndarray:
         """qs_clade_placement: per listed non-root node of `ref` (None = eligible_clades(ref)) the 2 * n_nodes link sums W_C of the
