@@ -82,13 +82,13 @@ struct Args {
     std::string per_taxon;  // --per-taxon FILE: quartet support per taxon of -r from the count table (TSV)
     std::string place_taxa; // --place-taxa FILE: quartet placement of the taxa of -r from the count table (TSV)
     std::string place_only; // --place-only NAMES: a file of the taxon labels to place (default: all)
-    std::vector<uint16_t> place_ids;   // the lookup ids to place, ascending (check_place_taxa)
+    std::vector<uint16_t> place_ids;   // the lookup ids to place, ascending (check_taxon_list_output)
     std::string taxon_pairs;      // --taxon-pairs FILE: quartet support of the taxon pairs of -r from the count table (TSV)
     std::string taxon_pairs_only; // --taxon-pairs-only NAMES: a file of the taxon labels whose pairs are written (default: all)
-    std::vector<uint16_t> pair_ids;    // the lookup ids whose rows are computed, ascending (check_taxon_pairs)
+    std::vector<uint16_t> pair_ids;    // the lookup ids whose rows are computed, ascending (check_taxon_list_output)
     std::string drop_one;         // --drop-one FILE: QP-IC of every internode of -r without each single taxon, from the count table (TSV)
     std::string drop_one_only;    // --drop-one-only NAMES: a file of the taxon labels to drop (default: all)
-    std::vector<uint16_t> drop_ids;    // the lookup ids whose rows are computed, ascending (check_drop_one)
+    std::vector<uint16_t> drop_ids;    // the lookup ids whose rows are computed, ascending (check_taxon_list_output)
     std::string place_clades;      // --place-clades FILE: quartet placement of the clades of -r from the count table (TSV)
     std::string place_clades_only; // --place-clades-only SPEC: a file of the clades to place, one per line (default: every eligible inner clade)
     std::vector<uint32_t> place_nodes; // the nodes to place, in output order (check_place_clades)
@@ -372,18 +372,69 @@ void write_annotated(const Tree &tree, const std::string &path, const std::vecto
     out << write_newick(tree, comment) << "\n";
 }
 
+std::set<std::string> read_taxon_names(const std::string &path, const RefFlat &rf, const std::string &ref_path, const std::string &what);
+
+// the -r tree
+Tree read_reference(const Args &a) {
+    Tree primary;
+    const std::string text = slurp(a.ref);
+    NewickReader rr(text);
+    if (!rr.next(primary)) throw std::runtime_error("empty reference tree file");
+    return primary;
+}
+
+// Every output file of the command line with the option that names it; an option that was not given has an empty path
+std::vector<std::pair<std::string, std::string>> output_files(const Args &a) {
+    std::vector<std::pair<std::string, std::string>> files{
+        {"-o", a.out}, {"-q", a.raw}, {"--qic-binary", a.raw_bin}, {"--save-table", a.dev.save_table}, {"--per-tree", a.per_tree},
+        {"--tree-distances", a.tree_distances}, {"--per-taxon", a.per_taxon}, {"--place-taxa", a.place_taxa}, {"--place-clades", a.place_clades},
+        {"--test-groups", a.test_groups}, {"--taxon-pairs", a.taxon_pairs}, {"--drop-one", a.drop_one}};
+    for (const AlsoRef &x : a.also) files.emplace_back("--also-ref", x.out);
+    for (const WithoutTaxa &x : a.without) files.emplace_back("--without-taxa", x.out);
+    return files;
+}
+
+std::string output_file(const Args &a, const std::string &flag) {
+    for (const auto &e : output_files(a))
+        if (e.first == flag) return e.second;
+    return "";
+}
+
+// The FILE of `flag` (given): refused where another output of the command line goes to the same path, and where it exists
+void check_output_file(const Args &a, const std::string &flag) {
+    const std::string path = output_file(a, flag);
+    for (const auto &e : output_files(a))
+        if (e.first != flag && e.second == path) throw std::runtime_error(flag + ": " + path + " is also another output file");
+    if (std::ifstream(path).good()) throw std::runtime_error(flag + ": the output file " + path + " already exists");
+}
+
+// --X FILE [--X-only NAMES], an output per listed taxon of -r (--place-taxa, --taxon-pairs, --drop-one): refused before the device is
+// touched where the whole table is not on one GPU, where FILE exists or is another output, and where NAMES holds a label the -r tree
+// lacks; returns the lookup ids to compute, ascending (all without NAMES; none without FILE)
+std::vector<uint16_t> check_taxon_list_output(const Args &a, const std::string &flag, const std::string &only_flag, const std::string &only) {
+    if (output_file(a, flag).empty()) {
+        if (!only.empty()) throw std::runtime_error(only_flag + " needs " + flag + " FILE");
+        return {};
+    }
+    if (a.gpus > 0 || a.table_shards >= 0) throw std::runtime_error(flag + " needs the whole count table on one GPU: omit --gpus / --table-shards");
+    check_output_file(a, flag);
+    const RefFlat rf = flatten_reference(read_reference(a));
+    std::set<uint16_t> ids;
+    if (only.empty()) {
+        for (size_t i = 0; i < rf.names.size(); ++i) ids.insert((uint16_t)i);
+    } else {
+        for (const std::string &name : read_taxon_names(only, rf, a.ref, only_flag + " " + only + ": ")) ids.insert((uint16_t)rf.name_to_id.at(name));
+    }
+    return std::vector<uint16_t>(ids.begin(), ids.end());
+}
+
 // --also-ref: everything that needs no GPU, before the device is touched -- the files parse, every tree holds exactly the
 // taxa of -r, no OUT exists or repeats -o or another OUT, and qs_score_check passes for every tree with the run's flags
 void check_also_refs(Args &a) {
     if (a.also.empty()) return;
     if (a.gpus > 0 || a.table_shards >= 0)
         throw std::runtime_error("--also-ref works on one GPU with the whole table: omit --gpus / --table-shards");
-    Tree primary;
-    {
-        const std::string text = slurp(a.ref);
-        NewickReader rr(text);
-        if (!rr.next(primary)) throw std::runtime_error("empty reference tree file");
-    }
+    Tree primary = read_reference(a);
     const RefFlat rf = flatten_reference(primary);
     const std::set<std::string> names(rf.names.begin(), rf.names.end());
     std::set<std::string> outs{a.out};
@@ -428,12 +479,7 @@ void check_without_taxa(Args &a) {
     if (a.without.empty()) return;
     if (a.gpus > 0 || a.table_shards >= 0)
         throw std::runtime_error("--without-taxa works on one GPU with the whole table: omit --gpus / --table-shards");
-    Tree primary;
-    {
-        const std::string text = slurp(a.ref);
-        NewickReader rr(text);
-        if (!rr.next(primary)) throw std::runtime_error("empty reference tree file");
-    }
+    Tree primary = read_reference(a);
     const RefFlat rf = flatten_reference(primary);
     std::set<std::string> outs{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon};
     for (const AlsoRef &x : a.also) outs.insert(x.out);
@@ -456,11 +502,7 @@ void check_per_tree(const Args &a) {
     if (a.per_tree.empty()) return;
     if (a.gpus > 0 || a.table_shards >= 0 || !a.dev.load_table.empty())
         throw std::runtime_error("--per-tree needs the evaluation trees counted on one GPU: omit --gpus / --table-shards / --load-table");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_taxon, a.taxon_pairs, a.drop_one};
-    for (const AlsoRef &x : a.also) others.insert(x.out);
-    for (const WithoutTaxa &x : a.without) others.insert(x.out);
-    if (others.count(a.per_tree)) throw std::runtime_error("--per-tree: " + a.per_tree + " is also another output file");
-    if (std::ifstream(a.per_tree).good()) throw std::runtime_error("--per-tree: the output file " + a.per_tree + " already exists");
+    check_output_file(a, "--per-tree");
 }
 
 // --tree-distances: refused like --per-tree, before the device is touched
@@ -468,11 +510,7 @@ void check_tree_distances(const Args &a) {
     if (a.tree_distances.empty()) return;
     if (a.gpus > 0 || a.table_shards >= 0 || !a.dev.load_table.empty())
         throw std::runtime_error("--tree-distances needs the evaluation trees counted on one GPU: omit --gpus / --table-shards / --load-table");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.place_clades, a.test_groups, a.taxon_pairs, a.drop_one};
-    for (const AlsoRef &x : a.also) others.insert(x.out);
-    for (const WithoutTaxa &x : a.without) others.insert(x.out);
-    if (others.count(a.tree_distances)) throw std::runtime_error("--tree-distances: " + a.tree_distances + " is also another output file");
-    if (std::ifstream(a.tree_distances).good()) throw std::runtime_error("--tree-distances: the output file " + a.tree_distances + " already exists");
+    check_output_file(a, "--tree-distances");
 }
 
 // --per-tree: qs_tree_agreement behind every batch's count into one device buffer of 4 x m words, downloaded once after the last
@@ -522,11 +560,7 @@ void check_per_taxon(const Args &a) {
     if (a.per_taxon.empty()) return;
     if (a.gpus > 0 || a.table_shards >= 0)
         throw std::runtime_error("--per-taxon needs the whole count table on one GPU: omit --gpus / --table-shards");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.taxon_pairs, a.drop_one};
-    for (const AlsoRef &x : a.also) others.insert(x.out);
-    for (const WithoutTaxa &x : a.without) others.insert(x.out);
-    if (others.count(a.per_taxon)) throw std::runtime_error("--per-taxon: " + a.per_taxon + " is also another output file");
-    if (std::ifstream(a.per_taxon).good()) throw std::runtime_error("--per-taxon: the output file " + a.per_taxon + " already exists");
+    check_output_file(a, "--per-taxon");
 }
 
 // --per-taxon: one qs_taxon_support over the counted (or loaded) table, 6 x n words downloaded, one TSV line per taxon
@@ -580,37 +614,6 @@ struct PlaceShape {
             if (ref.parent[v] >= 0) { const size_t p = (size_t)ref.parent[v]; lo[p] = std::min(lo[p], lo[v]); hi[p] = std::max(hi[p], hi[v]); }
     }
 };
-
-// --place-taxa: refused before the device is touched where the whole table is not on one GPU, where FILE exists or is another output,
-// and where --place-only names a label the -r tree lacks; leaves the lookup ids to place in a.place_ids
-void check_place_taxa(Args &a) {
-    if (a.place_taxa.empty()) {
-        if (!a.place_only.empty()) throw std::runtime_error("--place-only needs --place-taxa FILE");
-        return;
-    }
-    if (a.gpus > 0 || a.table_shards >= 0)
-        throw std::runtime_error("--place-taxa needs the whole count table on one GPU: omit --gpus / --table-shards");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.taxon_pairs, a.drop_one};
-    for (const AlsoRef &x : a.also) others.insert(x.out);
-    for (const WithoutTaxa &x : a.without) others.insert(x.out);
-    if (others.count(a.place_taxa)) throw std::runtime_error("--place-taxa: " + a.place_taxa + " is also another output file");
-    if (std::ifstream(a.place_taxa).good()) throw std::runtime_error("--place-taxa: the output file " + a.place_taxa + " already exists");
-    Tree primary;
-    {
-        const std::string text = slurp(a.ref);
-        NewickReader rr(text);
-        if (!rr.next(primary)) throw std::runtime_error("empty reference tree file");
-    }
-    const RefFlat rf = flatten_reference(primary);
-    std::set<uint16_t> ids;
-    if (a.place_only.empty()) {
-        for (size_t i = 0; i < rf.names.size(); ++i) ids.insert((uint16_t)i);
-    } else {
-        for (const std::string &name : read_taxon_names(a.place_only, rf, a.ref, "--place-only " + a.place_only + ": "))
-            ids.insert((uint16_t)rf.name_to_id.at(name));
-    }
-    a.place_ids.assign(ids.begin(), ids.end());
-}
 
 // --place-taxa: one qs_taxon_placement over the counted (or loaded) table for the listed taxa, their link sums downloaded, per taxon
 // qs_placement_scores and the columns (tests/placement_model.py defines them): a position = the edges that induce the same
@@ -673,37 +676,6 @@ void write_place_taxa(qs_ctx *ctx, const RefFlat &ref, int device, const std::st
     if (!f) throw std::runtime_error("cannot write " + path);
 }
 
-// --taxon-pairs: refused before the device is touched where the whole table is not on one GPU, where FILE exists or is another output,
-// and where --taxon-pairs-only names a label the -r tree lacks; leaves the lookup ids whose rows are computed in a.pair_ids
-void check_taxon_pairs(Args &a) {
-    if (a.taxon_pairs.empty()) {
-        if (!a.taxon_pairs_only.empty()) throw std::runtime_error("--taxon-pairs-only needs --taxon-pairs FILE");
-        return;
-    }
-    if (a.gpus > 0 || a.table_shards >= 0)
-        throw std::runtime_error("--taxon-pairs needs the whole count table on one GPU: omit --gpus / --table-shards");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.place_clades, a.test_groups, a.tree_distances, a.drop_one};
-    for (const AlsoRef &x : a.also) others.insert(x.out);
-    for (const WithoutTaxa &x : a.without) others.insert(x.out);
-    if (others.count(a.taxon_pairs)) throw std::runtime_error("--taxon-pairs: " + a.taxon_pairs + " is also another output file");
-    if (std::ifstream(a.taxon_pairs).good()) throw std::runtime_error("--taxon-pairs: the output file " + a.taxon_pairs + " already exists");
-    Tree primary;
-    {
-        const std::string text = slurp(a.ref);
-        NewickReader rr(text);
-        if (!rr.next(primary)) throw std::runtime_error("empty reference tree file");
-    }
-    const RefFlat rf = flatten_reference(primary);
-    std::set<uint16_t> ids;
-    if (a.taxon_pairs_only.empty()) {
-        for (size_t i = 0; i < rf.names.size(); ++i) ids.insert((uint16_t)i);
-    } else {
-        for (const std::string &name : read_taxon_names(a.taxon_pairs_only, rf, a.ref, "--taxon-pairs-only " + a.taxon_pairs_only + ": "))
-            ids.insert((uint16_t)rf.name_to_id.at(name));
-    }
-    a.pair_ids.assign(ids.begin(), ids.end());
-}
-
 // --taxon-pairs: one qs_taxon_pair_support over the counted (or loaded) table for the listed taxa, their rows of n x 8 words downloaded,
 // one TSV line per pair a < b with a listed taxon (tests/taxon_pair_model.py defines the columns; the matrix is symmetric: a pair's
 // words come from the row of whichever of the two is listed)
@@ -738,37 +710,6 @@ void write_taxon_pairs(qs_ctx *ctx, const RefFlat &ref, int device, const std::s
               << (v[7] - v[6]) << '\t' << affinity << '\t' << kept << '\t' << joined << '\n';
         }
     if (!f) throw std::runtime_error("cannot write " + path);
-}
-
-// --drop-one: refused before the device is touched where the whole table is not on one GPU, where FILE exists or is another output,
-// and where --drop-one-only names a label the -r tree lacks; leaves the lookup ids whose rows are computed in a.drop_ids
-void check_drop_one(Args &a) {
-    if (a.drop_one.empty()) {
-        if (!a.drop_one_only.empty()) throw std::runtime_error("--drop-one-only needs --drop-one FILE");
-        return;
-    }
-    if (a.gpus > 0 || a.table_shards >= 0)
-        throw std::runtime_error("--drop-one needs the whole count table on one GPU: omit --gpus / --table-shards");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.place_clades, a.test_groups, a.tree_distances, a.taxon_pairs};
-    for (const AlsoRef &x : a.also) others.insert(x.out);
-    for (const WithoutTaxa &x : a.without) others.insert(x.out);
-    if (others.count(a.drop_one)) throw std::runtime_error("--drop-one: " + a.drop_one + " is also another output file");
-    if (std::ifstream(a.drop_one).good()) throw std::runtime_error("--drop-one: the output file " + a.drop_one + " already exists");
-    Tree primary;
-    {
-        const std::string text = slurp(a.ref);
-        NewickReader rr(text);
-        if (!rr.next(primary)) throw std::runtime_error("empty reference tree file");
-    }
-    const RefFlat rf = flatten_reference(primary);
-    std::set<uint16_t> ids;
-    if (a.drop_one_only.empty()) {
-        for (size_t i = 0; i < rf.names.size(); ++i) ids.insert((uint16_t)i);
-    } else {
-        for (const std::string &name : read_taxon_names(a.drop_one_only, rf, a.ref, "--drop-one-only " + a.drop_one_only + ": "))
-            ids.insert((uint16_t)rf.name_to_id.at(name));
-    }
-    a.drop_ids.assign(ids.begin(), ids.end());
 }
 
 // --drop-one: one qs_branch_taxon_support over the counted (or loaded) table for the listed taxa, their rows of n_nodes x 4 words and
@@ -848,17 +789,8 @@ void check_place_clades(Args &a) {
     }
     if (a.gpus > 0 || a.table_shards >= 0)
         throw std::runtime_error("--place-clades needs the whole count table on one GPU: omit --gpus / --table-shards");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.taxon_pairs, a.drop_one};
-    for (const AlsoRef &x : a.also) others.insert(x.out);
-    for (const WithoutTaxa &x : a.without) others.insert(x.out);
-    if (others.count(a.place_clades)) throw std::runtime_error("--place-clades: " + a.place_clades + " is also another output file");
-    if (std::ifstream(a.place_clades).good()) throw std::runtime_error("--place-clades: the output file " + a.place_clades + " already exists");
-    Tree primary;
-    {
-        const std::string text = slurp(a.ref);
-        NewickReader rr(text);
-        if (!rr.next(primary)) throw std::runtime_error("empty reference tree file");
-    }
+    check_output_file(a, "--place-clades");
+    Tree primary = read_reference(a);
     const RefFlat rf = flatten_reference(primary);
     const PlaceShape S(rf, "--place-clades");
     const size_t n = rf.names.size(), N = rf.parent.size();
@@ -1019,17 +951,8 @@ void check_test_groups(Args &a) {
     if (a.test_groups.empty()) return;
     if (a.gpus > 0 || a.table_shards >= 0)
         throw std::runtime_error("--test-groups needs the whole count table on one GPU: omit --gpus / --table-shards");
-    std::set<std::string> others{a.out, a.raw, a.raw_bin, a.dev.save_table, a.per_tree, a.per_taxon, a.place_taxa, a.place_clades, a.taxon_pairs, a.drop_one};
-    for (const AlsoRef &x : a.also) others.insert(x.out);
-    for (const WithoutTaxa &x : a.without) others.insert(x.out);
-    if (others.count(a.test_groups)) throw std::runtime_error("--test-groups: " + a.test_groups + " is also another output file");
-    if (std::ifstream(a.test_groups).good()) throw std::runtime_error("--test-groups: the output file " + a.test_groups + " already exists");
-    Tree primary;
-    {
-        const std::string text = slurp(a.ref);
-        NewickReader rr(text);
-        if (!rr.next(primary)) throw std::runtime_error("empty reference tree file");
-    }
+    check_output_file(a, "--test-groups");
+    Tree primary = read_reference(a);
     const RefFlat rf = flatten_reference(primary);
     const size_t n = rf.names.size();
     auto trimmed = [](const std::string &t) {
@@ -1259,11 +1182,11 @@ int main(int argc, char *argv[]) {
         check_per_tree(a);
         check_tree_distances(a);
         check_per_taxon(a);
-        check_place_taxa(a);
+        a.place_ids = check_taxon_list_output(a, "--place-taxa", "--place-only", a.place_only);
         check_place_clades(a);
         check_test_groups(a);
-        check_taxon_pairs(a);
-        check_drop_one(a);
+        a.pair_ids = check_taxon_list_output(a, "--taxon-pairs", "--taxon-pairs-only", a.taxon_pairs_only);
+        a.drop_ids = check_taxon_list_output(a, "--drop-one", "--drop-one-only", a.drop_one_only);
     } catch (const std::exception &e) {
         std::cerr << "ERROR: " << e.what() << std::endl;
         return 1;

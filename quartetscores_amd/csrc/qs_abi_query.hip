@@ -13,19 +13,39 @@
 
 using namespace qs;
 
+// The refusals the table queries share. Every entry point calls them in an order of its own, which its callers see (a 3000-taxon shard
+// is refused for its taxa, not for being a shard): they are not one prologue.
+static int need_args(qs_ctx *c, const char *who, bool all_given) {
+    return all_given ? QS_OK : fail(c, QS_ERR_ARG, std::string(who) + ": NULL argument");
+}
+static int need_aligned(qs_ctx *c, const char *who, const void *p, const char *name = "dst_device") {
+    return reinterpret_cast<uintptr_t>(p) % 8 ? fail(c, QS_ERR_ARG, std::string(who) + ": " + name + " is not 8-byte aligned") : QS_OK;
+}
+static int need_table(qs_ctx *c, const char *who) { return c->table ? QS_OK : fail(c, QS_ERR_STATE, std::string(who) + ": no table"); }
+static int need_whole_table(qs_ctx *c, const char *who, const char *unit) {
+    if (c->d_lo == 0 && c->d_hi == c->n) return QS_OK;
+    return fail(c, QS_ERR_UNSUPPORTED, std::string(who) + ": a table-shard context (the walks of a " + unit + " cross every shard: use a whole-table one)");
+}
+// every sum over the 4-sets that hold one taxon is at most C(n-1,3) x (largest count): the trees behind the table if known, else what
+// a cell can hold
+static int need_taxon_sums_fit(qs_ctx *c, const char *who, uint64_t max_count) {
+    const uint64_t per_taxon = c->n >= 4 ? (uint64_t)(c->n - 1) * (c->n - 2) / 2 * (c->n - 3) / 3 : 0;
+    if (per_taxon && max_count > (uint64_t)INT64_MAX / per_taxon)
+        return fail(c, QS_ERR_OVERFLOW, std::string(who) + ": C(n-1,3) x the largest possible count exceeds 63 bits");
+    return QS_OK;
+}
+
 // Per-taxon quartet support of this context's table against the reference tree (qs_taxon.hip). The reference has no such
 // output: this replaces nothing there (the nearest is printRawQICScores, one text line per quartet).
 extern "C" int qs_taxon_support(qs_ctx *c, const qs_ref_tree *ref, int64_t *dst_device) {
     if (!c) return QS_ERR_ARG;
-    if (!dst_device) return fail(c, QS_ERR_ARG, "qs_taxon_support: NULL argument");
-    if (reinterpret_cast<uintptr_t>(dst_device) % 8) return fail(c, QS_ERR_ARG, "qs_taxon_support: dst_device is not 8-byte aligned");
-    if (!c->table) return fail(c, QS_ERR_STATE, "qs_taxon_support: no table");
+    const char *who = "qs_taxon_support";
+    if (int rc = need_args(c, who, dst_device)) return rc;
+    if (int rc = need_aligned(c, who, dst_device)) return rc;
+    if (int rc = need_table(c, who)) return rc;
     if (taxon_lds_bytes(c->n) > 160u * 1024u) return fail(c, QS_ERR_UNSUPPORTED, "qs_taxon_support: more than 3413 taxa (the accumulators of a workgroup live in LDS)");
-    // every sum is at most C(n-1,3) x (largest count): the trees behind the table if known, else what a cell can hold
     const uint64_t max_count = table_max_count(c);
-    const uint64_t per_taxon = c->n >= 4 ? (uint64_t)(c->n - 1) * (c->n - 2) / 2 * (c->n - 3) / 3 : 0;
-    if (per_taxon && max_count > (uint64_t)INT64_MAX / per_taxon)
-        return fail(c, QS_ERR_OVERFLOW, "qs_taxon_support: C(n-1,3) x the largest possible count exceeds 63 bits");
+    if (int rc = need_taxon_sums_fit(c, who, max_count)) return rc;
     QS_HIP(c, hipSetDevice(c->device));
     const RefHost *Rp = nullptr;
     if (int rc = get_ref(c, ref, true, &Rp)) return rc;
@@ -56,10 +76,11 @@ extern "C" int qs_group_check(uint32_t n_taxa, const uint8_t *labels, uint32_t n
 // the metaquartet sum of processNodePair, which knows only the four subtrees beside a node pair of the reference tree.
 extern "C" int qs_group_support(qs_ctx *c, const uint8_t *labels, uint32_t n_hyp, int64_t *dst_device) {
     if (!c) return QS_ERR_ARG;
-    if (!labels || !dst_device) return fail(c, QS_ERR_ARG, "qs_group_support: NULL argument");
-    if (reinterpret_cast<uintptr_t>(dst_device) % 8) return fail(c, QS_ERR_ARG, "qs_group_support: dst_device is not 8-byte aligned");
+    const char *who = "qs_group_support";
+    if (int rc = need_args(c, who, labels && dst_device)) return rc;
+    if (int rc = need_aligned(c, who, dst_device)) return rc;
     if (n_hyp == 0) return fail(c, QS_ERR_ARG, "qs_group_support: n_hyp must be at least 1");
-    if (!c->table) return fail(c, QS_ERR_STATE, "qs_group_support: no table");
+    if (int rc = need_table(c, who)) return rc;
     const uint32_t n = c->n;
     std::vector<uint8_t> kind(n_hyp);
     std::vector<uint64_t> quartets(n_hyp);
@@ -167,21 +188,28 @@ static int ensure_place_walks(qs_ctx *c, const std::vector<uint16_t> &list) {
     return QS_OK;
 }
 
+// ... and what every gather over that list reads (after ensure_place_walks)
+static GatherDevice gather_device(const qs_ctx *c) {
+    GatherDevice g;
+    g.ref_lca = c->ref_lca_dev.get(); g.tasks = c->place_tasks_dev.get(); g.taxa = c->place_taxa_dev.get();
+    g.n = c->n; g.n_tasks = (uint32_t)c->place_tasks.size();
+    g.table = c->table; g.count_bits = (int)c->count_bits;   // the context's own table, not a scoring view
+    return g;
+}
+
 // Link sums of the quartet placement of the listed taxa (qs_place.hip). The reference never asks where the evaluation trees would
 // put a taxon: this replaces nothing there.
 extern "C" int qs_taxon_placement(qs_ctx *c, const qs_ref_tree *ref, const uint16_t *taxa, uint32_t n_list, int64_t *dst_device) {
     if (!c) return QS_ERR_ARG;
-    if (!dst_device) return fail(c, QS_ERR_ARG, "qs_taxon_placement: NULL argument");
-    if (reinterpret_cast<uintptr_t>(dst_device) % 8) return fail(c, QS_ERR_ARG, "qs_taxon_placement: dst_device is not 8-byte aligned");
-    if (!c->table) return fail(c, QS_ERR_STATE, "qs_taxon_placement: no table");
-    // every sum is at most C(n-1,3) x (largest count): the trees behind the table if known, else what a cell can hold (as qs_taxon_support)
+    const char *who = "qs_taxon_placement";
+    if (int rc = need_args(c, who, dst_device)) return rc;
+    if (int rc = need_aligned(c, who, dst_device)) return rc;
+    if (int rc = need_table(c, who)) return rc;
     const uint64_t max_count = table_max_count(c);
-    const uint64_t per_taxon = c->n >= 4 ? (uint64_t)(c->n - 1) * (c->n - 2) / 2 * (c->n - 3) / 3 : 0;
-    if (per_taxon && max_count > (uint64_t)INT64_MAX / per_taxon)
-        return fail(c, QS_ERR_OVERFLOW, "qs_taxon_placement: C(n-1,3) x the largest possible count exceeds 63 bits");
-    if (c->d_lo != 0 || c->d_hi != c->n) return fail(c, QS_ERR_UNSUPPORTED, "qs_taxon_placement: a table-shard context (the walks of a taxon cross every shard: use a whole-table one)");
+    if (int rc = need_taxon_sums_fit(c, who, max_count)) return rc;
+    if (int rc = need_whole_table(c, who, "taxon")) return rc;
     std::vector<uint16_t> list;
-    if (int rc = check_taxon_list(c, "qs_taxon_placement", taxa, n_list, list)) return rc;
+    if (int rc = check_taxon_list(c, who, taxa, n_list, list)) return rc;
     QS_HIP(c, hipSetDevice(c->device));
     const RefHost *Rp = nullptr;
     if (int rc = get_ref(c, ref, true, &Rp)) return rc;
@@ -191,10 +219,9 @@ extern "C" int qs_taxon_placement(qs_ctx *c, const qs_ref_tree *ref, const uint1
     if (int rc = ensure_n_cu(c)) return rc;
     if (int rc = ensure_place_walks(c, list)) return rc;
     PlaceDevice pd;
-    pd.ref_lca = c->ref_lca_dev.get(); pd.inner_node = c->place_node_dev.get(); pd.tasks = c->place_tasks_dev.get();
-    pd.child = c->place_child_dev.get(); pd.next = c->place_next_dev.get(); pd.taxa = c->place_taxa_dev.get();
-    pd.n = c->n; pd.n_nodes = Rp->n_nodes; pd.n_tasks = (uint32_t)c->place_tasks.size();
-    pd.table = c->table; pd.count_bits = (int)c->count_bits;   // the context's own table, not a scoring view
+    pd.g = gather_device(c);
+    pd.inner_node = c->place_node_dev.get(); pd.child = c->place_child_dev.get(); pd.next = c->place_next_dev.get();
+    pd.n_nodes = Rp->n_nodes;
     QS_HIP(c, hipMemsetAsync(dst_device, 0, (size_t)n_list * 2 * Rp->n_nodes * 8, c->stream));
     // 32-bit partial sums: a walk has q < n_taxa steps, so 4096 x (largest count) < 2^32 suffices only while n_taxa <= 4096
     // (qs_create's cap today; the LDS limit alone would allow more)
@@ -207,13 +234,14 @@ extern "C" int qs_taxon_placement(qs_ctx *c, const qs_ref_tree *ref, const uint1
 // output per pair of taxa: this replaces nothing there.
 extern "C" int qs_taxon_pair_support(qs_ctx *c, const qs_ref_tree *ref, const uint16_t *taxa, uint32_t n_list, int64_t *dst_device) {
     if (!c) return QS_ERR_ARG;
-    if (!dst_device) return fail(c, QS_ERR_ARG, "qs_taxon_pair_support: NULL argument");
-    if (reinterpret_cast<uintptr_t>(dst_device) % 8) return fail(c, QS_ERR_ARG, "qs_taxon_pair_support: dst_device is not 8-byte aligned");
-    if (!c->table) return fail(c, QS_ERR_STATE, "qs_taxon_pair_support: no table");
+    const char *who = "qs_taxon_pair_support";
+    if (int rc = need_args(c, who, dst_device)) return rc;
+    if (int rc = need_aligned(c, who, dst_device)) return rc;
+    if (int rc = need_table(c, who)) return rc;
     if (taxon_pairs_lds_bytes(c->n) > 160u * 1024u) return fail(c, QS_ERR_UNSUPPORTED, "qs_taxon_pair_support: more than 2560 taxa (the accumulators of a workgroup live in LDS)");
-    if (c->d_lo != 0 || c->d_hi != c->n) return fail(c, QS_ERR_UNSUPPORTED, "qs_taxon_pair_support: a table-shard context (the walks of a taxon cross every shard: use a whole-table one)");
+    if (int rc = need_whole_table(c, who, "taxon")) return rc;
     std::vector<uint16_t> list;
-    if (int rc = check_taxon_list(c, "qs_taxon_pair_support", taxa, n_list, list)) return rc;
+    if (int rc = check_taxon_list(c, who, taxa, n_list, list)) return rc;
     // (a word is at most C(n-2,2) x 3 x (largest count) < 2^23 x 2^34: no overflow to refuse)
     const uint64_t max_count = table_max_count(c);
     QS_HIP(c, hipSetDevice(c->device));
@@ -221,10 +249,7 @@ extern "C" int qs_taxon_pair_support(qs_ctx *c, const qs_ref_tree *ref, const ui
     if (int rc = get_ref(c, ref, true, &Rp)) return rc;
     if (int rc = ensure_n_cu(c)) return rc;
     if (int rc = ensure_place_walks(c, list)) return rc;
-    PairDevice pd;
-    pd.ref_lca = c->ref_lca_dev.get(); pd.tasks = c->place_tasks_dev.get(); pd.taxa = c->place_taxa_dev.get();
-    pd.n = c->n; pd.n_tasks = (uint32_t)c->place_tasks.size();
-    pd.table = c->table; pd.count_bits = (int)c->count_bits;   // the context's own table, not a scoring view
+    const GatherDevice pd = gather_device(c);
     QS_HIP(c, hipMemsetAsync(dst_device, 0, (size_t)n_list * c->n * kPairFields * 8, c->stream));
     // 32-bit partial sums: a walk has q < 4096 steps of up to three counts each
     const bool wide = max_count >= (1ull << 32) / (4096 * 3);
@@ -297,18 +322,16 @@ static int ensure_branch_ref(qs_ctx *c, const RefHost &R) {
 extern "C" int qs_branch_taxon_support(qs_ctx *c, const qs_ref_tree *ref, const uint16_t *taxa, uint32_t n_list, int64_t *rows_device,
                                        int64_t *totals_device) {
     if (!c) return QS_ERR_ARG;
-    if (!rows_device) return fail(c, QS_ERR_ARG, "qs_branch_taxon_support: NULL argument");
-    if (reinterpret_cast<uintptr_t>(rows_device) % 8 || reinterpret_cast<uintptr_t>(totals_device) % 8)
-        return fail(c, QS_ERR_ARG, "qs_branch_taxon_support: rows_device / totals_device is not 8-byte aligned");
-    if (!c->table) return fail(c, QS_ERR_STATE, "qs_branch_taxon_support: no table");
-    // every sum is at most C(n-1,3) x (largest count), a total C(n,4) x it: the bound of qs_taxon_support
+    const char *who = "qs_branch_taxon_support";
+    if (int rc = need_args(c, who, rows_device)) return rc;
+    for (const void *p : {(const void *)rows_device, (const void *)totals_device})
+        if (int rc = need_aligned(c, who, p, "rows_device / totals_device")) return rc;
+    if (int rc = need_table(c, who)) return rc;
     const uint64_t max_count = table_max_count(c);
-    const uint64_t per_taxon = c->n >= 4 ? (uint64_t)(c->n - 1) * (c->n - 2) / 2 * (c->n - 3) / 3 : 0;
-    if (per_taxon && max_count > (uint64_t)INT64_MAX / per_taxon)
-        return fail(c, QS_ERR_OVERFLOW, "qs_branch_taxon_support: C(n-1,3) x the largest possible count exceeds 63 bits");
-    if (c->d_lo != 0 || c->d_hi != c->n) return fail(c, QS_ERR_UNSUPPORTED, "qs_branch_taxon_support: a table-shard context (the walks of a taxon cross every shard: use a whole-table one)");
+    if (int rc = need_taxon_sums_fit(c, who, max_count)) return rc;   // (the bound of qs_taxon_support for a row; the totals are the score's sums)
+    if (int rc = need_whole_table(c, who, "taxon")) return rc;
     std::vector<uint16_t> list;
-    if (int rc = check_taxon_list(c, "qs_branch_taxon_support", taxa, n_list, list)) return rc;
+    if (int rc = check_taxon_list(c, who, taxa, n_list, list)) return rc;
     QS_HIP(c, hipSetDevice(c->device));
     const RefHost *Rp = nullptr;
     if (int rc = get_ref(c, ref, true, &Rp)) return rc;
@@ -319,12 +342,11 @@ extern "C" int qs_branch_taxon_support(qs_ctx *c, const qs_ref_tree *ref, const 
     if (int rc = ensure_place_walks(c, list)) return rc;
     const uint32_t NI = Rp->n_inner, N = Rp->n_nodes;
     BranchDevice bd;
-    bd.ref_lca = c->ref_lca_dev.get(); bd.tasks = c->place_tasks_dev.get(); bd.taxa = c->place_taxa_dev.get();
+    bd.g = gather_device(c);
     bd.par = c->branch_words_dev.get(); bd.inner_node = bd.par + NI; bd.next = c->branch_next_dev.get();
-    bd.n = c->n; bd.n_nodes = N; bd.n_inner = NI; bd.n_tasks = (uint32_t)c->place_tasks.size();
+    bd.n_nodes = N; bd.n_inner = NI;
     bd.dup_from = c->branch_dup_from; bd.dup_to = c->branch_dup_to;
     bd.frame = Rp->bifurcating ? 0 : 1;   // (fill_score_device: the order of (q1,q2,q3) qs_score uses without flags)
-    bd.table = c->table; bd.count_bits = (int)c->count_bits;   // the context's own table, not a scoring view
     QS_HIP(c, hipMemsetAsync(rows_device, 0, (size_t)n_list * N * kBranchWords * 8, c->stream));
     const bool wide = max_count >= (1ull << 32) / 4096 || c->n > 4096;   // the rule of qs_taxon_placement
     QS_HIP(c, launch_branch_taxa(c->stream, bd, n_list, wide, c->n_cu, reinterpret_cast<unsigned long long *>(rows_device)));
@@ -352,9 +374,10 @@ extern "C" int qs_branch_taxon_support(qs_ctx *c, const qs_ref_tree *ref, const 
 // inside, on every edge outside it. The reference never asks where the evaluation trees would put a subtree: this replaces nothing there.
 extern "C" int qs_clade_placement(qs_ctx *c, const qs_ref_tree *ref, const uint32_t *nodes, uint32_t n_list, int64_t *dst_device) {
     if (!c) return QS_ERR_ARG;
-    if (!dst_device) return fail(c, QS_ERR_ARG, "qs_clade_placement: NULL argument");
-    if (reinterpret_cast<uintptr_t>(dst_device) % 8) return fail(c, QS_ERR_ARG, "qs_clade_placement: dst_device is not 8-byte aligned");
-    if (!c->table) return fail(c, QS_ERR_STATE, "qs_clade_placement: no table");
+    const char *who = "qs_clade_placement";
+    if (int rc = need_args(c, who, dst_device)) return rc;
+    if (int rc = need_aligned(c, who, dst_device)) return rc;
+    if (int rc = need_table(c, who)) return rc;
     if (!nodes || n_list == 0) return fail(c, QS_ERR_ARG, "qs_clade_placement: the list needs at least one node");
     // the list against the tree's shape, before anything touches the device
     const uint32_t n = c->n;
@@ -382,7 +405,7 @@ extern "C" int qs_clade_placement(qs_ctx *c, const qs_ref_tree *ref, const uint3
         if (max_count > (uint64_t)INT64_MAX / cost[i])
             return fail(c, QS_ERR_OVERFLOW, "qs_clade_placement: |C| x C(n-|C|,3) x the largest possible count exceeds 63 bits for node " + std::to_string(nodes[i]));
     }
-    if (c->d_lo != 0 || c->d_hi != c->n) return fail(c, QS_ERR_UNSUPPORTED, "qs_clade_placement: a table-shard context (the walks of a clade cross every shard: use a whole-table one)");
+    if (int rc = need_whole_table(c, who, "clade")) return rc;
     if (place_lds_bytes(ref->n_nodes) > 160u * 1024u)
         return fail(c, QS_ERR_UNSUPPORTED, "qs_clade_placement: more than 10240 nodes (the link sums of a workgroup live in LDS)");
     QS_HIP(c, hipSetDevice(c->device));

@@ -179,46 +179,43 @@ constexpr int kGroupHyp = 8;      // hypotheses one read of the table serves (DE
 constexpr int kGroupWords = 6;    // quartets, F1, F2, F3, outvoted, uninformed
 hipError_t launch_group_support(hipStream_t s, const ScoreDevice &sd, const uint32_t *labw, uint32_t split_mask, uint32_t n_hyp, bool wide,
                                 int n_cu, unsigned long long *dst);
-// qs_place.hip: link sums of the quartet placement of the taxa pd.taxa[0 .. n_list) (qs_taxon_placement); whole tables only. child[i][j] =
-// node of the child of lca(i,j) that holds leaf j; next[q][p], p < q = the first p' > p at which lca(p',q) or child[q][p'] differs (q if
-// none); inner_node = node index of a compact inner id of ref_lca; tasks = q | group of 64 largest ids << 16, longest walks first;
-// dst = n_list rows of 2 x n_nodes words, zeroed beforehand; wide: counts may reach 2^32 / 4096
-struct PlaceDevice {
-    const uint32_t *ref_lca, *inner_node, *tasks;
-    const uint16_t *child, *next, *taxa;
-    uint32_t n, n_nodes, n_tasks;
-    const void *table;
-    int count_bits;
-};
-constexpr int kPlaceWaves = 4;
-size_t place_lds_bytes(uint32_t n_nodes);
-hipError_t launch_taxon_placement(hipStream_t s, const PlaceDevice &pd, uint32_t n_list, bool wide, int n_cu, unsigned long long *dst);
-// qs_taxon_pairs.hip: the eight words of every pair (x, j), x = pd.taxa[0 .. n_list), over the 4-sets that hold both
-// (qs_taxon_pair_support); whole tables only. ref_lca, tasks, taxa as in PlaceDevice (the same walk list); dst = n_list rows of n x 8
-// words, zeroed beforehand; wide: counts may reach 2^32 / (4096 x 3)
-struct PairDevice {
+// The gathers of the tuples that hold a listed taxon (qs_taxon_walk.hpp), whole tables only: ref_lca as in ScoreDevice; tasks = q | group
+// of 64 largest ids << 16, the walks of an n-taxon table, longest first; taxa = the listed ids, one row of dst each (zeroed beforehand)
+struct GatherDevice {
     const uint32_t *ref_lca, *tasks;
     const uint16_t *taxa;
     uint32_t n, n_tasks;
     const void *table;
     int count_bits;
 };
+constexpr int kPlaceWaves = 4;
+// qs_place.hip: link sums of the quartet placement of the listed taxa (qs_taxon_placement). child[i][j] = node of the child of lca(i,j)
+// that holds leaf j; next[q][p], p < q = the first p' > p at which lca(p',q) or child[q][p'] differs (q if none); inner_node = node index
+// of a compact inner id of ref_lca; dst = n_list rows of 2 x n_nodes words; wide: counts may reach 2^32 / 4096
+struct PlaceDevice {
+    GatherDevice g;
+    const uint32_t *inner_node;
+    const uint16_t *child, *next;
+    uint32_t n_nodes;
+};
+size_t place_lds_bytes(uint32_t n_nodes);
+hipError_t launch_taxon_placement(hipStream_t s, const PlaceDevice &pd, uint32_t n_list, bool wide, int n_cu, unsigned long long *dst);
+// qs_taxon_pairs.hip: the eight words of every pair (x, j), x a listed taxon, over the 4-sets that hold both (qs_taxon_pair_support);
+// needs nothing beyond the common fields; dst = n_list rows of n x 8 words; wide: counts may reach 2^32 / (4096 x 3)
 constexpr int kPairFields = 8;    // n_rt, n_ra, T_rt, S_rt, T_ra, S_ra, T_all, S_all
 size_t taxon_pairs_lds_bytes(uint32_t n);
-hipError_t launch_taxon_pairs(hipStream_t s, const PairDevice &pd, uint32_t n_list, bool wide, int n_cu, unsigned long long *dst);
-// qs_branch_taxa.hip: per listed taxon x = bd.taxa[0 .. n_list) and internode the four words over the 4-sets around the internode
-// that hold x (qs_branch_taxon_support); whole tables only. ref_lca, tasks, taxa, inner_node as in PlaceDevice. par[j] = compact inner
-// id of the parent of inner node j (none: all ones); under a degree-2 root with two inner children par[second] = first, dup_from =
-// the second's inner id and dup_to = the first's node (else dup_from = all ones). next[i][p] = the first p' > p at which lca(p',i)
-// differs or p' - 1 or p' is i (n if none): run ends on both sides of the diagonal. frame as in ScoreDevice. dst = n_list rows of
-// n_nodes x 4 words, zeroed beforehand; wide: counts may reach 2^32 / 4096
+hipError_t launch_taxon_pairs(hipStream_t s, const GatherDevice &pd, uint32_t n_list, bool wide, int n_cu, unsigned long long *dst);
+// qs_branch_taxa.hip: per listed taxon x and internode the four words over the 4-sets around the internode that hold x
+// (qs_branch_taxon_support). inner_node as in PlaceDevice. par[j] = compact inner id of the parent of inner node j (none: all ones);
+// under a degree-2 root with two inner children par[second] = first, dup_from = the second's inner id and dup_to = the first's node
+// (else dup_from = all ones). next[i][p] = the first p' > p at which lca(p',i) differs or p' - 1 or p' is i (n if none): run ends on
+// both sides of the diagonal. frame as in ScoreDevice. dst = n_list rows of n_nodes x 4 words; wide: counts may reach 2^32 / 4096
 struct BranchDevice {
-    const uint32_t *ref_lca, *inner_node, *tasks, *par;
-    const uint16_t *next, *taxa;
-    uint32_t n, n_nodes, n_inner, n_tasks, dup_from, dup_to;
+    GatherDevice g;
+    const uint32_t *inner_node, *par;
+    const uint16_t *next;
+    uint32_t n_nodes, n_inner, dup_from, dup_to;
     int frame;
-    const void *table;
-    int count_bits;
 };
 constexpr int kBranchWords = 4;   // quartets, F1, F2, F3
 size_t branch_taxa_lds_bytes(uint32_t n_inner);

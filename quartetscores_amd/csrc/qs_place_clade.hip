@@ -8,10 +8,10 @@
 // The median, its links and the cell order depend on (p, q, r) and on where the INTERVAL stands among them, not on x: the
 // kernel sums the tuples of a triple over x first and accounts for the triple once.
 //
-// Shape: qs_place.hip's. A wave owns the middle id q, its lanes 64 consecutive largest ids r > q (both outside the clade: the
+// Shape: the taxon gather's (qs_taxon_walk.hpp). A wave owns the middle id q, its lanes 64 consecutive largest ids r > q (both outside the clade: the
 // walks are numbered in the n - |C| outside ids and mapped over the interval), and walks p over [0, min(q, lo)) and then over
 // [hi, q): the walk jumps the interval.
-//   first stretch (p < lo)   per x one table row, consecutive in p, as in qs_place.hip:
+//   first stretch (p < lo)   per x one table row, consecutive in p, the taxon gather's first three address cases:
 //       r < lo        (p,q,r,x)  rank C(x,4) + C(r,3) + C(q,2) + p   cells (r, q, p)
 //       q < lo, hi<=r (p,q,x,r)  rank C(r,4) + C(x,3) + C(q,2) + p   cells (r, p, q)
 //       hi <= q       (p,x,q,r)  rank C(r,4) + C(q,3) + C(x,2) + p   cells (p, r, q)
@@ -19,64 +19,32 @@
 //   second stretch (hi <= p) (x,p,q,r)  rank C(r,4) + C(q,3) + C(p,2) + x   cells (p, q, r): consecutive in x, the clade's tuples
 //     are one contiguous piece of a table row, streamed in the same 96-byte chunks (what is left over: tuple by tuple), four
 //     steps of p requested together.
-// Then one accounting per step, qs_place.hip's: run sums with wave-uniform targets (reduced over the wave at the run's end),
-// lane-constant targets summed over the whole walk. A run of place_next may span the interval (a child of lca(p,q) can hold
+// Then one accounting per step, PlaceAccount of qs_taxon_walk.hpp. A run of place_next may span the interval (a child of lca(p,q) can hold
 // p, the clade and p' together): at p = hi the run is always closed and its state read again.
 // A large clade is cut into x-slices [xa, xb) so that one clade alone still fills the device; an item = (walk, x-slice). The
 // workgroups are listed by the host (clade, first item, stride): a workgroup stays with one clade, its 2N 64-bit LDS words
 // are flushed once with one 64-bit atomic per non-zero cell. Integer sums: independent of order, grid and slicing.
 // 32-bit register sums hold at most (n - |C| - 2 steps) x (slice length) tuples: the host (qs_clade_placement) keeps
 // (n - |C|) x slice x (largest count) < 2^32 by shortening the slices, and picks the instance with 64-bit sums otherwise.
-#include "qs_common.hpp"
-#include "qs_internal.hpp"
-
-#include <algorithm>
+#include "qs_taxon_walk.hpp"
 
 namespace qs {
-
-typedef uint32_t qc_u32x4 __attribute__((ext_vector_type(4)));
-typedef qc_u32x4 qc_u32x4_a2 __attribute__((aligned(2)));   // rows and pieces start at any tuple
-
-__device__ __forceinline__ unsigned long long clade_wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-    return v;
-}
-
-// sums[k] += the cells k of the CH tuples that start at src (96 bytes)
-template <typename CT, typename ACC, int CH>
-__device__ __forceinline__ void clade_add_chunk(const CT *src, ACC (&sums)[CH][3]) {
-    constexpr int NV = CH * 3 * (int)sizeof(CT) / 16;
-    const qc_u32x4_a2 *v = reinterpret_cast<const qc_u32x4_a2 *>(src);
-    uint32_t w[NV * 4];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) { const qc_u32x4 x = v[j]; w[4 * j] = x.x; w[4 * j + 1] = x.y; w[4 * j + 2] = x.z; w[4 * j + 3] = x.w; }
-#pragma unroll
-    for (int u = 0; u < CH; ++u)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int e = 3 * u + k;
-            sums[u][k] += (ACC)(sizeof(CT) == 4 ? w[e] : ((w[e >> 1] >> (16 * (e & 1))) & 0xFFFFu));
-        }
-}
 
 template <typename CT, typename ACC>
 __global__ __launch_bounds__(kPlaceWaves * kWave) void place_clade_kernel(CladeDevice cd, unsigned long long *__restrict__ dst) {
     extern __shared__ __align__(16) unsigned char clade_smem[];
     unsigned long long *acc = reinterpret_cast<unsigned long long *>(clade_smem);   // [link]
-    constexpr int kThreads = kPlaceWaves * kWave;
-    constexpr int CH = sizeof(CT) == 2 ? 16 : 8;            // tuples a lane requests at once: 96 bytes
+    constexpr int CH = WalkChunk<CT>::CH;                   // tuples a lane requests at once: 96 bytes
     constexpr int PU = 4;                                   // steps of the second stretch requested together
-    const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    const uint32_t n = cd.n, N = cd.n_nodes, cells = 2 * N;
+    const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const uint32_t n = cd.n, cells = 2 * cd.n_nodes;
     const uint32_t ci = cd.groups[2 * blockIdx.x], ks = cd.groups[2 * blockIdx.x + 1];
     const uint32_t first = ks & 0xFFFFu, share = ks >> 16;
     const uint32_t lo = cd.clades[4 * ci], hi = cd.clades[4 * ci + 1], xs = cd.clades[4 * ci + 2], n_tasks = cd.clades[4 * ci + 3];
     const uint32_t s = hi - lo, no = n - s, nsl = (s + xs - 1) / xs, n_items = n_tasks * nsl;
-    for (uint32_t i = tid; i < cells; i += kThreads) acc[i] = 0;
+    walk_zero(acc, cells);
     __syncthreads();
     const CT *table = reinterpret_cast<const CT *>(cd.table);
-    const uint32_t *__restrict__ L = cd.ref_lca;
     for (uint32_t item = first * kPlaceWaves + wave; item < n_items; item += share * kPlaceWaves) {   // uniform over the wave
         const uint32_t task = item / nsl, sl = item - task * nsl;
         const uint32_t xa = lo + sl * xs, xb = min(hi, xa + xs), cnt = xb - xa;
@@ -87,44 +55,10 @@ __global__ __launch_bounds__(kPlaceWaves * kWave) void place_clade_kernel(CladeD
         const bool live = ro_raw < no;
         const uint32_t ro = live ? ro_raw : qo + 1;   // (idle lanes read nothing of the table; qo + 1 < no keeps their tree lookups in range)
         const uint32_t r = ro < lo ? ro : ro + s;
-        // the lane's constants: Q = lca(q,r), its parent link and its children towards q and r
-        const uint32_t eQ = L[(size_t)q * n + r];
-        const uint32_t dQ = eQ >> 16;
-        const uint32_t upQ = N + cd.inner_node[eQ & 0xFFFFu];
-        const uint32_t lq = cd.child[(size_t)r * n + q], lr = cd.child[(size_t)q * n + r];
-        const uint32_t *__restrict__ lrow = L + (size_t)q * n;
-        const uint16_t *__restrict__ nrow = cd.next + (size_t)q * n;
-        const uint16_t *__restrict__ crow = cd.child + (size_t)q * n;
-        uint32_t end = 0, cp = 0, cq = 0, upP = 0;          // uniform: the run's end and its three targets
-        bool c1 = false, c13 = false, c2 = false, c23 = false, any1 = false, any13 = false;
-        ACC Ucp = 0, Ucq = 0, Uup = 0;                      // the lane's share of the run's wave-uniform targets
-        ACC Aup = 0, Alq = 0, Alr = 0;                      // the lane's own targets, over the whole walk
-        auto close_run = [&]() {
-            if (any13) { const unsigned long long t = clade_wave_sum((unsigned long long)Ucp); if (lane == 0 && t) atomicAdd(&acc[cp], t); }
-            if (any1) {
-                const unsigned long long t = clade_wave_sum((unsigned long long)Ucq), t2 = clade_wave_sum((unsigned long long)Uup);
-                if (lane == 0 && t) atomicAdd(&acc[cq], t);
-                if (lane == 0 && t2) atomicAdd(&acc[upP], t2);
-            }
-            Ucp = 0; Ucq = 0; Uup = 0;
-        };
-        // one step of the walk: the triple (p,q,r) with its three counts summed over the slice's x
-        auto step = [&](uint32_t p, ACC vp, ACC vq, ACC vr) {
-            if (p == end || p == hi) {                      // uniform: lca(p,q) or its child towards p changes here, or the walk has jumped
-                close_run();
-                const uint32_t eP = __builtin_amdgcn_readfirstlane(lrow[p]);
-                const uint32_t dP = eP >> 16;
-                upP = N + __builtin_amdgcn_readfirstlane(cd.inner_node[eP & 0xFFFFu]);
-                cp = __builtin_amdgcn_readfirstlane((uint32_t)crow[p]);
-                cq = __builtin_amdgcn_readfirstlane((uint32_t)cd.child[(size_t)p * n + q]);
-                end = __builtin_amdgcn_readfirstlane((uint32_t)nrow[p]);
-                c1 = live && dP > dQ; c2 = live && dP < dQ;
-                c13 = live && dP >= dQ; c23 = live && dP <= dQ;
-                any1 = __any(c1) != 0; any13 = __any(c13) != 0;
-            }
-            Ucp += c13 ? vp : (ACC)0; Ucq += c1 ? vq : (ACC)0; Uup += c1 ? vr : (ACC)0;
-            Aup += c2 ? vp : (ACC)0; Alq += c23 ? vq : (ACC)0; Alr += c23 ? vr : (ACC)0;
-        };
+        // one step of the walk: the triple (p,q,r) with its three counts summed over the slice's x; at p = hi the walk has jumped
+        PlaceAccount<ACC> a;
+        a.begin(cd.ref_lca, cd.inner_node, cd.child, cd.next, n, cd.n_nodes, q, r, live);
+        auto step = [&](uint32_t p, ACC vp, ACC vq, ACC vr) { a.run_break(p, p == hi, acc, lane); a.step(vp, vq, vr); };
         // first stretch [0, seg): where the interval stands behind q decides the rows and the cells (per lane: r < lo or hi <= r)
         const uint32_t seg = min(q, lo);
         if (seg) {
@@ -140,7 +74,7 @@ __global__ __launch_bounds__(kPlaceWaves * kWave) void place_clade_kernel(CladeD
                     uint64_t b2 = binom2(xa), b3 = binom3(xa);
                     const bool whole = p0 + CH <= seg;      // uniform: else the stretch's last steps, tuple by tuple
                     for (uint32_t x = xa; x < xb; ++x) {    // uniform
-                        if (whole) clade_add_chunk<CT, ACC, CH>(table + row, t);
+                        if (whole) walk_chunk<true>(table + row, true, t);
                         else {
 #pragma unroll
                             for (int u = 0; u < CH; ++u)
@@ -184,7 +118,7 @@ __global__ __launch_bounds__(kPlaceWaves * kWave) void place_clade_kernel(CladeD
                                 ACC c[CH][3];
 #pragma unroll
                                 for (int e = 0; e < CH; ++e) c[e][0] = c[e][1] = c[e][2] = 0;
-                                clade_add_chunk<CT, ACC, CH>(src[u] + 3 * (size_t)j, c);
+                                walk_chunk<true>(src[u] + 3 * (size_t)j, true, c);
 #pragma unroll
                                 for (int e = 0; e < CH; ++e) { t[u][0] += c[e][0]; t[u][1] += c[e][1]; t[u][2] += c[e][2]; }
                             }
@@ -203,19 +137,10 @@ __global__ __launch_bounds__(kPlaceWaves * kWave) void place_clade_kernel(CladeD
                     if (p0 + u < q) step(p0 + u, t[u][0], t[u][1], t[u][2]);
             }
         }
-        close_run();
-        if (live) {
-            if (Aup) atomicAdd(&acc[upQ], (unsigned long long)Aup);
-            if (Alq) atomicAdd(&acc[lq], (unsigned long long)Alq);
-            if (Alr) atomicAdd(&acc[lr], (unsigned long long)Alr);
-        }
+        a.finish(acc, lane);
     }
     __syncthreads();
-    unsigned long long *out = dst + (size_t)ci * cells;
-    for (uint32_t i = tid; i < cells; i += kThreads) {
-        const unsigned long long v = acc[i];
-        if (v) atomicAdd(&out[i], v);
-    }
+    walk_flush(acc, cells, dst + (size_t)ci * cells);
 }
 
 template <typename CT, typename ACC>

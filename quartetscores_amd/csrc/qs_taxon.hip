@@ -24,6 +24,7 @@
 // 32-bit partial sums need 64 x 3 x (largest count) < 2^32; the host picks the WIDE instance (64-bit, shuffles) otherwise.
 #include "qs_common.hpp"
 #include "qs_internal.hpp"
+#include "qs_wave_sum.hpp"
 
 #include <algorithm>
 
@@ -33,21 +34,6 @@ constexpr int kTaxonFields = 6;   // ref_resolved, concordant, discordant, eval_
 
 typedef uint32_t qt_u32x4 __attribute__((ext_vector_type(4)));
 typedef qt_u32x4 qt_u32x4_a2 __attribute__((aligned(2)));   // rows start at any tuple
-
-// sum over the wave, the same value in every lane's copy (wave-uniform): DPP inside the rows of 16, row totals by readlane
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true);   // row_half_mirror
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, true);   // row_mirror
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16) +
-           (uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
-}
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-    return v;
-}
 
 template <typename CT> __device__ __forceinline__ void taxon_load_tuple(const CT *p, uint32_t &n0, uint32_t &n1, uint32_t &n2) {
     n0 = p[0]; n1 = p[1]; n2 = p[2];

@@ -574,73 +574,68 @@ class Context:
         self.sync()
         return buf[: 5 * n_r * n_c].cpu().numpy().view(np.uint64).reshape(n_r, n_c, 5)
 
+    def _id_list(self, who, ids, limit, dtype=np.uint16):
+        """ids (None stays None) -> the contiguous array of unsigned ids the ABI takes, refused before the cast would wrap."""
+        if ids is None:
+            return None
+        wide = np.asarray(ids, dtype=np.int64).reshape(-1)
+        if ((wide < 0) | (wide >= limit)).any():
+            raise QSError(_lib.QS_ERR_ARG, who + " out of range")
+        return np.ascontiguousarray(wide, dtype=dtype)
+
+    def _query(self, ref, words, call) -> np.ndarray:
+        """Allocates `words` int64 on the device, runs call(reference struct or None, device address), waits for the result and
+        downloads it."""
+        import torch
+        buf = torch.empty(max(1, words), dtype=torch.int64, device=f"cuda:{self.device}")
+        s, keep = self._ref_struct(ref) if ref is not None else (None, None)
+        self._chk(call(None if s is None else C.byref(s), buf.data_ptr()))
+        self.sync()
+        del keep
+        return buf[:words].cpu().numpy()
+
+    def _list_query(self, fn, who, ref, taxa, width, extra=0):
+        """One of the calls over a list of taxa (None = all, in id order): `width` words per listed taxon and `extra` words behind
+        them (their device address is the call's last argument) -> (n_list, the words)."""
+        ids = self._id_list(who + ": taxon id", taxa, self.n)
+        n_list = self.n if ids is None else len(ids)
+        ptr = None if ids is None else ids.ctypes.data_as(C.c_void_p)
+
+        def call(s, p):
+            args = (self.h, s, ptr, n_list, C.c_void_p(p))
+            return fn(*args, C.c_void_p(p + n_list * width * 8)) if extra else fn(*args)
+        return n_list, self._query(ref, n_list * width + extra, call)
+
     def taxon_support(self, ref: flatten.RefTree) -> np.ndarray:
         """qs_taxon_support: per taxon (lookup id) the six sums of TAXON_FIELDS over the 4-sets of this context's table (whole
         table or shard: add the shards) that hold it -> int64 (n, 6); taxon_columns names and derives the rest. Allocates the
         device buffer, waits for the result and downloads it."""
-        import torch
-        buf = torch.empty(6 * self.n, dtype=torch.int64, device=f"cuda:{self.device}")
-        s, keep = self._ref_struct(ref)
-        self._chk(self.L.qs_taxon_support(self.h, C.byref(s), C.c_void_p(buf.data_ptr())))
-        self.sync()
-        del keep
-        return buf.cpu().numpy().reshape(self.n, 6)
+        return self._query(ref, 6 * self.n, lambda s, p: self.L.qs_taxon_support(self.h, s, C.c_void_p(p))).reshape(self.n, 6)
 
     def group_support(self, labels) -> np.ndarray:
         """qs_group_support: per hypothesis (labels (n_hyp, n_taxa) in 0..4; parse_group_spec builds them) the six words of
         GROUP_FIELDS over the 4-sets of this context's table (whole table or shard: add the shards) -> int64 (n_hyp, 6);
         group_columns derives the ratios. Needs no reference tree. Allocates the device buffer, waits for the result and
         downloads it."""
-        import torch
         a = _group_labels(self.n, labels)
-        buf = torch.empty(max(1, 6 * len(a)), dtype=torch.int64, device=f"cuda:{self.device}")
-        self._chk(self.L.qs_group_support(self.h, a.ctypes.data_as(C.c_void_p), len(a), C.c_void_p(buf.data_ptr())))
-        self.sync()
-        return buf[: 6 * len(a)].cpu().numpy().reshape(len(a), 6)
+        return self._query(None, 6 * len(a), lambda s, p: self.L.qs_group_support(self.h, a.ctypes.data_as(C.c_void_p), len(a),
+                                                                                    C.c_void_p(p))).reshape(len(a), 6)
 
     def taxon_placement(self, ref: flatten.RefTree, taxa=None) -> np.ndarray:
         """qs_taxon_placement: per listed taxon (lookup ids; None = all, in id order) the 2 * n_nodes link sums W_x of its
         quartet placement on `ref` from this context's whole table -> int64 (n_list, 2 * n_nodes); placement_scores turns them
         into the score of every edge, placement_columns into the CLI's columns. Allocates the device buffer, waits for the
         result and downloads it."""
-        import torch
-        ids = None
-        if taxa is not None:
-            wide = np.asarray(taxa, dtype=np.int64).reshape(-1)
-            if ((wide < 0) | (wide >= self.n)).any():     # (before the cast to the ABI's 16-bit ids, which would wrap)
-                raise QSError(_lib.QS_ERR_ARG, "taxon_placement: taxon id out of range")
-            ids = np.ascontiguousarray(wide, dtype=np.uint16)
-        n_list = self.n if ids is None else len(ids)
-        width = 2 * ref.n_nodes
-        buf = torch.empty(max(1, n_list * width), dtype=torch.int64, device=f"cuda:{self.device}")
-        s, keep = self._ref_struct(ref)
-        self._chk(self.L.qs_taxon_placement(self.h, C.byref(s), None if ids is None else ids.ctypes.data_as(C.c_void_p), n_list,
-                                            C.c_void_p(buf.data_ptr())))
-        self.sync()
-        del keep
-        return buf[: n_list * width].cpu().numpy().reshape(n_list, width)
+        n_list, host = self._list_query(self.L.qs_taxon_placement, "taxon_placement", ref, taxa, 2 * ref.n_nodes)
+        return host.reshape(n_list, 2 * ref.n_nodes)
 
     def taxon_pair_support(self, ref: flatten.RefTree, taxa=None) -> np.ndarray:
         """qs_taxon_pair_support: per listed taxon x (lookup ids; None = all, in id order) and every taxon j the eight words of
         TAXON_PAIR_FIELDS over the 4-sets of this context's whole table that hold both, split by what `ref` shows for the 4-set
         -> int64 (n_list, n, 8); taxon_pair_columns turns them into the CLI's columns. Allocates the device buffer, waits for the
         result and downloads it."""
-        import torch
-        ids = None
-        if taxa is not None:
-            wide = np.asarray(taxa, dtype=np.int64).reshape(-1)
-            if ((wide < 0) | (wide >= self.n)).any():     # (before the cast to the ABI's 16-bit ids, which would wrap)
-                raise QSError(_lib.QS_ERR_ARG, "taxon_pair_support: taxon id out of range")
-            ids = np.ascontiguousarray(wide, dtype=np.uint16)
-        n_list = self.n if ids is None else len(ids)
-        width = 8 * self.n
-        buf = torch.empty(max(1, n_list * width), dtype=torch.int64, device=f"cuda:{self.device}")
-        s, keep = self._ref_struct(ref)
-        self._chk(self.L.qs_taxon_pair_support(self.h, C.byref(s), None if ids is None else ids.ctypes.data_as(C.c_void_p), n_list,
-                                               C.c_void_p(buf.data_ptr())))
-        self.sync()
-        del keep
-        return buf[: n_list * width].cpu().numpy().reshape(n_list, self.n, 8)
+        n_list, host = self._list_query(self.L.qs_taxon_pair_support, "taxon_pair_support", ref, taxa, 8 * self.n)
+        return host.reshape(n_list, self.n, 8)
 
     def branch_taxon_support(self, ref: flatten.RefTree, taxa=None):
         """qs_branch_taxon_support: per listed taxon x (lookup ids; None = all, in id order) and node v of `ref` the four words of
@@ -648,22 +643,8 @@ class Context:
         -> (rows int64 (n_list, n_nodes, 4), totals int64 (n_nodes, 4)); QP-IC of the internode without x is log_score of
         (totals - rows[x])[1:4], and drop_one_columns turns both into the CLI's columns. Allocates the device buffers, waits for the
         result and downloads it."""
-        import torch
-        ids = None
-        if taxa is not None:
-            wide = np.asarray(taxa, dtype=np.int64).reshape(-1)
-            if ((wide < 0) | (wide >= self.n)).any():     # (before the cast to the ABI's 16-bit ids, which would wrap)
-                raise QSError(_lib.QS_ERR_ARG, "branch_taxon_support: taxon id out of range")
-            ids = np.ascontiguousarray(wide, dtype=np.uint16)
-        n_list = self.n if ids is None else len(ids)
         width = 4 * ref.n_nodes
-        buf = torch.empty(max(1, (n_list + 1) * width), dtype=torch.int64, device=f"cuda:{self.device}")
-        s, keep = self._ref_struct(ref)
-        self._chk(self.L.qs_branch_taxon_support(self.h, C.byref(s), None if ids is None else ids.ctypes.data_as(C.c_void_p), n_list,
-                                                 C.c_void_p(buf.data_ptr()), C.c_void_p(buf.data_ptr() + n_list * width * 8)))
-        self.sync()
-        del keep
-        host = buf[: (n_list + 1) * width].cpu().numpy()
+        n_list, host = self._list_query(self.L.qs_branch_taxon_support, "branch_taxon_support", ref, taxa, width, extra=width)
         return host[: n_list * width].reshape(n_list, ref.n_nodes, 4), host[n_list * width:].reshape(ref.n_nodes, 4)
 
     def clade_placement(self, ref: flatten.RefTree, nodes=None) -> np.ndarray:
@@ -672,19 +653,10 @@ class Context:
         (n_list, 2 * n_nodes); placement_scores turns a row into the score of every edge outside the clade (the entries of the
         nodes strictly inside it are not positions, the node's own entry is the current position's score),
         clade_placement_columns into the CLI's columns. Allocates the device buffer, waits for the result and downloads it."""
-        import torch
-        wide = np.asarray(eligible_clades(ref) if nodes is None else nodes, dtype=np.int64).reshape(-1)
-        if ((wide < 0) | (wide >= ref.n_nodes)).any():    # (before the cast to the ABI's unsigned indices, which would wrap)
-            raise QSError(_lib.QS_ERR_ARG, "clade_placement: node index out of range")
-        ids = np.ascontiguousarray(wide, dtype=np.uint32)
+        ids = self._id_list("clade_placement: node index", eligible_clades(ref) if nodes is None else nodes, ref.n_nodes, np.uint32)
         width = 2 * ref.n_nodes
-        buf = torch.empty(max(1, len(ids) * width), dtype=torch.int64, device=f"cuda:{self.device}")
-        s, keep = self._ref_struct(ref)
-        self._chk(self.L.qs_clade_placement(self.h, C.byref(s), ids.ctypes.data_as(C.c_void_p) if len(ids) else None, len(ids),
-                                            C.c_void_p(buf.data_ptr())))
-        self.sync()
-        del keep
-        return buf[: len(ids) * width].cpu().numpy().reshape(len(ids), width)
+        return self._query(ref, len(ids) * width, lambda s, p: self.L.qs_clade_placement(
+            self.h, s, ids.ctypes.data_as(C.c_void_p) if len(ids) else None, len(ids), C.c_void_p(p))).reshape(len(ids), width)
 
     def table_clear(self):
         self._chk(self.L.qs_table_clear(self.h))

@@ -42,7 +42,7 @@ def counted(eng, ref, trees, bits):
 
 @pytest.mark.parametrize("kind", ["binary", "multifurcating", "rooted"])
 @pytest.mark.parametrize("bits", [16, 32])
-@pytest.mark.parametrize("n", [4, 5, 7, 9, 17, 33, 65, 130])
+@pytest.mark.parametrize("n", [4, 5, 7, 9, 17, 33, 65, 66, 130])
 def test_equals_model_of_the_downloaded_table(eng, n, bits, kind):
     ref = reference(n, kind, 1000 + n)
     ctx = counted(eng, ref, mixed_trees(n, 300 + n), bits)
