@@ -23,6 +23,8 @@
  *                                 line per quartet, which a user would reduce per taxon on the host)
  *   qs_taxon_pair_support         replaces nothing in the reference (it has no output per pair of taxa)
  *   qs_branch_taxon_support       replaces nothing in the reference (it never asks what a branch's QP-IC would be without one taxon)
+ *   qs_tree_branch_support /      replace nothing in the reference (it sums over the trees before it looks at a branch, and never
+ *   qs_branch_resample            resamples them)
  *   qs_group_check /              replace nothing in the reference; the nearest is the metaquartet sum of processNodePair
  *   qs_group_support              (QuartetScoreComputer.hpp:379-472), which knows only the four subtrees beside a node pair of the tree
  *   qs_taxon_placement /          replace nothing in the reference (it never asks where the evaluation trees would put a taxon; the
@@ -467,6 +469,35 @@ int qs_taxon_pair_support(qs_ctx *ctx, const qs_ref_tree *ref, const uint16_t *t
  * at 2259 taxa). Asynchronous on the context's stream. The reference has no such output: this replaces nothing there. */
 int qs_branch_taxon_support(qs_ctx *ctx, const qs_ref_tree *ref, const uint16_t *taxa, uint32_t n_list, int64_t *rows_device,
                             int64_t *totals_device);
+
+/* Per-tree quartet support of every branch: which evaluation trees contradict this internode. For tree t of the uploaded batch `b`
+ * (uploaded with its node ranges) with taxon set P_t, and node v of the reference tree, four exact words for the internode e between v
+ * and its parent, over the 4-sets around e (as defined for qs_branch_taxon_support) whose four taxa all lie in P_t:
+ *   k = 0 present  their number        k = 1..3 q1, q2, q3  how many of them t shows as the reference's topology and as the two others
+ * with (q1, q2, q3) in the order of qs_branch_taxon_support's totals, i.e. the order qs_score uses without flags. dst_device
+ * (caller-owned device memory, 8-byte aligned, [n_trees of b][n_nodes][4] words) is OVERWRITTEN; the node indexing is that of
+ * qs_branch_taxon_support's rows: the entries of leaves, of the root and of edges with a leaf at either end are 0, and the internode
+ * through a degree-2 root stands identically at both its inner children. Summed over the trees of a counted batch, words 1..3 are the
+ * totals qs_branch_taxon_support reads from the table; word 0 of a tree with all taxa is the totals' word 0. A tree with fewer than
+ * four taxa gives zeros. No table is needed and none is touched: the call changes neither the table nor trees-counted nor a pending
+ * score log. No 4-set is enumerated: closed forms over the pairs (internode, node of t) from interval counts in LDS bitmaps
+ * (DESIGN.md 18); exact integers, independent of grid, batching, rooting and repetition. The reference tree is checked as by
+ * qs_tree_agreement and cached per context.
+ * Errors: QS_ERR_ARG = NULL argument, misaligned dst_device, malformed reference, n_taxa differs from the context's, ids not in
+ * depth-first order; QS_ERR_STATE = the batch was uploaded without node ranges; QS_ERR_UNSUPPORTED = a table-shard context.
+ * Asynchronous on the context's stream. The reference sums over the trees before it looks at a branch: this replaces nothing there. */
+int qs_tree_branch_support(qs_ctx *ctx, const qs_ref_tree *ref, const qs_device_batch *b, int64_t *dst_device);
+
+/* Weighted sums of such rows over the trees, for a bootstrap over the evaluation trees: QP-IC of an internode is log_score of three
+ * sums over trees, so a replicate is a reweighting of the per-tree words, not a recount.
+ *   dst_device[rep][node][k] += sum over t of weights_host[rep][t] x rows_device[t][node][k],   k = 0..3
+ * rows_device = [n_trees][n_nodes][4] words as qs_tree_branch_support writes them, weights_host = [n_rep][n_trees] (lent for the call),
+ * dst_device = [n_rep][n_nodes][4] words, 8-byte aligned, ADDED to: the caller zeroes it once and streams batch after batch with the
+ * matching slice of every replicate's weights. The rows are read once per 16 replicates. Exact integers.
+ * Errors: QS_ERR_ARG = NULL argument, misaligned rows_device / dst_device; QS_ERR_OVERFLOW = (sum of a replicate's weights in this
+ * call) x C(n_taxa,4) can exceed 63 bits. Asynchronous on the context's stream. */
+int qs_branch_resample(qs_ctx *ctx, const int64_t *rows_device, uint32_t n_trees, uint32_t n_nodes, const uint32_t *weights_host,
+                       uint32_t n_rep, int64_t *dst_device);
 
 /* Quartet support of user-defined taxon groups from the count table: how often do the evaluation trees show each resolution around a
  * branch the caller names -- whether or not any reference tree has it. Replaces nothing in the reference; the nearest is the metaquartet

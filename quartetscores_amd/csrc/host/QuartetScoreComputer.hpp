@@ -140,7 +140,7 @@ private:
         return opt.ingest_threads ? opt.ingest_threads : std::max(1u, std::thread::hardware_concurrency());
     }
     static bool wants_ranges(const DeviceOptions &opt) { // the gather kernels do not read them; the per-tree and pairwise agreement do
-        return (opt.algo & 0xFFu) == QS_ALGO_SCATTER || !opt.per_tree.empty() || !opt.tree_distances.empty();
+        return (opt.algo & 0xFFu) == QS_ALGO_SCATTER || !opt.per_tree.empty() || !opt.tree_distances.empty() || opt.tree_branches;
     }
     // batch boundaries: [0, first_batch_trees), then steps of batch_trees
     static size_t batch_end(size_t i0, size_t n, const DeviceOptions &opt) {

@@ -28,9 +28,12 @@
 #include "QuartetScoreComputer.hpp"
 #include "multi_gpu.hpp"
 #include "table_shards.hpp"
+#include "synth.hpp"
 #include "tree_distances.hpp"
 
+#include <algorithm>
 #include <cerrno>
+#include <cmath>
 #include <map>
 #include <set>
 #include <sstream>
@@ -89,6 +92,11 @@ struct Args {
     std::string drop_one;         // --drop-one FILE: QP-IC of every internode of -r without each single taxon, from the count table (TSV)
     std::string drop_one_only;    // --drop-one-only NAMES: a file of the taxon labels to drop (default: all)
     std::vector<uint16_t> drop_ids;    // the lookup ids whose rows are computed, ascending (check_taxon_list_output)
+    std::string branch_trees;     // --branch-trees FILE: per evaluation tree the quartet support of every internode of -r (TSV)
+    std::string bootstrap;        // --bootstrap FILE: QP-IC of every internode of -r under a bootstrap over the evaluation trees (TSV)
+    uint32_t bootstrap_reps = 100;   // --bootstrap-reps B
+    uint64_t bootstrap_seed = 1;     // --bootstrap-seed S
+    bool bootstrap_reps_given = false, bootstrap_seed_given = false;
     std::string place_clades;      // --place-clades FILE: quartet placement of the clades of -r from the count table (TSV)
     std::string place_clades_only; // --place-clades-only SPEC: a file of the clades to place, one per line (default: every eligible inner clade)
     std::vector<uint32_t> place_nodes; // the nodes to place, in output order (check_place_clades)
@@ -229,7 +237,25 @@ void usage(std::ostream &os) {
           "                  EQP-IC are minima and have no such decomposition. One gather over the table per taxon and one read of it;\n"
           "                  one GPU with the whole table (not with --gpus / --table-shards); works with --load-table and beside every\n"
           "                  other output\n"
-          "   --drop-one-only NAMES  with --drop-one: write only the taxa listed in NAMES (one label per line, as for --place-only)\n";
+          "   --drop-one-only NAMES  with --drop-one: write only the taxa listed in NAMES (one label per line, as for --place-only)\n"
+          "   --branch-trees F  write, per evaluation tree and internal branch of the -r tree, how the tree resolves the 4-sets around that\n"
+          "                  branch to F (TSV, after a header one line per tree in -e order and branch in node order: tree node lo hi present\n"
+          "                  q1 q2 q3 concordance). [lo, hi) = the lookup ids below the branch; present = the 4-sets around the branch whose\n"
+          "                  four taxa the tree holds; q1 = how many of them it shows as the -r tree does, q2 and q3 the two other\n"
+          "                  resolutions, in the order of --drop-one's sums (the q1 q2 q3 of all trees add up to them); concordance =\n"
+          "                  q1 / (q1 + q2 + q3), nan where the tree resolves none. Lines with present = 0 are left out; a rooted -r\n"
+          "                  tree's branch through the root is written once. Which gene trees contradict this branch: computed on the\n"
+          "                  device behind the counting from the trees themselves; one GPU that counts (not with --gpus / --table-shards /\n"
+          "                  --load-table); works beside every other output\n"
+          "   --bootstrap F  write, per internal branch of the -r tree, its QP-IC under a bootstrap over the evaluation trees to F (TSV,\n"
+          "                  one line per branch in node order after a header: node lo hi qpic mean sd lo95 hi95 reps). qpic = the\n"
+          "                  branch's QP-IC from exact sums (--drop-one's qpic); a replicate draws as many trees as there are, with\n"
+          "                  replacement, and its QP-IC is that of the redrawn trees' sums: a reweighting of the per-tree sums of\n"
+          "                  --branch-trees, not a recount. mean and sd (of the population) are over the replicates, lo95 / hi95 their\n"
+          "                  2.5 % / 97.5 % points (the sorted values at floor(0.025 (B-1)) and ceil(0.975 (B-1))). One GPU that counts\n"
+          "                  (not with --gpus / --table-shards / --load-table); works with --branch-trees and beside every other output\n"
+          "   --bootstrap-reps B  with --bootstrap: the number of replicates (default 100)\n"
+          "   --bootstrap-seed S  with --bootstrap: the seed of the resampling (default 1); the same seed gives the same file\n";
 }
 
 // returns 0 ok, 1 error (message printed like the reference prints TCLAP::ArgException), 2 exit quietly
@@ -308,6 +334,10 @@ int parse(int argc, char **argv, Args &a) {
         else if (f == "--taxon-pairs-only") { if (!(v = need(i, "--taxon-pairs-only"))) return 1; a.taxon_pairs_only = v; }
         else if (f == "--drop-one") { if (!(v = need(i, "--drop-one"))) return 1; a.drop_one = v; }
         else if (f == "--drop-one-only") { if (!(v = need(i, "--drop-one-only"))) return 1; a.drop_one_only = v; }
+        else if (f == "--branch-trees") { if (!(v = need(i, "--branch-trees"))) return 1; a.branch_trees = v; }
+        else if (f == "--bootstrap") { if (!(v = need(i, "--bootstrap"))) return 1; a.bootstrap = v; }
+        else if (f == "--bootstrap-reps") { if (!(v = need(i, "--bootstrap-reps")) || !number(v, "--bootstrap-reps", num)) return 1; a.bootstrap_reps = (uint32_t)std::min<unsigned long>(num, 0xFFFFFFFFul); a.bootstrap_reps_given = true; }
+        else if (f == "--bootstrap-seed") { if (!(v = need(i, "--bootstrap-seed")) || !number(v, "--bootstrap-seed", num)) return 1; a.bootstrap_seed = num; a.bootstrap_seed_given = true; }
         else if (f == "--place-only") { if (!(v = need(i, "--place-only"))) return 1; a.place_only = v; }
         else if (f == "--place-clades") { if (!(v = need(i, "--place-clades"))) return 1; a.place_clades = v; }
         else if (f == "--place-clades-only") { if (!(v = need(i, "--place-clades-only"))) return 1; a.place_clades_only = v; }
@@ -388,7 +418,8 @@ std::vector<std::pair<std::string, std::string>> output_files(const Args &a) {
     std::vector<std::pair<std::string, std::string>> files{
         {"-o", a.out}, {"-q", a.raw}, {"--qic-binary", a.raw_bin}, {"--save-table", a.dev.save_table}, {"--per-tree", a.per_tree},
         {"--tree-distances", a.tree_distances}, {"--per-taxon", a.per_taxon}, {"--place-taxa", a.place_taxa}, {"--place-clades", a.place_clades},
-        {"--test-groups", a.test_groups}, {"--taxon-pairs", a.taxon_pairs}, {"--drop-one", a.drop_one}};
+        {"--test-groups", a.test_groups}, {"--taxon-pairs", a.taxon_pairs}, {"--drop-one", a.drop_one}, {"--branch-trees", a.branch_trees},
+        {"--bootstrap", a.bootstrap}};
     for (const AlsoRef &x : a.also) files.emplace_back("--also-ref", x.out);
     for (const WithoutTaxa &x : a.without) files.emplace_back("--without-taxa", x.out);
     return files;
@@ -712,6 +743,36 @@ void write_taxon_pairs(qs_ctx *ctx, const RefFlat &ref, int device, const std::s
     if (!f) throw std::runtime_error("cannot write " + path);
 }
 
+// The internodes of the -r tree as the per-branch outputs list them (tests/branch_taxon_model.py): the id interval below every node, its
+// children in id order, and the edges (child node, other end) in node order -- the internode through a degree-2 root once, at the child
+// that holds lookup id 0
+struct Internodes {
+    struct Edge { size_t v, w; bool through_root; };
+    std::vector<size_t> lo, hi;
+    std::vector<std::vector<size_t>> kids;
+    std::vector<Edge> edges;
+    explicit Internodes(const RefFlat &ref) {
+        const size_t n = ref.names.size(), N = ref.parent.size();
+        lo.assign(N, n); hi.assign(N, 0); kids.resize(N);
+        for (size_t i = 0; i < n; ++i)
+            for (int64_t v = ref.leaf_node[i]; v >= 0; v = ref.parent[(size_t)v]) { lo[(size_t)v] = std::min(lo[(size_t)v], i); hi[(size_t)v] = std::max(hi[(size_t)v], i + 1); }
+        size_t root = 0;
+        for (size_t v = 0; v < N; ++v) {
+            if (ref.parent[v] >= 0) kids[(size_t)ref.parent[v]].push_back(v);
+            else root = v;
+        }
+        for (auto &k : kids) std::sort(k.begin(), k.end(), [&](size_t x, size_t y) { return lo[x] < lo[y]; });
+        for (size_t v = 0; v < N; ++v) {
+            if (v == root || kids[v].empty()) continue;
+            const size_t u = (size_t)ref.parent[v];
+            if (u == root && kids[u].size() == 2) {
+                const size_t o = kids[u][0] == v ? kids[u][1] : kids[u][0];
+                if (!kids[o].empty() && v == kids[u][0]) edges.push_back({v, o, true});
+            } else edges.push_back({v, u, false});
+        }
+    }
+};
+
 // --drop-one: one qs_branch_taxon_support over the counted (or loaded) table for the listed taxa, their rows of n_nodes x 4 words and
 // the totals downloaded, one TSV line per taxon and internode (tests/branch_taxon_model.py defines the columns; the internode through a
 // degree-2 root once, at the child that holds lookup id 0)
@@ -725,27 +786,10 @@ void write_drop_one(qs_ctx *ctx, const RefFlat &ref, int device, const std::stri
     std::vector<int64_t> w((L + 1) * N * 4);
     if (hipMemcpy(w.data(), dev.get(), w.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("--drop-one: download failed");
     const int64_t *totals = w.data() + L * N * 4;
-    // the id interval below every node, its children in id order, the internodes (child node, other end)
-    std::vector<size_t> lo(N, n), hi(N, 0);
-    for (size_t i = 0; i < n; ++i)
-        for (int64_t v = ref.leaf_node[i]; v >= 0; v = ref.parent[(size_t)v]) { lo[(size_t)v] = std::min(lo[(size_t)v], i); hi[(size_t)v] = std::max(hi[(size_t)v], i + 1); }
-    std::vector<std::vector<size_t>> kids(N);
-    size_t root = 0;
-    for (size_t v = 0; v < N; ++v) {
-        if (ref.parent[v] >= 0) kids[(size_t)ref.parent[v]].push_back(v);
-        else root = v;
-    }
-    for (auto &k : kids) std::sort(k.begin(), k.end(), [&](size_t x, size_t y) { return lo[x] < lo[y]; });
-    struct Edge { size_t v, w; bool through_root; };
-    std::vector<Edge> edges;
-    for (size_t v = 0; v < N; ++v) {
-        if (v == root || kids[v].empty()) continue;
-        const size_t u = (size_t)ref.parent[v];
-        if (u == root && kids[u].size() == 2) {
-            const size_t o = kids[u][0] == v ? kids[u][1] : kids[u][0];
-            if (!kids[o].empty() && v == kids[u][0]) edges.push_back({v, o, true});
-        } else edges.push_back({v, u, false});
-    }
+    const Internodes in(ref);
+    const std::vector<size_t> &lo = in.lo, &hi = in.hi;
+    const std::vector<std::vector<size_t>> &kids = in.kids;
+    const std::vector<Internodes::Edge> &edges = in.edges;
     // taxa in x's link at the node `end`, whose link towards `away` (N = none) is the edge itself
     auto link_size = [&](size_t end, size_t x, size_t away) {
         for (size_t k : kids[end])
@@ -758,7 +802,7 @@ void write_drop_one(qs_ctx *ctx, const RefFlat &ref, int device, const std::stri
     char qpic[64], without[64], delta[64];
     for (size_t k = 0; k < L; ++k) {
         const size_t x = ids[k];
-        for (const Edge &e : edges) {
+        for (const Internodes::Edge &e : edges) {
             const int64_t *r = &w[(k * N + e.v) * 4], *t = totals + e.v * 4;
             const bool below = lo[e.v] <= x && x < hi[e.v];
             const size_t group = below ? link_size(e.v, x, N) : e.through_root ? link_size(e.w, x, N) : link_size(e.w, x, e.v);
@@ -778,6 +822,117 @@ void write_drop_one(qs_ctx *ctx, const RefFlat &ref, int device, const std::stri
     }
     if (!f) throw std::runtime_error("cannot write " + path);
 }
+
+// --branch-trees / --bootstrap: refused like --per-tree, before the device is touched
+void check_tree_branches(const Args &a) {
+    if (a.bootstrap.empty() && (a.bootstrap_reps_given || a.bootstrap_seed_given)) throw std::runtime_error("--bootstrap-reps / --bootstrap-seed need --bootstrap FILE");
+    for (const char *flag : {"--branch-trees", "--bootstrap"}) {
+        if (output_file(a, flag).empty()) continue;
+        if (a.gpus > 0 || a.table_shards >= 0 || !a.dev.load_table.empty())
+            throw std::runtime_error(std::string(flag) + " needs the evaluation trees counted on one GPU: omit --gpus / --table-shards / --load-table");
+        check_output_file(a, flag);
+    }
+    if (!a.bootstrap.empty() && a.bootstrap_reps == 0) throw std::runtime_error("--bootstrap-reps must be at least 1");
+}
+
+// --branch-trees / --bootstrap: qs_tree_branch_support behind every batch's count into one device buffer of (trees of the batch) x n_nodes
+// x 4 words, shared by the two outputs. --branch-trees downloads every batch and writes its lines as it comes; --bootstrap adds the batch
+// to the sums of every replicate with its slice of the replicates' weights (qs_branch_resample; row 0 of the weights is all ones: the
+// unweighted sums behind the qpic column) and downloads those once behind the final qs_sync. No buffer grows with m on the device.
+struct TreeBranches {
+    size_t m = 0;
+    int device = 0;
+    std::string lines_path, boot_path;
+    uint32_t reps = 0;
+    uint64_t seed = 1;
+    qs::DevBuf<int64_t> rows, sums;
+    std::vector<uint32_t> weights, slice;   // [1 + reps][m]; the columns of one batch
+    std::vector<int64_t> host, totals;
+    std::ofstream lines;
+    std::unique_ptr<Internodes> in;
+    void hook(DeviceOptions &opt, const RefFlat &ref) {
+        opt.tree_branches = true;
+        in.reset(new Internodes(ref));
+        const size_t N = ref.parent.size();
+        if (!lines_path.empty()) {
+            lines.open(lines_path);
+            if (!lines) throw std::runtime_error("cannot write " + lines_path);
+            lines << "tree\tnode\tlo\thi\tpresent\tq1\tq2\tq3\tconcordance\n";
+        }
+        if (!boot_path.empty()) {
+            // replicate r draws m tree indices; its weights are their multiplicities
+            weights.assign((size_t)(1 + reps) * m, 0);
+            std::fill(weights.begin(), weights.begin() + (std::ptrdiff_t)m, 1u);
+            for (uint32_t r = 0; r < reps; ++r) {
+                Rng rng(seed, r);
+                for (size_t i = 0; i < m; ++i) weights[(size_t)(1 + r) * m + rng.below((uint32_t)m)]++;
+            }
+        }
+        add_after_count(opt, [this, &ref, N](qs_ctx *ctx, const qs_device_batch *db, size_t i0, const BatchFlat &b) {
+            const size_t k = b.n_trees, words = k * N * 4;
+            if (hipSetDevice(device) != hipSuccess || rows.reserve(std::max<size_t>(1, words) * 8, nullptr) != hipSuccess)
+                throw std::runtime_error("--branch-trees / --bootstrap: Insufficient memory!");
+            const qs_ref_tree rt = ref_view(ref);
+            if (qs_tree_branch_support(ctx, &rt, db, rows.get()) != QS_OK) throw std::runtime_error(qs_last_error(ctx));
+            if (!boot_path.empty()) {
+                const size_t sum_words = (size_t)(1 + reps) * N * 4;
+                if (!sums) {
+                    if (sums.reserve(std::max<size_t>(1, sum_words) * 8, nullptr) != hipSuccess || hipMemset(sums.get(), 0, sum_words * 8) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+                        throw std::runtime_error("--bootstrap: Insufficient memory!");
+                }
+                slice.resize((size_t)(1 + reps) * k);
+                for (size_t r = 0; r <= reps; ++r) std::copy_n(weights.begin() + (std::ptrdiff_t)(r * m + i0), k, slice.begin() + (std::ptrdiff_t)(r * k));
+                if (qs_branch_resample(ctx, rows.get(), (uint32_t)k, (uint32_t)N, slice.data(), 1 + reps, sums.get()) != QS_OK) throw std::runtime_error(qs_last_error(ctx));
+            }
+            if (lines_path.empty()) return;   // (the next batch's rows come behind this one's sums on the context's stream)
+            // the lines are written as the batch comes: the device is waited for here, which this output pays for and no other
+            if (qs_sync(ctx) != QS_OK) throw std::runtime_error(qs_last_error(ctx));
+            host.resize(words);
+            if (words && hipMemcpy(host.data(), rows.get(), words * 8, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("--branch-trees: download failed");
+            char conc[64];
+            for (size_t t = 0; t < k; ++t)
+                for (const Internodes::Edge &e : in->edges) {
+                    const int64_t *w = &host[(t * N + e.v) * 4];
+                    if (w[0] == 0) continue;
+                    const int64_t s = w[1] + w[2] + w[3];
+                    if (s) std::snprintf(conc, sizeof conc, "%.6f", (double)w[1] / (double)s);
+                    else std::snprintf(conc, sizeof conc, "nan");
+                    lines << (i0 + t) << '\t' << e.v << '\t' << in->lo[e.v] << '\t' << in->hi[e.v] << '\t' << w[0] << '\t' << w[1] << '\t' << w[2] << '\t' << w[3] << '\t' << conc << '\n';
+                }
+            if (!lines) throw std::runtime_error("cannot write " + lines_path);
+        });
+        add_after_sync(opt, [this, N](qs_ctx *) {
+            if (boot_path.empty()) return;
+            totals.assign((size_t)(1 + reps) * N * 4, 0);
+            if (sums && hipMemcpy(totals.data(), sums.get(), totals.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("--bootstrap: download failed");
+        });
+    }
+    void write() {
+        if (!lines_path.empty()) {
+            lines.close();
+            if (!lines) throw std::runtime_error("cannot write " + lines_path);
+        }
+        if (boot_path.empty()) return;
+        const size_t N = in->lo.size(), B = reps;
+        std::ofstream f(boot_path);
+        if (!f) throw std::runtime_error("cannot write " + boot_path);
+        f << "node\tlo\thi\tqpic\tmean\tsd\tlo95\thi95\treps\n";
+        std::vector<double> vals(B);
+        char text[5][64];
+        for (const Internodes::Edge &e : in->edges) {
+            auto score = [&](size_t r) { const int64_t *w = &totals[(r * N + e.v) * 4]; return raw_log_score((size_t)w[1], (size_t)w[2], (size_t)w[3]); };
+            double total = 0.0, dev2 = 0.0;   // plain double sums in replicate order
+            for (size_t r = 0; r < B; ++r) { vals[r] = score(1 + r); total += vals[r]; }
+            const double mean = total / (double)B;
+            for (size_t r = 0; r < B; ++r) dev2 += (vals[r] - mean) * (vals[r] - mean);
+            std::sort(vals.begin(), vals.end());
+            const double cols[5] = {score(0), mean, std::sqrt(dev2 / (double)B), vals[(size_t)std::floor(0.025 * (double)(B - 1))], vals[(size_t)std::ceil(0.975 * (double)(B - 1))]};
+            for (int i = 0; i < 5; ++i) std::snprintf(text[i], sizeof text[i], "%.6f", cols[i]);
+            f << e.v << '\t' << in->lo[e.v] << '\t' << in->hi[e.v] << '\t' << text[0] << '\t' << text[1] << '\t' << text[2] << '\t' << text[3] << '\t' << text[4] << '\t' << B << '\n';
+        }
+        if (!f) throw std::runtime_error("cannot write " + boot_path);
+    }
+};
 
 // --place-clades: refused before the device is touched where the whole table is not on one GPU, where FILE exists or is another output,
 // and where a line of --place-clades-only names a label the -r tree lacks, the whole tree, a clade with fewer than three taxa outside it
@@ -1131,6 +1286,18 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
         dev.per_tree = a.per_tree;
         per_tree.hook(dev, per_tree_ref);
     }
+    TreeBranches tree_branches;
+    const bool want_branches = !a.branch_trees.empty() || !a.bootstrap.empty();
+    const RefFlat tree_branches_ref = want_branches ? flatten_reference(referenceTree) : RefFlat();
+    if (want_branches) {
+        tree_branches.m = m;
+        tree_branches.device = a.dev.device;
+        tree_branches.lines_path = a.branch_trees;
+        tree_branches.boot_path = a.bootstrap;
+        tree_branches.reps = a.bootstrap_reps;
+        tree_branches.seed = a.bootstrap_seed;
+        tree_branches.hook(dev, tree_branches_ref);
+    }
     TreeDistances tree_distances;
     if (!a.tree_distances.empty()) {
         dev.tree_distances = a.tree_distances;
@@ -1147,6 +1314,7 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
     if (!a.raw_bin.empty()) qsc.printRawQICBinary(a.raw_bin);
     if (!a.per_tree.empty()) per_tree.write(a.per_tree);
     if (!a.tree_distances.empty()) tree_distances.write(qsc.context(), a.dev.device, a.tree_distances);
+    if (want_branches) tree_branches.write();
     if (!a.per_taxon.empty()) write_per_taxon(qsc.context(), qsc.reference(), a.dev.device, a.per_taxon);
     if (!a.place_taxa.empty()) write_place_taxa(qsc.context(), qsc.reference(), a.dev.device, a.place_taxa, a.place_ids);
     if (!a.place_clades.empty()) write_place_clades(qsc.context(), qsc.reference(), a.dev.device, a.place_clades, a.place_nodes);
@@ -1181,6 +1349,7 @@ int main(int argc, char *argv[]) {
         check_without_taxa(a);
         check_per_tree(a);
         check_tree_distances(a);
+        check_tree_branches(a);
         check_per_taxon(a);
         a.place_ids = check_taxon_list_output(a, "--place-taxa", "--place-only", a.place_only);
         check_place_clades(a);

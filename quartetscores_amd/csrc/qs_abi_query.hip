@@ -1,7 +1,8 @@
 // qs_abi_query.hip -- what reads a finished table and is not the score: per-taxon, per-pair and per-branch-and-taxon support, taxon and clade placement, per-tree
-// agreement (against a reference tree), the agreement of the evaluation trees with each other and the support of taxon groups (against
-// none). Host code only; the kernels are in qs_taxon.hip, qs_taxon_pairs.hip, qs_branch_taxa.hip, qs_place.hip, qs_place_clade.hip, qs_agree.hip, qs_agree_pairs.hip and
-// qs_groups.hip.
+// agreement and per-tree support of every branch with its resampling (against a reference tree; these two read the trees, not a table),
+// the agreement of the evaluation trees with each other and the support of taxon groups (against none). Host code only; the kernels are
+// in qs_taxon.hip, qs_taxon_pairs.hip, qs_branch_taxa.hip, qs_place.hip, qs_place_clade.hip, qs_agree.hip, qs_tree_branch.hip,
+// qs_agree_pairs.hip and qs_groups.hip.
 #include "qs_ctx.hpp"
 #include "qs_plan.hpp"
 
@@ -575,5 +576,106 @@ extern "C" int qs_tree_pair_agreement(qs_ctx *c, const qs_device_batch *rows, ui
     if (dc.ready && rows != cols) QS_HIP(c, hipStreamWaitEvent(c->stream, dc.ready, 0));
     QS_HIP(c, launch_tree_pairs(c->stream, dr, r0, r1, dc, c0, c1, (flags & QS_PAIRS_UPPER) != 0, c->n, c->pair_pos.get(),
                                 reinterpret_cast<unsigned long long *>(dst_device)));
+    return QS_OK;   // asynchronous on the context's stream
+}
+
+// Per tree of a batch the quartet support of every internode of the reference tree (qs_tree_branch.hip). The internodes are
+// qs_branch_taxon_support's: both ends inner nodes, the edge through a degree-2 root once, standing at both its inner children. The
+// reference sums over the trees before it looks at a branch: this replaces nothing there.
+static int tree_branch_ref_upload(qs_ctx *c, const qs_ref_tree *ref) {
+    if (!ref || !ref->parent || !ref->leaf_node) return fail(c, QS_ERR_ARG, "qs_tree_branch_support: NULL reference arrays");
+    if (ref->n_taxa != c->n) return fail(c, QS_ERR_ARG, "qs_tree_branch_support: the reference tree's n_taxa differs from the context");
+    const uint32_t N = ref->n_nodes, n = ref->n_taxa, none = 0xFFFFFFFFu;
+    if (c->tbranch_edges && c->tbranch_parent.size() == N && c->tbranch_leaf_node.size() == n &&
+        memcmp(c->tbranch_parent.data(), ref->parent, (size_t)N * 4) == 0 && memcmp(c->tbranch_leaf_node.data(), ref->leaf_node, (size_t)n * 4) == 0)
+        return QS_OK;
+    RefHost R;
+    if (int rc = build_ref_shape(c, ref, R)) return rc;
+    std::vector<std::vector<uint32_t>> kids(N);
+    for (uint32_t v = 0; v < N; ++v)
+        if (R.parent[v] >= 0) kids[(uint32_t)R.parent[v]].push_back(v);
+    std::vector<uint32_t> boff(N, 0), edges;
+    std::vector<uint16_t> bnd;
+    for (uint32_t v = 0; v < N; ++v) {
+        if (kids[v].empty()) continue;
+        std::sort(kids[v].begin(), kids[v].end(), [&](uint32_t x, uint32_t y) { return R.leaf_lo[x] < R.leaf_lo[y]; });
+        boff[v] = (uint32_t)bnd.size();
+        for (uint32_t k : kids[v]) bnd.push_back((uint16_t)R.leaf_lo[k]);
+        bnd.push_back((uint16_t)(R.leaf_lo[v] + R.leaf_cnt[v]));
+    }
+    const bool root_deg2 = R.nchild[R.root] == 2;
+    const bool merged = root_deg2 && R.nchild[kids[R.root][0]] > 0 && R.nchild[kids[R.root][1]] > 0;
+    for (uint32_t v = 0; v < N; ++v) {
+        if (R.nchild[v] == 0 || R.parent[v] < 0) continue;
+        const uint32_t u = (uint32_t)R.parent[v];
+        uint32_t w = u, dup = none, iv = none, par = R.parent[u] >= 0 ? 1u : 0u;
+        if (u == R.root && root_deg2) {
+            if (!merged || v != kids[u][0]) continue;   // the edge through the root: one record, written to both children
+            w = dup = kids[u][1]; par = 0;
+        } else {
+            iv = (uint32_t)(std::find(kids[u].begin(), kids[u].end(), v) - kids[u].begin());
+        }
+        const uint32_t rec[kTreeBranchEdgeWords] = {v, dup, boff[v], R.nchild[v], boff[w], R.nchild[w], iv, par};
+        edges.insert(edges.end(), rec, rec + kTreeBranchEdgeWords);
+    }
+    QS_HIP(c, hipSetDevice(c->device));
+    QS_HIP(c, hipStreamSynchronize(c->stream));   // kernels of this context may still read the previous tree's arrays
+    // (the cache key goes before the first buffer, as in agree_ref_upload)
+    c->tbranch_parent.clear(); c->tbranch_leaf_node.clear();
+    c->tbranch_edges.reset(); c->tbranch_bnd.reset();
+    QS_HIP(c, c->tbranch_edges.reserve(std::max<size_t>(edges.size(), 1) * 4, nullptr));
+    QS_HIP(c, c->tbranch_bnd.reserve(std::max<size_t>(bnd.size(), 1) * 2, nullptr));
+    if (!edges.empty()) QS_HIP(c, hipMemcpy(c->tbranch_edges.get(), edges.data(), edges.size() * 4, hipMemcpyHostToDevice));
+    if (!bnd.empty()) QS_HIP(c, hipMemcpy(c->tbranch_bnd.get(), bnd.data(), bnd.size() * 2, hipMemcpyHostToDevice));
+    c->tbranch_n_e = (uint32_t)(edges.size() / kTreeBranchEdgeWords);
+    c->tbranch_n_nodes = N;
+    c->tbranch_frame = R.bifurcating ? 0 : 1;   // (fill_score_device: the order of (q1,q2,q3) qs_score uses without flags)
+    c->tbranch_parent.assign(ref->parent, ref->parent + N);
+    c->tbranch_leaf_node.assign(ref->leaf_node, ref->leaf_node + n);
+    return QS_OK;
+}
+
+extern "C" int qs_tree_branch_support(qs_ctx *c, const qs_ref_tree *ref, const qs_device_batch *b, int64_t *dst_device) {
+    if (!c) return QS_ERR_ARG;
+    const char *who = "qs_tree_branch_support";
+    if (int rc = need_args(c, who, b && dst_device)) return rc;
+    if (c->d_lo != 0 || c->d_hi != c->n)
+        return fail(c, QS_ERR_UNSUPPORTED, "qs_tree_branch_support: whole-table contexts only (no table shards)");
+    if (int rc = need_aligned(c, who, dst_device)) return rc;
+    if (int rc = tree_branch_ref_upload(c, ref)) return rc;
+    const DeviceBatch &d = b->d;
+    if (d.n_trees && !d.node_off) return fail(c, QS_ERR_STATE, "qs_tree_branch_support: the batch was uploaded without node ranges");
+    QS_HIP(c, hipSetDevice(c->device));
+    if (d.ready) QS_HIP(c, hipStreamWaitEvent(c->stream, d.ready, 0));
+    QS_HIP(c, launch_tree_branch(c->stream, d, c->n, d.max_tree_nodes, c->tbranch_edges.get(), c->tbranch_bnd.get(), c->tbranch_n_e,
+                                 c->tbranch_n_nodes, c->tbranch_frame, reinterpret_cast<unsigned long long *>(dst_device)));
+    return QS_OK;   // asynchronous on the context's stream
+}
+
+// Weighted sums over the trees of the rows of qs_tree_branch_support, one per replicate of a bootstrap over the trees; dst is ADDED to.
+extern "C" int qs_branch_resample(qs_ctx *c, const int64_t *rows_device, uint32_t n_trees, uint32_t n_nodes, const uint32_t *weights_host,
+                                  uint32_t n_rep, int64_t *dst_device) {
+    if (!c) return QS_ERR_ARG;
+    const char *who = "qs_branch_resample";
+    if (int rc = need_args(c, who, rows_device && weights_host && dst_device)) return rc;
+    if (int rc = need_aligned(c, who, dst_device)) return rc;
+    if (int rc = need_aligned(c, who, rows_device, "rows_device")) return rc;
+    if ((uint64_t)n_nodes * kBranchWords > 0xFFFFFFFFull) return fail(c, QS_ERR_ARG, "qs_branch_resample: n_nodes x 4 must fit 32 bits");
+    // a word of a row is at most C(n,4): every replicate's sum stays below 2^63 if (sum of its weights) x C(n,4) does
+    const uint64_t n = c->n, quads = n >= 4 ? n * (n - 1) / 2 * (n - 2) / 3 * (n - 3) / 4 : 0;
+    for (uint32_t r = 0; r < n_rep; ++r) {
+        uint64_t s = 0;
+        for (uint32_t t = 0; t < n_trees; ++t) s += weights_host[(size_t)r * n_trees + t];
+        if (quads && s > (uint64_t)INT64_MAX / quads)
+            return fail(c, QS_ERR_OVERFLOW, "qs_branch_resample: (sum of the weights) x C(n,4) exceeds 63 bits for replicate " + std::to_string(r));
+    }
+    if (n_trees == 0 || n_rep == 0 || n_nodes == 0) return QS_OK;
+    QS_HIP(c, hipSetDevice(c->device));
+    QS_HIP(c, hipStreamSynchronize(c->stream));   // (an earlier call's upload may still read the old weights)
+    c->resample_weights.assign(weights_host, weights_host + (size_t)n_rep * n_trees);
+    QS_HIP(c, c->resample_weights_dev.reserve(c->resample_weights.size() * 4, nullptr));
+    QS_HIP(c, hipMemcpyAsync(c->resample_weights_dev.get(), c->resample_weights.data(), c->resample_weights.size() * 4, hipMemcpyHostToDevice, c->stream));
+    QS_HIP(c, launch_branch_resample(c->stream, reinterpret_cast<const long long *>(rows_device), n_trees, n_nodes * kBranchWords,
+                                     c->resample_weights_dev.get(), n_rep, reinterpret_cast<unsigned long long *>(dst_device)));
     return QS_OK;   // asynchronous on the context's stream
 }

@@ -50,15 +50,7 @@ __global__ __launch_bounds__(kAgreeThreads) void tree_agree_kernel(AgreeArgs a) 
     const long long N = L;
     uint2 *pres = lds, *links = lds + W;
 
-    for (uint32_t w = tid; w < W; w += kAgreeThreads) pres[w] = make_uint2(0, 0);
-    __syncthreads();
-    for (uint32_t p = tid; p < L; p += kAgreeThreads) atomicOr(&pres[ids[p] >> 5].x, 1u << (ids[p] & 31));
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t s = 0;
-        for (uint32_t w = 0; w < W; ++w) { pres[w].y = s; s += __popc(pres[w].x); }
-    }
-    __syncthreads();
+    bm_build_presence(pres, ids, L, W, tid, kAgreeThreads);
 
     unsigned long long *out = a.dst + 4ull * t;
     const auto range_len = [&](uint32_t k) { return (int)((a.ranges[2 * k + 1] + L - a.ranges[2 * k]) % L); };
@@ -93,24 +85,7 @@ __global__ __launch_bounds__(kAgreeThreads) void tree_agree_kernel(AgreeArgs a) 
         const bool stored = v1 > v0;
         if (!stored) v1 = v0 + 1;
         const uint32_t n_links = stored ? a.rng_off[v1] - k_base : 0;
-        __syncthreads();   // the previous round's readers are done
-        for (uint32_t i = tid; i < n_links * W; i += kAgreeThreads) links[i] = make_uint2(0, 0);
-        __syncthreads();
-        for (uint32_t li = tid / kWave; li < n_links; li += kAgreeThreads / kWave) {
-            const uint32_t s = a.ranges[2 * (k_base + li)], len = range_len(k_base + li);
-            uint2 *bm = links + li * W;
-            for (uint32_t i = tid % kWave; i < len; i += kWave) {
-                const uint32_t id = ids[(s + i) % L];
-                atomicOr(&bm[id >> 5].x, 1u << (id & 31));
-            }
-        }
-        __syncthreads();
-        for (uint32_t li = tid; li < n_links; li += kAgreeThreads) {
-            uint2 *bm = links + li * W;
-            uint32_t s = 0;
-            for (uint32_t w = 0; w < W; ++w) { bm[w].y = s; s += __popc(bm[w].x); }
-        }
-        __syncthreads();
+        bm_build_links(links, a.ranges, ids, L, W, k_base, n_links, tid, kAgreeThreads);
 
         for (uint32_t u = tid; u < a.n_u; u += kAgreeThreads) {
             const uint32_t bo = a.ref_off[u];

@@ -13,6 +13,44 @@ __device__ __forceinline__ int bm_count(const uint2 *bm, uint32_t x) {
     return (int)e.y + __popc(e.x & ((1u << (x & 31)) - 1u));
 }
 
+// The LDS bitmaps of the kernels that walk (reference node, node of one evaluation tree) pairs (qs_agree.hip, qs_tree_branch.hip), built
+// by the whole workgroup of `threads` lanes; both end with a barrier.
+// pres <- the ids of the tree's L leaves
+__device__ __forceinline__ void bm_build_presence(uint2 *pres, const uint16_t *ids, uint32_t L, uint32_t W, uint32_t tid, uint32_t threads) {
+    for (uint32_t w = tid; w < W; w += threads) pres[w] = make_uint2(0, 0);
+    __syncthreads();
+    for (uint32_t p = tid; p < L; p += threads) atomicOr(&pres[ids[p] >> 5].x, 1u << (ids[p] & 31));
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t s = 0;
+        for (uint32_t w = 0; w < W; ++w) { pres[w].y = s; s += __popc(pres[w].x); }
+    }
+    __syncthreads();
+}
+// links[li] <- the ids behind link k_base + li of the tree, li < n_links: the circular stretch ranges[2k] .. ranges[2k + 1] of its leaf
+// list; a wave per link. Starts with a barrier: the previous round's readers are done.
+__device__ __forceinline__ void bm_build_links(uint2 *links, const uint16_t *ranges, const uint16_t *ids, uint32_t L, uint32_t W, uint32_t k_base,
+                                               uint32_t n_links, uint32_t tid, uint32_t threads) {
+    __syncthreads();
+    for (uint32_t i = tid; i < n_links * W; i += threads) links[i] = make_uint2(0, 0);
+    __syncthreads();
+    for (uint32_t li = tid / kWave; li < n_links; li += threads / kWave) {
+        const uint32_t s = ranges[2 * (k_base + li)], len = (ranges[2 * (k_base + li) + 1] + L - s) % L;
+        uint2 *bm = links + li * W;
+        for (uint32_t i = tid % kWave; i < len; i += kWave) {
+            const uint32_t id = ids[(s + i) % L];
+            atomicOr(&bm[id >> 5].x, 1u << (id & 31));
+        }
+    }
+    __syncthreads();
+    for (uint32_t li = tid; li < n_links; li += threads) {
+        uint2 *bm = links + li * W;
+        uint32_t s = 0;
+        for (uint32_t w = 0; w < W; ++w) { bm[w].y = s; s += __popc(bm[w].x); }
+    }
+    __syncthreads();
+}
+
 struct ClaimSums {
     long long sm = 0;   // sum over node pairs of same + mixed = 4 x concordant
     long long dc = 0;   // 4 x discordant

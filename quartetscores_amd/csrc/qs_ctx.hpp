@@ -168,6 +168,16 @@ struct qs_ctx {
     DevBuf<uint16_t> agree_bnd;
     DevBuf<uint8_t> agree_par;
     uint32_t agree_n_u = 0;
+    // qs_tree_branch_support: the reference tree's internodes and child boundaries on the device (launch_tree_branch), and the tree they
+    // came from; qs_branch_resample: the weights of the last call, kept until the upload on `stream` has read them
+    std::vector<int32_t> tbranch_parent;
+    std::vector<uint32_t> tbranch_leaf_node;
+    DevBuf<uint32_t> tbranch_edges;
+    DevBuf<uint16_t> tbranch_bnd;
+    uint32_t tbranch_n_e = 0, tbranch_n_nodes = 0;
+    int tbranch_frame = 0;
+    std::vector<uint32_t> resample_weights;
+    DevBuf<uint32_t> resample_weights_dev;
     // qs_tree_pair_agreement: the position maps and node orders of the last call's row trees (tree_pairs_work_words; grown, never shrunk)
     DevBuf<uint16_t> pair_pos;
     // qs_taxon_placement: the cached reference tree's link lookups (dropped with ref_lca_dev), the walks of an n-taxon table and

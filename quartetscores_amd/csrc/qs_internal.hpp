@@ -224,6 +224,18 @@ hipError_t launch_branch_taxa(hipStream_t s, const BranchDevice &bd, uint32_t n_
 // key of the node pair at the ends of the internode above node v (all ones: none), quartets[v] = its number of 4-sets
 hipError_t launch_branch_totals(hipStream_t s, const unsigned long long *sums, const uint32_t *edge_key, const unsigned long long *quartets,
                                 uint32_t n_nodes, unsigned long long *dst);
+// qs_tree_branch.hip: per tree of the batch and internode of the reference the four words (4-sets inside the tree's taxa, q1, q2, q3)
+// over the 4-sets around the internode (qs_tree_branch_support). edges = n_e records of kTreeBranchEdgeWords words: node of the lower
+// end v, second node that gets the same words (all ones: none; under a degree-2 root its other inner child), offset into bnd and
+// number of v's children, the same two of the upper end w, v's index among w's children (all ones: none, the two are the children of
+// a degree-2 root) and whether w has a parent link. bnd = per inner node its children's first ids in id order and the id behind the
+// last. frame as in ScoreDevice. dst = n_trees rows of n_nodes x 4 words, overwritten
+constexpr int kTreeBranchEdgeWords = 8;
+hipError_t launch_tree_branch(hipStream_t s, const DeviceBatch &b, uint32_t n, uint32_t max_tree_nodes, const uint32_t *edges, const uint16_t *bnd,
+                              uint32_t n_e, uint32_t n_nodes, int frame, unsigned long long *dst);
+// ... and dst[rep][cell] += sum over t of weights[rep][t] x rows[t][cell] (qs_branch_resample); weights on the device, n_rep x n_trees
+hipError_t launch_branch_resample(hipStream_t s, const long long *rows, uint32_t n_trees, uint32_t cells, const uint32_t *weights, uint32_t n_rep,
+                                  unsigned long long *dst);
 // qs_place_clade.hip: link sums of the quartet placement of listed clades (qs_clade_placement); whole tables only. ref_lca, inner_node,
 // child, next as in PlaceDevice. tasks = d | group of 64 largest ids << 16 by d ascending, in the numbering of the ids OUTSIDE a clade:
 // the walk of the middle id n_outside - 1 - d (d = 1 ..: the longest walks first), so that the first clades[4 i + 3] entries are the walks

@@ -135,19 +135,12 @@ BRANCH_TAXON_FIELDS = ("quartets", "q1", "q2", "q3")
 DROP_ONE_COLUMNS = ("taxon", "name", "node", "lo", "hi", "group", "quartets", "q1", "q2", "q3", "qpic", "qpic_without", "delta")
 
 
-def drop_one_columns(ref: flatten.RefTree, taxa, rows, totals) -> dict:
-    """The columns of QuartetScores --drop-one from Context.branch_taxon_support: rows (len(taxa), n_nodes, 4) and totals (n_nodes, 4)
-    int64 in BRANCH_TAXON_FIELDS order, taxa = the lookup ids of the rows (None = all, in id order) -> dict in DROP_ONE_COLUMNS order
-    with one entry per row's taxon (in the order of taxa) and internode (in node order; under a degree-2 root the edge through the root
-    once, at the child that holds lookup id 0): int64 arrays taxon, node = the edge's child node, [lo, hi) = the lookup ids below it,
-    group = the number of taxa in the taxon's link at its end of the edge, quartets q1 q2 q3 = the row's words, the list name and the
-    float64 arrays qpic = log_score(totals), qpic_without = log_score(totals - row), nan where no 4-set around the edge is left
-    without the taxon (it is alone in its link at an end of degree 3: the edge dissolves), and delta = qpic_without - qpic."""
+def _internodes(ref: flatten.RefTree):
+    """(parent, lo, hi, kids, edges) of a reference tree: [lo, hi) = the lookup ids below every node, kids in id order, edges = the
+    internodes as (child node, other end) in node order -- under a degree-2 root the edge through the root once, at the child that
+    holds lookup id 0, with the root's other child as its other end"""
     parent = np.asarray(ref.parent, dtype=np.int64)
     N, n = len(parent), ref.n_taxa
-    ids = np.arange(n, dtype=np.int64) if taxa is None else np.asarray(taxa, dtype=np.int64).reshape(-1)
-    rows = np.asarray(rows, dtype=np.int64).reshape(len(ids), N, 4)
-    totals = np.asarray(totals, dtype=np.int64).reshape(N, 4)
     lo, hi = np.full(N, n, dtype=np.int64), np.zeros(N, dtype=np.int64)
     for i in range(n):
         v = int(ref.leaf_node[i])
@@ -156,15 +149,7 @@ def drop_one_columns(ref: flatten.RefTree, taxa, rows, totals) -> dict:
             v = int(parent[v])
     kids = [sorted(np.nonzero(parent == v)[0].tolist(), key=lambda k: lo[k]) for v in range(N)]
     root = int(np.nonzero(parent < 0)[0][0])
-
-    def link_size(end, x, away):
-        """taxa in x's link at the node `end`, whose link towards `away` is the edge itself"""
-        for k in kids[end]:
-            if k != away and lo[k] <= x < hi[k]:
-                return int(hi[k] - lo[k])
-        return int(n - (hi[end] - lo[end]))          # the parent's side
-
-    edges = []                                       # (child node, other end)
+    edges = []
     for v in range(N):
         if v == root or not kids[v]:
             continue
@@ -175,6 +160,30 @@ def drop_one_columns(ref: flatten.RefTree, taxa, rows, totals) -> dict:
                 edges.append((v, w))
         else:
             edges.append((v, u))
+    return parent, lo, hi, kids, edges
+
+
+def drop_one_columns(ref: flatten.RefTree, taxa, rows, totals) -> dict:
+    """The columns of QuartetScores --drop-one from Context.branch_taxon_support: rows (len(taxa), n_nodes, 4) and totals (n_nodes, 4)
+    int64 in BRANCH_TAXON_FIELDS order, taxa = the lookup ids of the rows (None = all, in id order) -> dict in DROP_ONE_COLUMNS order
+    with one entry per row's taxon (in the order of taxa) and internode (in node order; under a degree-2 root the edge through the root
+    once, at the child that holds lookup id 0): int64 arrays taxon, node = the edge's child node, [lo, hi) = the lookup ids below it,
+    group = the number of taxa in the taxon's link at its end of the edge, quartets q1 q2 q3 = the row's words, the list name and the
+    float64 arrays qpic = log_score(totals), qpic_without = log_score(totals - row), nan where no 4-set around the edge is left
+    without the taxon (it is alone in its link at an end of degree 3: the edge dissolves), and delta = qpic_without - qpic."""
+    parent, lo, hi, kids, edges = _internodes(ref)
+    N, n = len(parent), ref.n_taxa
+    ids = np.arange(n, dtype=np.int64) if taxa is None else np.asarray(taxa, dtype=np.int64).reshape(-1)
+    rows = np.asarray(rows, dtype=np.int64).reshape(len(ids), N, 4)
+    totals = np.asarray(totals, dtype=np.int64).reshape(N, 4)
+
+    def link_size(end, x, away):
+        """taxa in x's link at the node `end`, whose link towards `away` is the edge itself"""
+        for k in kids[end]:
+            if k != away and lo[k] <= x < hi[k]:
+                return int(hi[k] - lo[k])
+        return int(n - (hi[end] - lo[end]))          # the parent's side
+
     out = {name: [] for name in DROP_ONE_COLUMNS}
     for k, x in enumerate(ids.tolist()):
         for v, w in edges:
@@ -196,6 +205,61 @@ def drop_one_columns(ref: flatten.RefTree, taxa, rows, totals) -> dict:
         if name != "name":
             out[name] = np.asarray(out[name], dtype=np.float64 if name in ("qpic", "qpic_without", "delta") else np.int64)
     return out
+
+
+TREE_BRANCH_FIELDS = ("present", "q1", "q2", "q3")
+TREE_BRANCH_COLUMNS = ("tree", "node", "lo", "hi", "present", "q1", "q2", "q3", "concordance")
+BOOTSTRAP_COLUMNS = ("node", "lo", "hi", "qpic", "mean", "sd", "lo95", "hi95", "reps")
+
+
+def tree_branch_columns(ref: flatten.RefTree, rows, first_tree=0) -> dict:
+    """The columns of QuartetScores --branch-trees from Context.tree_branch_support: rows (m, n_nodes, 4) int64 in TREE_BRANCH_FIELDS
+    order, first_tree = the index of rows[0] among all evaluation trees -> dict in TREE_BRANCH_COLUMNS order with one entry per tree
+    and internode (in node order; the edge through a degree-2 root once, as in drop_one_columns) that has present > 0: int64 arrays
+    tree, node = the edge's child node, [lo, hi) = the lookup ids below it, present q1 q2 q3 = the row's words, and the float64 array
+    concordance = q1 / (q1 + q2 + q3), nan where all three are 0."""
+    parent, lo, hi, _, edges = _internodes(ref)
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, len(parent), 4)
+    out = {name: [] for name in TREE_BRANCH_COLUMNS}
+    for t in range(len(rows)):
+        for v, _ in edges:
+            present, q1, q2, q3 = (int(z) for z in rows[t, v])
+            if present == 0:
+                continue
+            s = q1 + q2 + q3
+            for name, val in zip(TREE_BRANCH_COLUMNS, (first_tree + t, v, int(lo[v]), int(hi[v]), present, q1, q2, q3, q1 / s if s else math.nan)):
+                out[name].append(val)
+    return {name: np.asarray(col, dtype=np.float64 if name == "concordance" else np.int64) for name, col in out.items()}
+
+
+def bootstrap_columns(ref: flatten.RefTree, sums, replicates) -> dict:
+    """The columns of QuartetScores --bootstrap: sums (n_nodes, 4) = Context.tree_branch_support(...).sum(0) over all evaluation trees,
+    replicates (B, n_nodes, 4) = Context.branch_resample of the same rows with every replicate's multiplicities -> dict in
+    BOOTSTRAP_COLUMNS order with one entry per internode (as in drop_one_columns): int64 arrays node, lo, hi, reps = B and the float64
+    arrays qpic = log_score(sums[1:4]) and, over the B values log_score(replicates[r][1:4]), mean, sd (of the population),
+    lo95 = the sorted value at index floor(0.025 (B - 1)) and hi95 = the one at ceil(0.975 (B - 1))."""
+    parent, lo, hi, _, edges = _internodes(ref)
+    N = len(parent)
+    sums = np.asarray(sums, dtype=np.int64).reshape(N, 4)
+    reps = np.asarray(replicates, dtype=np.int64).reshape(-1, N, 4)
+    B = len(reps)
+    out = {name: [] for name in BOOTSTRAP_COLUMNS}
+    for v, _ in edges:
+        vals = [log_score(int(r[v, 1]), int(r[v, 2]), int(r[v, 3])) for r in reps]
+        total = dev = 0.0                            # plain double sums in replicate order, as the CLI adds them
+        for x in vals:
+            total += x
+        mean = total / B if B else math.nan
+        for x in vals:
+            dev += (x - mean) * (x - mean)
+        sd = math.sqrt(dev / B) if B else math.nan
+        vals.sort()
+        lo95 = vals[int(math.floor(0.025 * (B - 1)))] if B else math.nan
+        hi95 = vals[int(math.ceil(0.975 * (B - 1)))] if B else math.nan
+        for name, val in zip(BOOTSTRAP_COLUMNS, (v, int(lo[v]), int(hi[v]), log_score(int(sums[v, 1]), int(sums[v, 2]), int(sums[v, 3])),
+                                                 mean, sd, lo95, hi95, B)):
+            out[name].append(val)
+    return {name: np.asarray(col, dtype=np.int64 if name in ("node", "lo", "hi", "reps") else np.float64) for name, col in out.items()}
 
 
 GROUP_FIELDS = ("quartets", "q1", "q2", "q3", "outvoted", "uninformed")
@@ -556,6 +620,40 @@ class Context:
         self.sync()
         del keep
         return buf[: 4 * n_trees].cpu().numpy().view(np.uint64).reshape(n_trees, 4)
+
+    def tree_branch_support(self, ref: flatten.RefTree, hb) -> np.ndarray:
+        """qs_tree_branch_support: per tree of the uploaded batch `hb` (uploaded with its node ranges) and node v of `ref` the four
+        words of TREE_BRANCH_FIELDS over the 4-sets around the internode above v that lie inside the tree's taxa -> int64
+        (n_trees, n_nodes, 4); tree_branch_columns turns them into the CLI's columns. Allocates the device buffer, waits for the
+        result and downloads it."""
+        n_trees = self._batch_trees[hb.value]
+        words = n_trees * ref.n_nodes * 4
+        return self._query(ref, words, lambda s, p: self.L.qs_tree_branch_support(self.h, s, hb, C.c_void_p(p))).reshape(n_trees, ref.n_nodes, 4)
+
+    def branch_resample(self, rows, weights, out=None) -> np.ndarray:
+        """qs_branch_resample: rows int64 (m, n_nodes, 4) as tree_branch_support returns them, weights (B, m) unsigned 32-bit ->
+        int64 (B, n_nodes, 4), entry [r] = sum over t of weights[r][t] * rows[t]; added to `out` (same shape) if given, so that
+        batches of trees stream through with their slice of the weights. Uploads the rows, waits for the result and downloads it."""
+        import torch
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        if rows.ndim != 3 or rows.shape[2] != 4:
+            raise ValueError("branch_resample: rows must be (m, n_nodes, 4)")
+        m, n_nodes = rows.shape[:2]
+        wide = np.asarray(weights, dtype=np.int64)
+        if wide.ndim != 2 or wide.shape[1] != m:
+            raise ValueError(f"branch_resample: weights must be (B, {m})")
+        if ((wide < 0) | (wide > 0xFFFFFFFF)).any():
+            raise QSError(_lib.QS_ERR_ARG, "branch_resample: weight out of range")
+        w = np.ascontiguousarray(wide, dtype=np.uint32)
+        B = len(w)
+        dev = f"cuda:{self.device}"
+        d_rows = torch.from_numpy(rows.reshape(-1)).to(dev) if rows.size else torch.zeros(1, dtype=torch.int64, device=dev)
+        start = np.zeros((B, n_nodes, 4), dtype=np.int64) if out is None else np.ascontiguousarray(out, dtype=np.int64).reshape(B, n_nodes, 4)
+        d_out = torch.from_numpy(start.reshape(-1)).to(dev) if start.size else torch.zeros(1, dtype=torch.int64, device=dev)
+        self._chk(self.L.qs_branch_resample(self.h, C.c_void_p(d_rows.data_ptr()), m, n_nodes, w.ctypes.data_as(C.c_void_p), B,
+                                            C.c_void_p(d_out.data_ptr())))
+        self.sync()
+        return d_out[: start.size].cpu().numpy().reshape(B, n_nodes, 4)
 
     def tree_pair_agreement(self, hb_rows, hb_cols=None, rows=None, cols=None, upper=False) -> np.ndarray:
         """qs_tree_pair_agreement: the quartet agreement of the trees rows = (r0, r1) of the uploaded batch `hb_rows` with the trees
