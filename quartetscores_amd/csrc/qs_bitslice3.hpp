@@ -51,6 +51,8 @@ constexpr int kMaxDepthBits = 10;    // deepest bit-sliced class: LCA depths bel
 constexpr int kBitTrees = 32;  // trees per element
 
 struct Planes { uint32_t w[kBitWords]; };
+typedef uint32_t qs_u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t qs_u32x2 __attribute__((ext_vector_type(2)));
 
 // One v_bitop3_b32: any boolean function of three words, given by its truth table
 // TT = f(0xF0, 0xCC, 0xAA) (bit i of TT = f at (a,b,c) = (i>>2&1, i>>1&1, i&1)). hipcc only fuses some
@@ -62,6 +64,14 @@ template <int TT> __device__ __forceinline__ uint32_t lut3(uint32_t a, uint32_t 
 constexpr int kTT_XOR3 = 0xF0 ^ 0xCC ^ 0xAA;                                  // a ^ b ^ c
 constexpr int kTT_LT = ((0x0F & 0xCC) | (~(0xF0 ^ 0xCC) & 0xAA)) & 0xFF;      // (~a & b) | (~(a ^ b) & c): borrow / less-than step
 constexpr int kTT_GT = ((0xF0 & 0x33) | (~(0xF0 ^ 0xCC) & 0xAA)) & 0xFF;      // (a & ~b) | (~(a ^ b) & c): greater-than step
+constexpr int tt_swap12(int tt) {   // g(a, b, c) = f(a, c, b)
+    int r = 0;
+    for (int i = 0; i < 8; ++i) {
+        const int a = (i >> 2) & 1, b = (i >> 1) & 1, c = i & 1;
+        if ((tt >> ((a << 2) | (c << 1) | b)) & 1) r |= 1 << i;
+    }
+    return r;
+}
 
 // LDS image with HW (1, 2, 4 or 8) upper words per slot: words 0..3 at buf[e], the upper words in an array
 // of HW-word records behind the `stride` 16-byte slots
@@ -119,6 +129,69 @@ __device__ __forceinline__ Planes sub_biased(const Planes &x, const Planes &y) {
     return r;
 }
 
+// ---- VGPR source banks by construction (the instances of bs3_staggered) ----
+// A v_bitop3_b32 whose src0 and src1 sit in one VGPR bank (bank = register number mod 4) issues ~0.2 cycles later, a v_bcnt_u32_b32
+// whose two sources share a bank ~1 cycle later; src2 of the v_bitop3 is free (profiles/r03_experiments.md 7). Which numbers the
+// allocator picks cannot be told from here, but the PARITY of a register can: a VGPR tuple starts at an even register, so element k
+// of a tuple has parity k, and registers of different parity lie in different banks. The helpers below pass values through EMPTY
+// asm statements as elements of tuples: nothing is emitted, the statement only makes the allocator hold the value in such an element.
+//
+// stagger_planes: the NB planes of an L operand (a result of sub_biased that a whole step compares against) at elements 1..NB of ONE
+// tuple, element 0 left undefined: plane k of L at parity k + 1. Plane k (k < 4) of an R element arrives in element k of a
+// ds_read_b128 destination, at parity k. So no low-plane chain instruction (src0 = L plane, src1 = R plane) reads both from one bank.
+// PIN: a volatile statement, which also keeps L in front of what follows (step_dma).
+template <int NB, bool PIN = false> __device__ __forceinline__ void stagger_planes(Planes &p) {
+    static_assert(NB >= 4 && NB + 1 <= 8, "planes 0..3 of R come from one ds_read_b128; the tuple is NB + 1 registers, a size VGPR tuples exist in");
+    typedef uint32_t tuple_t __attribute__((ext_vector_type(NB + 1)));
+    static_assert(sizeof(tuple_t) >= (NB + 1) * 4 && alignof(tuple_t) >= 8, "a multi-register value: allocated as a tuple, which starts at an even VGPR");
+    tuple_t t;
+#pragma unroll
+    for (int k = 0; k < NB; ++k) t[k + 1] = p.w[k];
+    if (PIN) asm volatile("" : "+v"(t));
+    else asm("" : "+v"(t));
+#pragma unroll
+    for (int k = 0; k < NB; ++k) p.w[k] = t[k + 1];
+}
+// `acc` into the free element 0 of a staggered operand's tuple (even; the top plane, element NB, is odd for the 5-plane operands)
+template <int NB> __device__ __forceinline__ void acc_to_element0(Planes &p, uint32_t &acc) {
+    typedef uint32_t tuple_t __attribute__((ext_vector_type(NB + 1)));
+    tuple_t t;
+    t[0] = acc;
+#pragma unroll
+    for (int k = 0; k < NB; ++k) t[k + 1] = p.w[k];
+    asm("" : "+v"(t));
+    acc = t[0];
+#pragma unroll
+    for (int k = 0; k < NB; ++k) p.w[k] = t[k + 1];
+}
+// v in a register of the given parity: one half of a pair whose other half stays undefined (and free for other values)
+__device__ __forceinline__ uint32_t parity_reg(uint32_t v, int odd) {
+    qs_u32x2 t;
+    t[odd] = v;
+    asm("" : "+v"(t));
+    return t[odd];
+}
+// sub_biased for operands that BOTH come from 16-byte loads (plane k of x and of y at parity k: src0 / src1 of sub_biased meet in one
+// bank whenever the two tuples start 0 mod 4 apart). Here the borrow goes to src1 and the subtrahend to src2 (tables permuted), and
+// the borrow that enters plane k is held at parity k + 1. Used where it costs no register: the two L operands of a step.
+template <int B>
+__device__ __forceinline__ Planes sub_biased_staggered(const Planes &x, const Planes &y) {
+    Planes r;
+    uint32_t br = 0;
+#pragma unroll
+    for (int k = 0; k < B; ++k) {
+        const uint32_t a = x.w[k], b = y.w[k];
+        r.w[k] = lut3<kTT_XOR3>(a, br, b);
+        br = lut3<tt_swap12(kTT_LT)>(a, br, b);
+        if (k + 1 < B) br = parity_reg(br, k & 1);
+    }
+    r.w[B] = br;
+#pragma unroll
+    for (int k = B + 1; k < kPres; ++k) r.w[k] = 0;
+    r.w[kPres] = x.w[kPres] & y.w[kPres];
+    return r;
+}
+
 // [l > r] and [l < r] for two results of sub_biased (NB = B+1 planes, the top one inverted), 32 trees at once
 template <int NB>
 __device__ __forceinline__ void cmp_planes(const Planes &l, const Planes &r, uint32_t &gt, uint32_t &lt) {
@@ -132,6 +205,45 @@ __device__ __forceinline__ void cmp_planes(const Planes &l, const Planes &r, uin
     const uint32_t a = l.w[NB - 1], b = r.w[NB - 1];   // inverted planes: the roles of the two tables swap
     gt = lut3<kTT_LT>(a, b, gt);
     lt = lut3<kTT_GT>(a, b, lt);
+}
+// cmp_planes for an L operand that went through stagger_planes. The low planes are clean by the parity of L and R. The top plane's
+// R word comes from a 4-byte LDS read (ds_read_b32 / ds_read2_b32), at any parity: it goes to src2, and the accumulator to src1
+// against L's top plane (tables permuted for the swapped sources). The lt accumulator is held in element 0 of L's own tuple, even
+// against the top plane's odd (element NB; NB is odd where this is used: five planes). The gt accumulator is
+// left to the allocator: every way tried of holding it even as well (a pair of its own, element 0 of the other a-column's tuple)
+// cost the six-wave instance 6 to 16 spilled registers. (A parity for L's top word that R's cannot meet does not exist: ds_read2_b32
+// delivers the top words of two d-rows at both parities.)
+template <int NB>
+__device__ __forceinline__ void cmp_planes_staggered(Planes &l, const Planes &r, uint32_t &gt, uint32_t &lt) {
+    static_assert(NB % 2 == 1, "the top plane (element NB of L's tuple) must be odd against the accumulator in element 0");
+    gt = 0; lt = 0;
+#pragma unroll
+    for (int k = 0; k < NB - 1; ++k) {
+        const uint32_t a = l.w[k], b = r.w[k];
+        gt = lut3<kTT_GT>(a, b, gt);
+        lt = lut3<kTT_LT>(a, b, lt);
+    }
+    acc_to_element0<NB>(l, lt);
+    const uint32_t a = l.w[NB - 1], b = r.w[NB - 1];   // inverted planes: the roles of the two tables swap
+    gt = lut3<tt_swap12(kTT_LT)>(a, gt, b);
+    lt = lut3<tt_swap12(kTT_GT)>(a, lt, b);
+}
+// x0 += popcount(gt), x1 += popcount(lt) with gt in the even and lt in the odd half of one pair. The counters they feed stand at the
+// opposite parity where pair_counters put them.
+__device__ __forceinline__ void popc_pair(uint32_t gt, uint32_t lt, uint32_t &x0, uint32_t &x1) {
+    qs_u32x2 res;
+    res[0] = gt; res[1] = lt;
+    asm("" : "+v"(res));
+    popc_acc(res[0], x0);
+    popc_acc(res[1], x1);
+}
+// The two counters of a quartet as one pair: x1 (fed by lt, odd) in the even half, x0 (fed by gt, even) in the odd half. Stated once
+// in front of a segment's loop: in the loop the allocator has no reason to move a counter (a statement per step cost 16 moves).
+__device__ __forceinline__ void pair_counters(uint32_t &x0, uint32_t &x1) {
+    qs_u32x2 c;
+    c[0] = x1; c[1] = x0;
+    asm volatile("" : "+v"(c));
+    x1 = c[0]; x0 = c[1];
 }
 template <int NB>
 __device__ __forceinline__ uint32_t gt_planes(const Planes &l, const Planes &r) {
@@ -151,8 +263,6 @@ constexpr int s3_row0(bool gen) { return kDB * s3_cols(gen); }              // R
 constexpr int s3_slots(bool gen) { return s3_row0(gen) + s3_cols(gen); }    // 144 / 216
 constexpr uint32_t kS3Inv = 0x80000000u;       // offset beyond any tree group (also after >> 2): the buffer load returns zeros
 
-typedef uint32_t qs_u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t qs_u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t qs_u32x3 __attribute__((ext_vector_type(3)));
 typedef qs_u32x3 qs_u32x3_a4 __attribute__((aligned(4)));   // 12-byte vector at a 4-byte aligned address
 
@@ -299,6 +409,18 @@ template <int B, int MODE> constexpr int bs3_six_waves() { return (MODE == MODE_
 // raw area of the dma order, uint4 per wave: 64 x M[b,d] (lane = d-row * 8 + b-column), 8 x M[c,d], 16 x M[x,c]
 constexpr int kDmaY = 64, kDmaRow = 72, kDmaRaw = 88;
 
+// Which instances lay their operands out by VGPR bank ("VGPR source banks by construction" above): the six-wave dma instance
+// (76 -> 80 VGPRs, the bound of six waves; nothing spilled, no instruction added). Every other instance keeps the layout the
+// allocator picks: the tuple of stagger_planes alone spills in the late order at 5 bits and in the prefetch order at 4, measured 0.6 %
+// (inside the spread) in the prefetch order at 5 bits and 1.0 % (1.5 parent spreads, with more same-bank v_bcnt in two of its loops)
+// in the late order at 4 bits (profiles/r19_vgpr_banks.md). QS_STAGGER = 0: no instance (A/B builds).
+#ifndef QS_STAGGER
+#define QS_STAGGER 1
+#endif
+template <int B, int MODE, int ORD> constexpr bool bs3_staggered() {
+    return QS_STAGGER && MODE == MODE_BINARY_FULL && ORD == kOrdSix && QS_SIX_DMA;
+}
+
 constexpr int kWavesPerBlock = kCountThreads / kWave;   // 4: a workgroup = four independent wave tiles (consecutive in the launch order)
 
 // ======================================================================================
@@ -435,6 +557,7 @@ __device__ __forceinline__ void bs3_segment(const Bs3Tile &t, const uint4 *__res
     constexpr bool BIN = Lay::BIN, GEN = Lay::GEN, PART = Lay::PART, BP = Lay::BP;
     constexpr bool DMA = ORD == kOrdSix && QS_SIX_DMA, LATE = ORD == kOrdLate || (ORD == kOrdSix && !DMA);
     constexpr int LROW = ORD == kOrdSix ? kDB : bs3_late_row<B>();   // in front of which d-row the late order requests the next group
+    constexpr bool STAG = bs3_staggered<B, MODE, ORD>();   // L operands through stagger_planes, chains and popcounts by parity (step_dma)
     static_assert(!LATE || BIN, "the late-load step exists for the binary modes");
     static_assert(ORD != kOrdSix || (MODE == MODE_BINARY_FULL && B == 4), "the six-wave instance: binary_full, 16-byte panel elements");
     constexpr int RC = Lay::RC, kS3Row0 = Lay::kS3Row0, kS3Slots = Lay::kS3Slots, NBUF = Lay::NBUF, NB = Lay::NB, NW = Lay::NW, HW = Lay::HW, PW = Lay::PW;
@@ -506,26 +629,39 @@ __device__ __forceinline__ void bs3_segment(const Bs3Tile &t, const uint4 *__res
     struct Staged { Planes x0, x1, x2, y, row; };
     // binary modes, both step orders: the compare chains of d-row j -- R element Rb of (b,d) against L1 and, where the second
     // a-column exists, L2
-    auto bin_row = [&](int j, const Planes &L1, const Planes &L2, const Planes &Rb, auto a2_tag) {
+    // staggered instance: the counters in pairs, once per segment (pair_counters); the second a-column's only where it exists (a
+    // counter that went through the statement is no longer known to be zero)
+    auto pair_all = [&](auto a2_tag) {
+        if constexpr (STAG) {
+#pragma unroll
+            for (int j = 0; j < kDB; ++j) {
+                pair_counters(x0[j], x1[j]);
+                if (decltype(a2_tag)::value) pair_counters(y0[j], y1[j]);
+            }
+        }
+    };
+    auto bin_row = [&](int j, Planes &L1, Planes &L2, const Planes &Rb, auto a2_tag) {
         uint32_t gt, lt;
-        cmp_planes<NB>(L1, Rb, gt, lt);
+        if constexpr (STAG) cmp_planes_staggered<NB>(L1, Rb, gt, lt);
+        else cmp_planes<NB>(L1, Rb, gt, lt);
         if (BP) {
             const uint32_t v = L1.w[kPres] & Rb.w[kPres];   // a1, b, c, d all present
             gt &= v; lt &= v;
             popc_acc(v, z0[j]);   // trees that hold all four: a binary one resolves the quartet, so ad|bc = this count - the other two (epilogue)
         }
-        popc_acc(gt, x0[j]);
-        popc_acc(lt, x1[j]);
+        if (STAG) popc_pair(gt, lt, x0[j], x1[j]);
+        else { popc_acc(gt, x0[j]); popc_acc(lt, x1[j]); }
         if (decltype(a2_tag)::value) {
             uint32_t gt2, lt2;
-            cmp_planes<NB>(L2, Rb, gt2, lt2);
+            if constexpr (STAG) cmp_planes_staggered<NB>(L2, Rb, gt2, lt2);
+            else cmp_planes<NB>(L2, Rb, gt2, lt2);
             if (BP) {
                 const uint32_t v2 = L2.w[kPres] & Rb.w[kPres];
                 gt2 &= v2; lt2 &= v2;
                 popc_acc(v2, z1[j]);
             }
-            popc_acc(gt2, y0[j]);
-            popc_acc(lt2, y1[j]);
+            if (STAG) popc_pair(gt2, lt2, y0[j], y1[j]);
+            else { popc_acc(gt2, y0[j]); popc_acc(lt2, y1[j]); }
         }
     };
 
@@ -562,7 +698,7 @@ __device__ __forceinline__ void bs3_segment(const Bs3Tile &t, const uint4 *__res
         // binary modes: the compare chains run at issue priority 1, the request / staging part of the step at 0 (round 6: -1 % on
         // configs[2], -1.2 % for binary_partial; the general modes LOSE 0.6-4.5 % with it and keep priority 0: profiles/r06_experiments.md 8)
         if (BIN && QS_BIN_PRIO) __builtin_amdgcn_s_setprio(1);
-        const Planes L1 = sub_biased<B>(abc1, row0_load(cur, colA1)); // M[a1 b] - M[a1 c] + 2^B
+        Planes L1 = sub_biased<B>(abc1, row0_load(cur, colA1)); // M[a1 b] - M[a1 c] + 2^B
         Planes L2 = L1, G1 = L1, G2 = L1;
         if (A2) L2 = sub_biased<B>(abc2, row0_load(cur, colA2));      // M[a2 b] - M[a2 c] + 2^B
         if (GEN) {                                                    // M[ab] - M[bc] + 2^B: the other side of the third comparison
@@ -664,7 +800,7 @@ __device__ __forceinline__ void bs3_segment(const Bs3Tile &t, const uint4 *__res
             return r;
         };
         if (QS_BIN_PRIO) __builtin_amdgcn_s_setprio(1);
-        const Planes L1 = sub_biased<B>(ab1, row0_load(cur, colA));
+        Planes L1 = sub_biased<B>(ab1, row0_load(cur, colA));
         Planes L2 = L1;
         if (A2) L2 = sub_biased<B>(ab2, row0_load(cur, colA + kTA));
         Planes sx0 = L1, sy = L1, sx1 = L1, srow = L1;
@@ -770,18 +906,23 @@ __device__ __forceinline__ void bs3_segment(const Bs3Tile &t, const uint4 *__res
         if (decltype(nr_tag)::value >= 2) lstore(lds, slot0 + 8, sub_biased<B>(sx1, sy));
         lds_order<1>();
     };
+    // L1 / L2 of the dma step: the difference, pinned in front of the request -- as a tuple of its own (stagger_planes) or plane by plane
+    auto dma_L = [&](const Planes &ab, const Planes &row) {
+        Planes L = STAG ? sub_biased_staggered<B>(ab, row) : sub_biased<B>(ab, row);
+        if constexpr (STAG) stagger_planes<NB, true>(L);
+        else asm volatile("" : "+v"(L.w[0]), "+v"(L.w[1]), "+v"(L.w[2]), "+v"(L.w[3]), "+v"(L.w[4]));
+        return L;
+    };
     auto step_dma = [&](uint32_t g_next, Planes &ab1, Planes &ab2, auto a2_tag, auto full_tag, auto nr_tag) {
         constexpr bool A2 = decltype(a2_tag)::value, FULL = decltype(full_tag)::value;
         if (xcd_remap & 2u) __builtin_amdgcn_s_barrier();   // waves of a workgroup in step: see `step`
         const uint32_t colA = colA_o;
         if (QS_BIN_PRIO) __builtin_amdgcn_s_setprio(1);
-        Planes L1 = sub_biased<B>(ab1, raw_load(kDmaRow + colA));
-        Planes L2 = L1, sx1 = L1;
-        if (A2) L2 = sub_biased<B>(ab2, raw_load(kDmaRow + kTA + colA));
         // L1 / L2 are pinned in front of the request: the masked DMA is a branch, and the compiler otherwise sinks the two differences
         // into the block behind it -- behind a wait for the DMA that has just been issued (the raw area is read AND written here)
-        asm volatile("" : "+v"(L1.w[0]), "+v"(L1.w[1]), "+v"(L1.w[2]), "+v"(L1.w[3]), "+v"(L1.w[4]));
-        if (A2) asm volatile("" : "+v"(L2.w[0]), "+v"(L2.w[1]), "+v"(L2.w[2]), "+v"(L2.w[3]), "+v"(L2.w[4]));
+        Planes L1 = dma_L(ab1, raw_load(kDmaRow + colA));
+        Planes L2 = L1, sx1 = L1;
+        if (A2) L2 = dma_L(ab2, raw_load(kDmaRow + kTA + colA));
         dma_request(g_next, ab1, ab2, sx1, a2_tag, nr_tag);
 #pragma unroll
         for (int j = 0; j < kDB; ++j) {
@@ -806,6 +947,7 @@ __device__ __forceinline__ void bs3_segment(const Bs3Tile &t, const uint4 *__res
             Planes ab1, ab2, sx1;
 #pragma unroll
             for (int w = 0; w < kBitWords; ++w) ab2.w[w] = sx1.w[w] = 0;
+            pair_all(a2_tag);
             dma_request(0, ab1, ab2, sx1, a2_tag, nr_tag);
             dma_finish(sx1, nr_tag);
             const uint32_t g_last = n_groups - 1;
