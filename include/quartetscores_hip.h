@@ -24,7 +24,8 @@
  *   qs_taxon_pair_support         replaces nothing in the reference (it has no output per pair of taxa)
  *   qs_branch_taxon_support       replaces nothing in the reference (it never asks what a branch's QP-IC would be without one taxon)
  *   qs_tree_branch_support /      replace nothing in the reference (it sums over the trees before it looks at a branch, and never
- *   qs_branch_resample            resamples them)
+ *   qs_branch_resample /          resamples them, and has no per-tree normalised frequencies)
+ *   qs_branch_frequencies
  *   qs_group_check /              replace nothing in the reference; the nearest is the metaquartet sum of processNodePair
  *   qs_group_support              (QuartetScoreComputer.hpp:379-472), which knows only the four subtrees beside a node pair of the tree
  *   qs_taxon_placement /          replace nothing in the reference (it never asks where the evaluation trees would put a taxon; the
@@ -498,6 +499,22 @@ int qs_tree_branch_support(qs_ctx *ctx, const qs_ref_tree *ref, const qs_device_
  * call) x C(n_taxa,4) can exceed 63 bits. Asynchronous on the context's stream. */
 int qs_branch_resample(qs_ctx *ctx, const int64_t *rows_device, uint32_t n_trees, uint32_t n_nodes, const uint32_t *weights_host,
                        uint32_t n_rep, int64_t *dst_device);
+
+/* Sums over the trees of such rows' NORMALISED frequencies: the inputs of a branch's local posterior probability, its length in
+ * coalescent units and the polytomy test (Sayyari & Mirarab 2016, 2018). Each tree weighs the same however many of the
+ * 4-sets around the branch it holds, so these are no function of the sums over trees of q1, q2, q3: neither the count table nor
+ * qs_branch_resample gives them. With S = q1 + q2 + q3 of (tree, node) and ONE = 2^40:
+ *   dst_device[node][0] += the number of trees with S > 0                                   ("effective n", en)
+ *   dst_device[node][i] += the sum over those trees of floor(q_i x ONE / S),  i = 1, 2, 3   (Z_i; z_i = Z_i / ONE)
+ * Fixed point, so that the sums are exact integers, independent of grid, batching and repetition; z_i is below the rational sum by
+ * less than en x 2^-40. The division is exact for every S up to C(4096,4). rows_device = [n_trees][n_nodes][4] words as
+ * qs_tree_branch_support writes them, dst_device = [n_nodes][4] words; both 8-byte aligned. dst_device is ADDED to: the caller zeroes
+ * it once and streams batch after batch, fewer than 2^23 trees in all (the sums then stay below 2^63). n_trees = 0 or n_nodes = 0 does
+ * nothing. Words outside 0 <= q, S <= C(4096,4) give an unspecified sum and no access outside the buffers.
+ * Errors: QS_ERR_ARG = NULL argument, misaligned rows_device / dst_device, n_nodes > 2^21; QS_ERR_OVERFLOW = n_trees >= 2^23. Asynchronous on the
+ * context's stream. The posterior itself is host arithmetic on four words per branch (engine.local_pp, csrc/host/local_pp.hpp).
+ * Replaces nothing in the reference. */
+int qs_branch_frequencies(qs_ctx *ctx, const int64_t *rows_device, uint32_t n_trees, uint32_t n_nodes, int64_t *dst_device);
 
 /* Quartet support of user-defined taxon groups from the count table: how often do the evaluation trees show each resolution around a
  * branch the caller names -- whether or not any reference tree has it. Replaces nothing in the reference; the nearest is the metaquartet

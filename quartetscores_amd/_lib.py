@@ -43,7 +43,7 @@ EXPORTS = [
     "qs_sum_words", "qs_issue_probe", "qs_last_count_fix_ms", "qs_batch_clamp_info", "qs_depth_clamp_plan", "qs_score_check", "qs_last_count_events", "qs_class_plan", "qs_shard_bounds",
     "qs_table_remap", "qs_tree_agreement", "qs_taxon_support", "qs_table_restrict", "qs_taxon_placement", "qs_placement_scores", "qs_clade_placement",
     "qs_last_count_split", "qs_fix_overlap_plan", "qs_group_check", "qs_group_support", "qs_tree_pair_agreement", "qs_taxon_pair_support",
-    "qs_branch_taxon_support", "qs_tree_branch_support", "qs_branch_resample",
+    "qs_branch_taxon_support", "qs_tree_branch_support", "qs_branch_resample", "qs_branch_frequencies",
 ]
 
 
@@ -129,6 +129,8 @@ def load():
     L.qs_tree_branch_support.argtypes = [vp, vp, vp, vp]
     L.qs_branch_resample.restype = i32
     L.qs_branch_resample.argtypes = [vp, vp, u32, u32, vp, u32, vp]
+    L.qs_branch_frequencies.restype = i32
+    L.qs_branch_frequencies.argtypes = [vp, vp, u32, u32, vp]
     L.qs_taxon_placement.restype = i32
     L.qs_taxon_placement.argtypes = [vp, vp, vp, u32, vp]
     L.qs_placement_scores.restype = i32

@@ -30,6 +30,7 @@
 #include "table_shards.hpp"
 #include "synth.hpp"
 #include "tree_distances.hpp"
+#include "local_pp.hpp"
 
 #include <algorithm>
 #include <cerrno>
@@ -97,6 +98,9 @@ struct Args {
     uint32_t bootstrap_reps = 100;   // --bootstrap-reps B
     uint64_t bootstrap_seed = 1;     // --bootstrap-seed S
     bool bootstrap_reps_given = false, bootstrap_seed_given = false;
+    std::string local_pp;         // --local-pp FILE: local posterior, coalescent length and polytomy test of every internode of -r (TSV)
+    double local_pp_lambda = 0.5; // --local-pp-lambda L
+    bool local_pp_lambda_given = false;
     std::string place_clades;      // --place-clades FILE: quartet placement of the clades of -r from the count table (TSV)
     std::string place_clades_only; // --place-clades-only SPEC: a file of the clades to place, one per line (default: every eligible inner clade)
     std::vector<uint32_t> place_nodes; // the nodes to place, in output order (check_place_clades)
@@ -255,7 +259,21 @@ void usage(std::ostream &os) {
           "                  2.5 % / 97.5 % points (the sorted values at floor(0.025 (B-1)) and ceil(0.975 (B-1))). One GPU that counts\n"
           "                  (not with --gpus / --table-shards / --load-table); works with --branch-trees and beside every other output\n"
           "   --bootstrap-reps B  with --bootstrap: the number of replicates (default 100)\n"
-          "   --bootstrap-seed S  with --bootstrap: the seed of the resampling (default 1); the same seed gives the same file\n";
+          "   --bootstrap-seed S  with --bootstrap: the seed of the resampling (default 1); the same seed gives the same file\n"
+          "   --local-pp F   write, per internal branch of the -r tree, its local posterior probability, its length in coalescent units\n"
+          "                  and the polytomy test to F (TSV, one line per branch in node order after a header: node lo hi en f1 f2 f3\n"
+          "                  pp1 pp2 pp3 length polytomy_p). Every evaluation tree gives the FRACTIONS of the 4-sets around the branch\n"
+          "                  that it resolves as the -r tree does and as the two alternatives (--branch-trees' q1 q2 q3 over their sum), so\n"
+          "                  a tree that lacks half the taxa weighs as much as a complete one; en = the trees that resolve any, f1 f2 f3 =\n"
+          "                  the sums of the fractions (exact in units of 2^-40). pp1 = the posterior of the branch, pp2 pp3 = of its two\n"
+          "                  alternatives in the order of q2 q3 (Sayyari & Mirarab 2016), length = -ln(3/2 (1 - f1 / (en + 2L - 1))), 0\n"
+          "                  where f1 / (en + 2L - 1) <= 1/3 and inf where it is >= 1, polytomy_p = the p-value of the chi-square test of\n"
+          "                  f1 = f2 = f3 (2 degrees of freedom; Sayyari & Mirarab 2018). nan where en = 0. The model assumes a binary\n"
+          "                  branch: where the -r tree's branch ends in a node of degree above 3 the figures are written as computed from\n"
+          "                  the sums over all pairs of its groups. One GPU that counts (not with --gpus / --table-shards /\n"
+          "                  --load-table), fewer than 2^23 evaluation trees; works with --branch-trees / --bootstrap and beside every\n"
+          "                  other output\n"
+          "   --local-pp-lambda L  with --local-pp: the rate of the prior on branch lengths, L > 0 (default 0.5)\n";
 }
 
 // returns 0 ok, 1 error (message printed like the reference prints TCLAP::ArgException), 2 exit quietly
@@ -338,6 +356,17 @@ int parse(int argc, char **argv, Args &a) {
         else if (f == "--bootstrap") { if (!(v = need(i, "--bootstrap"))) return 1; a.bootstrap = v; }
         else if (f == "--bootstrap-reps") { if (!(v = need(i, "--bootstrap-reps")) || !number(v, "--bootstrap-reps", num)) return 1; a.bootstrap_reps = (uint32_t)std::min<unsigned long>(num, 0xFFFFFFFFul); a.bootstrap_reps_given = true; }
         else if (f == "--bootstrap-seed") { if (!(v = need(i, "--bootstrap-seed")) || !number(v, "--bootstrap-seed", num)) return 1; a.bootstrap_seed = num; a.bootstrap_seed_given = true; }
+        else if (f == "--local-pp") { if (!(v = need(i, "--local-pp"))) return 1; a.local_pp = v; }
+        else if (f == "--local-pp-lambda") {
+            if (!(v = need(i, "--local-pp-lambda"))) return 1;
+            char *end = nullptr;
+            a.local_pp_lambda = std::strtod(v, &end);
+            if (end == v || *end != '\0' || !std::isfinite(a.local_pp_lambda) || !(a.local_pp_lambda > 0.0)) {
+                std::cerr << "ERROR: Couldn't read argument value from string '" << v << "' for arg --local-pp-lambda (a positive number)" << std::endl;
+                return 1;
+            }
+            a.local_pp_lambda_given = true;
+        }
         else if (f == "--place-only") { if (!(v = need(i, "--place-only"))) return 1; a.place_only = v; }
         else if (f == "--place-clades") { if (!(v = need(i, "--place-clades"))) return 1; a.place_clades = v; }
         else if (f == "--place-clades-only") { if (!(v = need(i, "--place-clades-only"))) return 1; a.place_clades_only = v; }
@@ -419,7 +448,7 @@ std::vector<std::pair<std::string, std::string>> output_files(const Args &a) {
         {"-o", a.out}, {"-q", a.raw}, {"--qic-binary", a.raw_bin}, {"--save-table", a.dev.save_table}, {"--per-tree", a.per_tree},
         {"--tree-distances", a.tree_distances}, {"--per-taxon", a.per_taxon}, {"--place-taxa", a.place_taxa}, {"--place-clades", a.place_clades},
         {"--test-groups", a.test_groups}, {"--taxon-pairs", a.taxon_pairs}, {"--drop-one", a.drop_one}, {"--branch-trees", a.branch_trees},
-        {"--bootstrap", a.bootstrap}};
+        {"--bootstrap", a.bootstrap}, {"--local-pp", a.local_pp}};
     for (const AlsoRef &x : a.also) files.emplace_back("--also-ref", x.out);
     for (const WithoutTaxa &x : a.without) files.emplace_back("--without-taxa", x.out);
     return files;
@@ -823,10 +852,11 @@ void write_drop_one(qs_ctx *ctx, const RefFlat &ref, int device, const std::stri
     if (!f) throw std::runtime_error("cannot write " + path);
 }
 
-// --branch-trees / --bootstrap: refused like --per-tree, before the device is touched
+// --branch-trees / --bootstrap / --local-pp: refused like --per-tree, before the device is touched
 void check_tree_branches(const Args &a) {
     if (a.bootstrap.empty() && (a.bootstrap_reps_given || a.bootstrap_seed_given)) throw std::runtime_error("--bootstrap-reps / --bootstrap-seed need --bootstrap FILE");
-    for (const char *flag : {"--branch-trees", "--bootstrap"}) {
+    if (a.local_pp.empty() && a.local_pp_lambda_given) throw std::runtime_error("--local-pp-lambda needs --local-pp FILE");
+    for (const char *flag : {"--branch-trees", "--bootstrap", "--local-pp"}) {
         if (output_file(a, flag).empty()) continue;
         if (a.gpus > 0 || a.table_shards >= 0 || !a.dev.load_table.empty())
             throw std::runtime_error(std::string(flag) + " needs the evaluation trees counted on one GPU: omit --gpus / --table-shards / --load-table");
@@ -835,24 +865,27 @@ void check_tree_branches(const Args &a) {
     if (!a.bootstrap.empty() && a.bootstrap_reps == 0) throw std::runtime_error("--bootstrap-reps must be at least 1");
 }
 
-// --branch-trees / --bootstrap: qs_tree_branch_support behind every batch's count into one device buffer of (trees of the batch) x n_nodes
-// x 4 words, shared by the two outputs. --branch-trees downloads every batch and writes its lines as it comes; --bootstrap adds the batch
-// to the sums of every replicate with its slice of the replicates' weights (qs_branch_resample; row 0 of the weights is all ones: the
-// unweighted sums behind the qpic column) and downloads those once behind the final qs_sync. No buffer grows with m on the device.
+// --branch-trees / --bootstrap / --local-pp: qs_tree_branch_support behind every batch's count into one device buffer of (trees of the
+// batch) x n_nodes x 4 words, shared by the three outputs. --branch-trees downloads every batch and writes its lines as it comes;
+// --bootstrap adds the batch to the sums of every replicate with its slice of the replicates' weights (qs_branch_resample; row 0 of the
+// weights is all ones: the unweighted sums behind the qpic column); --local-pp adds the batch's normalised frequencies to n_nodes x 4
+// words (qs_branch_frequencies). Both sums are downloaded once behind the final qs_sync. No buffer grows with m on the device.
 struct TreeBranches {
-    size_t m = 0;
+    size_t m = 0, n_taxa = 0;
     int device = 0;
-    std::string lines_path, boot_path;
+    std::string lines_path, boot_path, pp_path;
     uint32_t reps = 0;
     uint64_t seed = 1;
-    qs::DevBuf<int64_t> rows, sums;
+    double lambda = 0.5;
+    qs::DevBuf<int64_t> rows, sums, freq;
     std::vector<uint32_t> weights, slice;   // [1 + reps][m]; the columns of one batch
-    std::vector<int64_t> host, totals;
+    std::vector<int64_t> host, totals, freq_totals;
     std::ofstream lines;
     std::unique_ptr<Internodes> in;
     void hook(DeviceOptions &opt, const RefFlat &ref) {
         opt.tree_branches = true;
         in.reset(new Internodes(ref));
+        n_taxa = ref.names.size();
         const size_t N = ref.parent.size();
         if (!lines_path.empty()) {
             lines.open(lines_path);
@@ -871,7 +904,7 @@ struct TreeBranches {
         add_after_count(opt, [this, &ref, N](qs_ctx *ctx, const qs_device_batch *db, size_t i0, const BatchFlat &b) {
             const size_t k = b.n_trees, words = k * N * 4;
             if (hipSetDevice(device) != hipSuccess || rows.reserve(std::max<size_t>(1, words) * 8, nullptr) != hipSuccess)
-                throw std::runtime_error("--branch-trees / --bootstrap: Insufficient memory!");
+                throw std::runtime_error("--branch-trees / --bootstrap / --local-pp: Insufficient memory!");
             const qs_ref_tree rt = ref_view(ref);
             if (qs_tree_branch_support(ctx, &rt, db, rows.get()) != QS_OK) throw std::runtime_error(qs_last_error(ctx));
             if (!boot_path.empty()) {
@@ -883,6 +916,13 @@ struct TreeBranches {
                 slice.resize((size_t)(1 + reps) * k);
                 for (size_t r = 0; r <= reps; ++r) std::copy_n(weights.begin() + (std::ptrdiff_t)(r * m + i0), k, slice.begin() + (std::ptrdiff_t)(r * k));
                 if (qs_branch_resample(ctx, rows.get(), (uint32_t)k, (uint32_t)N, slice.data(), 1 + reps, sums.get()) != QS_OK) throw std::runtime_error(qs_last_error(ctx));
+            }
+            if (!pp_path.empty()) {
+                if (!freq) {
+                    if (freq.reserve(std::max<size_t>(1, N * 4) * 8, nullptr) != hipSuccess || hipMemset(freq.get(), 0, N * 4 * 8) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+                        throw std::runtime_error("--local-pp: Insufficient memory!");
+                }
+                if (qs_branch_frequencies(ctx, rows.get(), (uint32_t)k, (uint32_t)N, freq.get()) != QS_OK) throw std::runtime_error(qs_last_error(ctx));
             }
             if (lines_path.empty()) return;   // (the next batch's rows come behind this one's sums on the context's stream)
             // the lines are written as the batch comes: the device is waited for here, which this output pays for and no other
@@ -902,6 +942,10 @@ struct TreeBranches {
             if (!lines) throw std::runtime_error("cannot write " + lines_path);
         });
         add_after_sync(opt, [this, N](qs_ctx *) {
+            if (!pp_path.empty()) {
+                freq_totals.assign(N * 4, 0);
+                if (freq && hipMemcpy(freq_totals.data(), freq.get(), freq_totals.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("--local-pp: download failed");
+            }
             if (boot_path.empty()) return;
             totals.assign((size_t)(1 + reps) * N * 4, 0);
             if (sums && hipMemcpy(totals.data(), sums.get(), totals.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("--bootstrap: download failed");
@@ -912,6 +956,7 @@ struct TreeBranches {
             lines.close();
             if (!lines) throw std::runtime_error("cannot write " + lines_path);
         }
+        write_local_pp();
         if (boot_path.empty()) return;
         const size_t N = in->lo.size(), B = reps;
         std::ofstream f(boot_path);
@@ -931,6 +976,32 @@ struct TreeBranches {
             f << e.v << '\t' << in->lo[e.v] << '\t' << in->hi[e.v] << '\t' << text[0] << '\t' << text[1] << '\t' << text[2] << '\t' << text[3] << '\t' << text[4] << '\t' << B << '\n';
         }
         if (!f) throw std::runtime_error("cannot write " + boot_path);
+    }
+    // one line per internode from the four words of its node: integers as they are, f_i = Z_i / 2^40 and local_pp.hpp's five as %.6f
+    void write_local_pp() {
+        if (pp_path.empty()) return;
+        const size_t n = n_taxa;
+        std::ofstream f(pp_path);
+        if (!f) throw std::runtime_error("cannot write " + pp_path);
+        f << "node\tlo\thi\ten\tf1\tf2\tf3\tpp1\tpp2\tpp3\tlength\tpolytomy_p\n";
+        char text[8][64];
+        for (const Internodes::Edge &e : in->edges) {
+            const int64_t *w = &freq_totals[e.v * 4];
+            // (no 4-set lies around a branch that does not leave two of the tree's n taxa on either side: it is written as en = 0 is)
+            const size_t below = in->hi[e.v] - in->lo[e.v];
+            const bool splits = n > 1 && below >= 2 && n - below >= 2;
+            double cols[8] = {(double)w[1] / 1099511627776.0, (double)w[2] / 1099511627776.0, (double)w[3] / 1099511627776.0};
+            local_pp(splits ? w[0] : 0, w + 1, lambda, cols + 3);
+            for (int i = 0; i < 8; ++i) {
+                if (std::isnan(cols[i])) std::snprintf(text[i], sizeof text[i], "nan");
+                else if (std::isinf(cols[i])) std::snprintf(text[i], sizeof text[i], "inf");   // (the length where f1 reaches en + 2L - 1)
+                else std::snprintf(text[i], sizeof text[i], "%.6f", cols[i]);
+            }
+            f << e.v << '\t' << in->lo[e.v] << '\t' << in->hi[e.v] << '\t' << w[0];
+            for (int i = 0; i < 8; ++i) f << '\t' << text[i];
+            f << '\n';
+        }
+        if (!f) throw std::runtime_error("cannot write " + pp_path);
     }
 };
 
@@ -1287,7 +1358,7 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
         per_tree.hook(dev, per_tree_ref);
     }
     TreeBranches tree_branches;
-    const bool want_branches = !a.branch_trees.empty() || !a.bootstrap.empty();
+    const bool want_branches = !a.branch_trees.empty() || !a.bootstrap.empty() || !a.local_pp.empty();
     const RefFlat tree_branches_ref = want_branches ? flatten_reference(referenceTree) : RefFlat();
     if (want_branches) {
         tree_branches.m = m;
@@ -1296,6 +1367,8 @@ void run(const Tree &referenceTree, const Args &a, size_t m, std::vector<double>
         tree_branches.boot_path = a.bootstrap;
         tree_branches.reps = a.bootstrap_reps;
         tree_branches.seed = a.bootstrap_seed;
+        tree_branches.pp_path = a.local_pp;
+        tree_branches.lambda = a.local_pp_lambda;
         tree_branches.hook(dev, tree_branches_ref);
     }
     TreeDistances tree_distances;
@@ -1395,6 +1468,7 @@ int main(int argc, char *argv[]) {
 
         std::vector<double> lqic, qpic, eqpic;
         size_t m = countEvalTrees(a.eval);
+        if (!a.local_pp.empty() && m >= (size_t(1) << 23)) throw std::runtime_error("--local-pp: 2^23 evaluation trees or more are not supported (the sums of 2^40-scaled frequencies could leave 63 bits)");
         trace_mark(a.dev, "main: evaluation file read and split into trees");
         // (round 5: no join of the HIP start-up here -- the counter's GPU set-up thread simply blocks in its first HIP call until the
         // runtime is up, while THIS thread already flattens the first batch: 25-30 ms of the start-up leave the critical path)

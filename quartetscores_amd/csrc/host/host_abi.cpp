@@ -1,10 +1,12 @@
 // host_abi.cpp -- the C++ host's Newick ingest (newick.hpp, flatten.hpp, ingest.hpp) behind a small C interface, so
 // that the Python multi-GPU driver (quartetscores_amd/dist_cli.py) reads evaluation files at native speed: every
 // rank cuts the file into tree spans once and parses + flattens only its own share with a pool of threads.
+// Also the posterior arithmetic of QuartetScores --local-pp (local_pp.hpp), so that the tests reach the C++ itself.
 // Plain g++ (no HIP); builds quartetscores_amd/lib/libquartetscores_host.so. Host plumbing, not the drop-in
 // boundary (that is include/quartetscores_hip.h).
 #include "ingest.hpp"
 
+#include "local_pp.hpp"
 #include "synth.hpp"
 
 #include <cstring>
@@ -135,6 +137,14 @@ int qsh_prune_newick(const char *text, uint64_t len, const char *const *names, u
         g_err = e.what();
         return 1;
     }
+}
+
+// The local posterior of one branch (local_pp.hpp; what QuartetScores --local-pp writes) from en and Z[3] of qs_branch_frequencies:
+// out[5] = pp1, pp2, pp3, length, polytomy_p. For the tests, which hold it against engine.local_pp and an mpmath model.
+int qsh_local_pp(int64_t en, const int64_t *Z, double lambda, double *out) {
+    if (!Z || !out || !(lambda > 0.0)) { g_err = "qsh_local_pp: NULL argument or lambda not positive"; return 1; }
+    local_pp(en, Z, lambda, out);
+    return 0;
 }
 
 uint32_t qsh_batch_n_trees(const qsh_batch *b) { return b ? b->b.n_trees : 0; }

@@ -679,3 +679,21 @@ extern "C" int qs_branch_resample(qs_ctx *c, const int64_t *rows_device, uint32_
                                      c->resample_weights_dev.get(), n_rep, reinterpret_cast<unsigned long long *>(dst_device)));
     return QS_OK;   // asynchronous on the context's stream
 }
+
+// Per node the number of trees that resolve a 4-set around its internode and the sums of their normalised frequencies in 2^-40 units
+// (the inputs of the local posterior); dst is ADDED to.
+extern "C" int qs_branch_frequencies(qs_ctx *c, const int64_t *rows_device, uint32_t n_trees, uint32_t n_nodes, int64_t *dst_device) {
+    if (!c) return QS_ERR_ARG;
+    const char *who = "qs_branch_frequencies";
+    if (int rc = need_args(c, who, rows_device && dst_device)) return rc;
+    if (int rc = need_aligned(c, who, dst_device)) return rc;
+    if (int rc = need_aligned(c, who, rows_device, "rows_device")) return rc;
+    if (n_nodes > (1u << 21)) return fail(c, QS_ERR_ARG, "qs_branch_frequencies: more than 2^21 nodes (a tree of 4096 taxa has fewer than 2^13)");
+    // a tree adds at most 2^40 to a sum: below 2^23 trees per call and in all, every sum stays below 2^63
+    if (n_trees >= (1u << 23)) return fail(c, QS_ERR_OVERFLOW, "qs_branch_frequencies: 2^23 trees or more (the sums of 2^40-scaled frequencies could leave 63 bits)");
+    if (n_trees == 0 || n_nodes == 0) return QS_OK;
+    QS_HIP(c, hipSetDevice(c->device));
+    QS_HIP(c, launch_branch_frequencies(c->stream, reinterpret_cast<const long long *>(rows_device), n_trees, n_nodes,
+                                        reinterpret_cast<unsigned long long *>(dst_device)));
+    return QS_OK;   // asynchronous on the context's stream
+}

@@ -236,6 +236,8 @@ hipError_t launch_tree_branch(hipStream_t s, const DeviceBatch &b, uint32_t n, u
 // ... and dst[rep][cell] += sum over t of weights[rep][t] x rows[t][cell] (qs_branch_resample); weights on the device, n_rep x n_trees
 hipError_t launch_branch_resample(hipStream_t s, const long long *rows, uint32_t n_trees, uint32_t cells, const uint32_t *weights, uint32_t n_rep,
                                   unsigned long long *dst);
+// ... and dst[node] += (trees with q1 + q2 + q3 > 0, sum over them of floor(q_i x 2^40 / (q1 + q2 + q3)), i = 1..3) (qs_branch_frequencies)
+hipError_t launch_branch_frequencies(hipStream_t s, const long long *rows, uint32_t n_trees, uint32_t n_nodes, unsigned long long *dst);
 // qs_place_clade.hip: link sums of the quartet placement of listed clades (qs_clade_placement); whole tables only. ref_lca, inner_node,
 // child, next as in PlaceDevice. tasks = d | group of 64 largest ids << 16 by d ascending, in the numbering of the ids OUTSIDE a clade:
 // the walk of the middle id n_outside - 1 - d (d = 1 ..: the longest walks first), so that the first clades[4 i + 3] entries are the walks

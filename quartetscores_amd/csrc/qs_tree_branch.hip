@@ -1,5 +1,6 @@
 // qs_tree_branch.hip -- per evaluation tree the quartet support of every internode of the reference tree on gfx950
-// (qs_tree_branch_support), and weighted sums of such rows over the trees (qs_branch_resample).
+// (qs_tree_branch_support), weighted sums of such rows over the trees (qs_branch_resample) and the sums of their per-tree normalised
+// frequencies (qs_branch_frequencies).
 //
 // Replaces nothing in the reference: it sums over the trees before it looks at a branch.
 //
@@ -217,6 +218,53 @@ hipError_t launch_branch_resample(hipStream_t s, const long long *rows, uint32_t
     if (n_trees == 0 || cells == 0 || n_rep == 0) return hipSuccess;
     const dim3 grid((cells + 255) / 256, (n_rep + kResampleReps - 1) / kResampleReps, (n_trees + kResampleTrees - 1) / kResampleTrees);
     hipLaunchKernelGGL(branch_resample_kernel, grid, dim3(256), 0, s, rows, n_trees, cells, weights, n_rep, dst);
+    return hipGetLastError();
+}
+
+// floor(q x 2^40 / S) for 0 <= q <= S < 2^53, exact, without a 128-bit division: q / S in double is within 2^-53 of the ratio (q and S
+// are exact doubles, the division is rounded once), so e = the integer part of it x 2^40 is the quotient or one beside it; q x 2^40 -
+// e x S lies in (-S, 2S) and is therefore right in 64-bit wrap-around arithmetic, and its sign and size say which of the three e is
+__device__ __forceinline__ unsigned long long frequency_fixed(unsigned long long q, unsigned long long S) {
+    unsigned long long e = (unsigned long long)((double)q / (double)S * 1099511627776.0);
+    const long long r = (long long)((q << 40) - e * S);
+    if (r < 0) --e;
+    else if ((unsigned long long)r >= S) ++e;
+    return e;
+}
+
+// dst[node] += (trees with q1 + q2 + q3 > 0, sum over them of floor(q_i x 2^40 / (q1 + q2 + q3)), i = 1..3): a lane owns a node and
+// reads its row of every tree of the chunk (lanes read consecutive rows; q1 q2 q3 come as one 16-byte and one 8-byte load), the four
+// sums stay in registers; one 64-bit atomic per non-zero sum. One wave per workgroup: 64 nodes x kFreqTrees trees, so that 512 taxa x
+// 10 000 trees are 157 x 16 workgroups, about ten waves for each of the chip's 256 CUs, all resident at once: that, not the loop (load,
+// wait, divide), keeps the loads in flight. No LDS.
+constexpr int kFreqNodes = 64, kFreqTrees = 64;
+
+__global__ __launch_bounds__(kFreqNodes) void branch_frequencies_kernel(const long long *__restrict__ rows, uint32_t n_trees, uint32_t n_nodes,
+                                                                        unsigned long long *__restrict__ dst) {
+    const uint32_t v = blockIdx.y * kFreqNodes + threadIdx.x, t0 = blockIdx.x * kFreqTrees;   // (the trees in x: up to 2^17 chunks)
+    if (v >= n_nodes) return;
+    const uint32_t nt = min((uint32_t)kFreqTrees, n_trees - t0);
+    struct Row { long long present, q1, q2, q3; };   // (8-byte aligned, as the ABI asks of the rows)
+    const Row *p = reinterpret_cast<const Row *>(rows) + (size_t)t0 * n_nodes + v;
+    unsigned long long acc[kBranchWords] = {0, 0, 0, 0};
+    for (uint32_t t = 0; t < nt; ++t, p += n_nodes) {
+        const Row r = *p;
+        const long long S = r.q1 + r.q2 + r.q3;
+        if (S <= 0) continue;
+        acc[0] += 1;
+        acc[1] += frequency_fixed((unsigned long long)r.q1, (unsigned long long)S);
+        acc[2] += frequency_fixed((unsigned long long)r.q2, (unsigned long long)S);
+        acc[3] += frequency_fixed((unsigned long long)r.q3, (unsigned long long)S);
+    }
+#pragma unroll
+    for (int k = 0; k < kBranchWords; ++k)
+        if (acc[k]) atomicAdd(&dst[(size_t)v * kBranchWords + k], acc[k]);
+}
+
+hipError_t launch_branch_frequencies(hipStream_t s, const long long *rows, uint32_t n_trees, uint32_t n_nodes, unsigned long long *dst) {
+    if (n_trees == 0 || n_nodes == 0) return hipSuccess;
+    const dim3 grid((n_trees + kFreqTrees - 1) / kFreqTrees, (n_nodes + kFreqNodes - 1) / kFreqNodes);
+    hipLaunchKernelGGL(branch_frequencies_kernel, grid, dim3(kFreqNodes), 0, s, rows, n_trees, n_nodes, dst);
     return hipGetLastError();
 }
 

@@ -262,6 +262,95 @@ def bootstrap_columns(ref: flatten.RefTree, sums, replicates) -> dict:
     return {name: np.asarray(col, dtype=np.int64 if name in ("node", "lo", "hi", "reps") else np.float64) for name, col in out.items()}
 
 
+BRANCH_FREQUENCY_FIELDS = ("en", "Z1", "Z2", "Z3")
+FREQUENCY_ONE = 1 << 40                              # the fixed-point unit of Z1, Z2, Z3
+LOCAL_PP_COLUMNS = ("node", "lo", "hi", "en", "f1", "f2", "f3", "pp1", "pp2", "pp3", "length", "polytomy_p")
+
+
+def _beta_continued_fraction(p: float, q: float, x: float) -> float:
+    """the continued fraction of I_x(p, q) without its front factor x^p (1-x)^q / (p B(p, q)) (modified Lentz), for
+    x < (p + 1) / (p + q + 2); csrc/host/local_pp.hpp step for step"""
+    tiny, eps = 1e-300, 1e-16
+    qab, qap, qam = p + q, p + 1.0, p - 1.0
+    c, d = 1.0, 1.0 - qab * x / qap
+    if abs(d) < tiny:
+        d = tiny
+    d = 1.0 / d
+    h = d
+    for m in range(1, 100001):
+        m2 = 2.0 * m
+        for aa in (m * (q - m) * x / ((qam + m2) * (p + m2)), -(p + m) * (qab + m) * x / ((p + m2) * (qap + m2))):
+            d = 1.0 + aa * d
+            if abs(d) < tiny:
+                d = tiny
+            c = 1.0 + aa / c
+            if abs(c) < tiny:
+                c = tiny
+            d = 1.0 / d
+            h *= d * c
+        if abs(d * c - 1.0) < eps:
+            break
+    return h
+
+
+def _log_beta_upper_third(a: float, b: float) -> float:
+    """ln(B(a, b) (1 - I_{1/3}(a, b))): the continued fraction on whichever of I_{2/3}(b, a) and I_{1/3}(a, b) converges"""
+    l13, l23 = math.log(1.0 / 3.0), math.log(2.0 / 3.0)
+    if 2.0 / 3.0 < (b + 1.0) / (a + b + 2.0):
+        return b * l23 + a * l13 - math.log(b) + math.log(_beta_continued_fraction(b, a, 2.0 / 3.0))
+    log_beta = math.lgamma(a) + math.lgamma(b) - math.lgamma(a + b)
+    log_lower = a * l13 + b * l23 - log_beta - math.log(a) + math.log(_beta_continued_fraction(a, b, 1.0 / 3.0))
+    return log_beta + math.log1p(-math.exp(log_lower))
+
+
+def local_pp(en: int, z, lam: float = 0.5) -> Tuple[float, float, float, float, float]:
+    """The local posterior of a branch (Sayyari & Mirarab 2016) from en = the trees that resolve a 4-set around it and
+    z = (z1, z2, z3) = the sums of their normalised frequencies (Context.branch_frequencies' Z_i / 2^40), lam = the prior's rate ->
+    (pp1, pp2, pp3, length, polytomy_p): the posterior of the branch and of its two alternatives (in the order of q2, q3), the
+    branch's length in coalescent units (0 where z1 / (en + 2 lam - 1) <= 1/3, inf where it is >= 1) and the p-value of the polytomy
+    test (chi-square, 2 degrees of freedom). All nan where en = 0. Log space throughout; the arithmetic of csrc/host/local_pp.hpp."""
+    if lam <= 0:
+        raise ValueError("local_pp: lam must be positive")
+    if en <= 0:
+        return (math.nan,) * 5
+    n = float(en)
+    z = [float(x) for x in z]
+    w = [x * math.log(2.0) + _log_beta_upper_third(x + 1.0, n - x + 2.0 * lam) for x in z]
+    top = max(w)
+    total = math.exp(w[0] - top) + math.exp(w[1] - top) + math.exp(w[2] - top)
+    pp = [math.exp(x - top) / total for x in w]
+    theta = z[0] / (n + 2.0 * lam - 1.0)
+    if not math.isfinite(theta) or theta <= 1.0 / 3.0:
+        length = 0.0
+    elif theta >= 1.0:
+        length = math.inf
+    else:
+        length = -math.log(1.5 * (1.0 - theta))
+    chi2 = 0.0
+    for x in z:
+        chi2 += (x - n / 3.0) * (x - n / 3.0) / (n / 3.0)
+    return pp[0], pp[1], pp[2], length, math.exp(-chi2 / 2.0)
+
+
+def local_pp_columns(ref: flatten.RefTree, freq, lam: float = 0.5) -> dict:
+    """The columns of QuartetScores --local-pp: freq (n_nodes, 4) int64 in BRANCH_FREQUENCY_FIELDS order = Context.branch_frequencies
+    over all evaluation trees -> dict in LOCAL_PP_COLUMNS order with one entry per internode (as in bootstrap_columns): int64 arrays
+    node, lo, hi, en and the float64 arrays f_i = Z_i / 2^40 and local_pp(en, (f1, f2, f3), lam)'s five. The floats other than f_i
+    are nan where en = 0, and where the branch does not leave two taxa of the tree's n on either side (no 4-set lies around it)."""
+    parent, lo, hi, _, edges = _internodes(ref)
+    N, n = len(parent), ref.n_taxa
+    freq = np.asarray(freq, dtype=np.int64).reshape(N, 4)
+    out = {name: [] for name in LOCAL_PP_COLUMNS}
+    for v, _ in edges:
+        en = int(freq[v, 0])
+        f = [int(freq[v, i]) / FREQUENCY_ONE for i in (1, 2, 3)]
+        below = int(hi[v] - lo[v])
+        splits = n - 1 > 0 and below >= 2 and n - below >= 2
+        for name, val in zip(LOCAL_PP_COLUMNS, (v, int(lo[v]), int(hi[v]), en, *f, *(local_pp(en if splits else 0, f, lam)))):
+            out[name].append(val)
+    return {name: np.asarray(col, dtype=np.int64 if name in ("node", "lo", "hi", "en") else np.float64) for name, col in out.items()}
+
+
 GROUP_FIELDS = ("quartets", "q1", "q2", "q3", "outvoted", "uninformed")
 GROUP_KINDS = ("quad", "split")
 
@@ -654,6 +743,33 @@ class Context:
                                             C.c_void_p(d_out.data_ptr())))
         self.sync()
         return d_out[: start.size].cpu().numpy().reshape(B, n_nodes, 4)
+
+    def branch_frequencies(self, rows, out=None) -> np.ndarray:
+        """qs_branch_frequencies: rows int64 (m, n_nodes, 4) as tree_branch_support returns them (a host array, or a torch tensor
+        on this context's device, which is read in place) -> int64 (n_nodes, 4) in BRANCH_FREQUENCY_FIELDS order: per node the number
+        of trees with q1 + q2 + q3 > 0 and the sums over them of floor(q_i * 2^40 / (q1 + q2 + q3)); added to `out` (same shape) if
+        given, so that batches of trees stream through. local_pp / local_pp_columns turn them into the posterior. Waits for the
+        result and downloads it."""
+        import torch
+        dev = f"cuda:{self.device}"
+        if isinstance(rows, torch.Tensor):
+            if rows.dtype != torch.int64 or not rows.is_contiguous() or str(rows.device) != dev:
+                raise ValueError(f"branch_frequencies: a tensor of rows must be contiguous int64 on {dev}")
+            d_rows = rows
+        else:
+            d_rows = np.ascontiguousarray(rows, dtype=np.int64)
+        if d_rows.ndim != 3 or d_rows.shape[2] != 4:
+            raise ValueError("branch_frequencies: rows must be (m, n_nodes, 4)")
+        m, n_nodes = int(d_rows.shape[0]), int(d_rows.shape[1])
+        if not isinstance(rows, torch.Tensor):
+            d_rows = torch.from_numpy(d_rows.reshape(-1)).to(dev)
+        if m * n_nodes == 0:
+            d_rows = torch.zeros(1, dtype=torch.int64, device=dev)
+        start = np.zeros((n_nodes, 4), dtype=np.int64) if out is None else np.ascontiguousarray(out, dtype=np.int64).reshape(n_nodes, 4)
+        d_out = torch.from_numpy(start.reshape(-1)).to(dev) if start.size else torch.zeros(1, dtype=torch.int64, device=dev)
+        self._chk(self.L.qs_branch_frequencies(self.h, C.c_void_p(d_rows.data_ptr()), m, n_nodes, C.c_void_p(d_out.data_ptr())))
+        self.sync()
+        return d_out[: start.size].cpu().numpy().reshape(n_nodes, 4)
 
     def tree_pair_agreement(self, hb_rows, hb_cols=None, rows=None, cols=None, upper=False) -> np.ndarray:
         """qs_tree_pair_agreement: the quartet agreement of the trees rows = (r0, r1) of the uploaded batch `hb_rows` with the trees

@@ -43,6 +43,8 @@ def _lib():
         L.qsh_free_text.argtypes = [C.c_void_p]
         L.qsh_prune_newick.restype = C.c_int
         L.qsh_prune_newick.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_void_p)]
+        L.qsh_local_pp.restype = C.c_int
+        L.qsh_local_pp.argtypes = [C.c_int64, C.POINTER(C.c_int64), C.c_double, C.POINTER(C.c_double)]
         L.qsh_batch_n_trees.restype = C.c_uint32
         L.qsh_batch_n_trees.argtypes = [C.c_void_p]
         L.qsh_batch_array.restype = C.c_void_p
@@ -116,6 +118,16 @@ def prune_newick(text: str, drop_names) -> str:
         return C.string_at(p).decode()
     finally:
         L.qsh_free_text(p)
+
+
+def local_pp(en: int, Z, lam: float = 0.5):
+    """The C++ host's posterior arithmetic (csrc/host/local_pp.hpp, what QuartetScores --local-pp writes): en and the three fixed-point
+    sums Z of Context.branch_frequencies -> (pp1, pp2, pp3, length, polytomy_p). engine.local_pp is the same in Python."""
+    L = _lib()
+    out = (C.c_double * 5)()
+    if L.qsh_local_pp(int(en), (C.c_int64 * 3)(*[int(x) for x in Z]), float(lam), out) != 0:
+        raise IngestError(L.qsh_last_error().decode())
+    return tuple(out)
 
 
 def _take(L, h) -> flatten.TreeBatch:
