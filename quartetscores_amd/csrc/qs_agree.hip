@@ -11,8 +11,12 @@
 // interval is two LDS reads. The reference's links are id intervals: the children of u split u's id interval, the parent
 // link is the rest. Each lane takes reference nodes u and walks the block's nodes v. A binary pair (3 x 3) needs six
 // interval counts and runs unrolled; other degrees go through the loops of pair_terms, O(min(k,l) k l) per pair. When the
-// links of the block exceed the LDS budget, the nodes are taken in rounds; a single node with more links than the budget
-// has its interval counts taken from the tree's leaf list instead (slow, exact; only above ~1000 taxa).
+// links of the block exceed the LDS budget of a round (agree_plan's cap: 256 links up to 991 taxa, fewer above: 232 at
+// 1100, 112 at 2259), the nodes are taken in rounds; a single node with more than cap links -- 257 links are enough up to
+// 991 taxa, so a 258-taxon tree with one big polytomy has one -- gets no bitmaps and has its interval counts taken from
+// the tree's leaf list instead. Exact, and slow: its pair with a reference node is the same O(min(k,l) k l) accessor calls
+// in one lane, but each call is two walks over one link's stretch of the leaf list in place of two LDS reads
+// (tests/agree_rounds.py restates the plan and the rounds; tests/test_gpu_tree_rounds.py runs them).
 //
 // Every lane adds exact integers (4x concordant, 4x discordant, 2x resolved counts; int64 arithmetic, modulo 2^64 in the
 // atomics) into dst; agree_finish_kernel divides. Integer sums do not depend on the order: the result is deterministic.

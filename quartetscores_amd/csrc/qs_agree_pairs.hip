@@ -19,7 +19,9 @@
 // leaves outside S do not count), I[r][c] arc counts on the link bitmaps. Links without a shared leaf give zeros, which
 // pair_terms and node_resolved2 take unchanged. Each lane takes inner nodes u of s and walks the block's nodes v; a binary pair
 // runs unrolled (rows 0, 1 and columns 0, 1 from the bitmaps: eight counts; the rest from the sizes). Rounds and the unstored
-// path of a node with more links than the LDS budget are qs_agree.hip's; the unstored counts walk t's leaf list through pos_s.
+// path are qs_agree.hip's: a node of t with more links than a round's budget (agree_plan's cap; 257 links are enough up to 991 taxa)
+// gets no bitmaps, and each accessor call of its pairs is one walk over its link's stretch of t's leaf list through pos_s (list_count:
+// leaves without a position in s do not count, the others by the arc test), the same O(min(k,l) k l) calls per pair, in one lane.
 //
 // Cost per node pair O(min(k,l) k l) in the two degrees: two stars of a thousand leaves meeting are 1e9 operations in ONE lane.
 // Every lane adds exact integers (4x, 4x, 2x, 2x; modulo 2^64 in the atomics), one atomic per wave; pair_finish_kernel divides.

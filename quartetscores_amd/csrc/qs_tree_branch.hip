@@ -28,7 +28,9 @@
 //
 // A lane adds the words of its own internodes to dst: plainly where the tree has one block of nodes, with one 64-bit atomic per
 // non-zero word where it has several. Integer sums: the result does not depend on grid, batching, rooting or repetition. The rounds
-// of a block whose links exceed the LDS budget and the leaf-list counts of a single node beyond it are qs_agree.hip's.
+// of a block whose links exceed a round's LDS budget (agree_plan's cap) and the leaf-list counts of a single node beyond it are
+// qs_agree.hip's: a node with more than cap links (257 are enough up to 991 taxa) has no bitmaps, and every cnt of it walks its link's
+// stretch of the leaf list: branch_piece calls cnt seven times per link, seven passes over the tree's leaves per (group, piece).
 #include "qs_agree_terms.hpp"
 #include "qs_common.hpp"
 #include "qs_internal.hpp"
