@@ -221,19 +221,6 @@ inline void raw_unrank(uint64_t r, uint32_t &s0, uint32_t &s1, uint32_t &s2, uin
         s0 = (uint32_t)r; s1 = (uint32_t)b; s2 = (uint32_t)c; s3 = (uint32_t)d;
     }
 
-    // QuartetScoreComputer.hpp:135-159 with the host libm
-inline double raw_log_score(size_t q1, size_t q2, size_t q3) {
-        if (q1 == 0 && q2 == 0 && q3 == 0) return 0;
-        size_t sum = q1 + q2 + q3;
-        double p1 = (double)q1 / sum, p2 = (double)q2 / sum, p3 = (double)q3 / sum;
-        double qic = 1;
-        if (p1 != 0) qic += p1 * std::log(p1) / std::log(3);
-        if (p2 != 0) qic += p2 * std::log(p2) / std::log(3);
-        if (p3 != 0) qic += p3 * std::log(p3) / std::log(3);
-        return (q1 < q2 || q1 < q3) ? qic * -1 : qic;
-    }
-
-
     // QuartetScoreComputer.hpp:623-690: "(a,b|c,d): qic" per quartet resolved in the reference tree.
     // The GPU classifies and looks up a chunk of ranks (qs_raw_qic); the host formats the chunk with all
     // ingest threads into per-thread buffers and writes them in order (the reference

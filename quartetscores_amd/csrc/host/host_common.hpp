@@ -5,6 +5,7 @@
 #include "../../../include/quartetscores_hip.h"
 #include "../qs_devbuf.hpp"
 #include "flatten.hpp"
+#include "quartet_math.hpp"
 
 #include <chrono>
 #include <cstdint>
@@ -62,8 +63,6 @@ inline void trace_mark(const DeviceOptions &opt, const char *what) {
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     std::fprintf(stderr, "[trace] +%8.1f ms  %s\n", ms, what);
 }
-
-inline uint64_t c4(uint64_t x) { return x < 4 ? 0 : x * (x - 1) * (x - 2) * (x - 3) / 24; }   // C(x,4)
 
 inline void hip_ok(hipError_t e, const char *what) { if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e)); }
 
