@@ -18,6 +18,8 @@
  *                                 qs_table_remap replaces nothing (the reference recounts per reference tree), nor does
  *                                 qs_table_restrict (the reference recounts per taxon set)
  *   qs_tree_agreement             replaces nothing in the reference (it reports no per-tree agreement)
+ *   qs_tree_taxon_agreement /     replace nothing in the reference (it has no output per tree and none per taxon)
+ *   qs_tree_taxa_plan
  *   qs_tree_pair_agreement        replaces nothing in the reference (it never compares the evaluation trees with each other)
  *   qs_taxon_support              replaces nothing in the reference (the nearest is printRawQICScores, :612-680: one text
  *                                 line per quartet, which a user would reduce per taxon on the host)
@@ -488,6 +490,32 @@ int qs_branch_taxon_support(qs_ctx *ctx, const qs_ref_tree *ref, const uint16_t 
  * depth-first order; QS_ERR_STATE = the batch was uploaded without node ranges; QS_ERR_UNSUPPORTED = a table-shard context.
  * Asynchronous on the context's stream. The reference sums over the trees before it looks at a branch: this replaces nothing there. */
 int qs_tree_branch_support(qs_ctx *ctx, const qs_ref_tree *ref, const qs_device_batch *b, int64_t *dst_device);
+
+/* Per-tree quartet agreement of every taxon: which leaf of which evaluation tree disagrees with the reference. For tree t of the
+ * uploaded batch `b` (uploaded with its node ranges) with taxon set P_t, L = |P_t|, the reference restricted to P_t and a taxon x of
+ * P_t, four exact words over the C(L-1,3) 4-sets of P_t that hold x:
+ *   k = 0 concordant     resolved in both trees, same topology       k = 2 resolved_eval  resolved in t
+ *   k = 1 discordant     resolved in both trees, different ones      k = 3 resolved_ref   resolved in the reference
+ * dst_device (caller-owned device memory, 8-byte aligned, [n_trees of b][n_taxa][4] words by lookup id) is OVERWRITTEN; taxa outside
+ * P_t and trees of fewer than four taxa give zeros. Multifurcating and rooted trees on both sides; the root plays no part. Two
+ * identities hold exactly: over the taxa of a tree every word sums to four times the word qs_tree_agreement gives for that tree (every
+ * 4-set has four members); over the trees of a counted batch word 0 sums to qs_taxon_support's concordant of the table, word 1 to its
+ * discordant and word 2 - word 0 - word 1 to its eval_only. No table is needed and none is touched: the call changes neither the table
+ * nor trees-counted nor a pending score log. No 4-set is enumerated: closed forms over the pairs (reference node, node of t) reach the
+ * taxa through difference arrays over the ids in LDS; exact integers, independent of grid, batching, rooting and
+ * repetition; every word is at most C(4095,3) < 2^34, so there is no overflow to report. The reference tree is checked as by
+ * qs_tree_agreement and shares its per-context cache.
+ * Errors: QS_ERR_ARG = NULL argument, misaligned dst_device, malformed reference, n_taxa differs from the context's, ids not in
+ * depth-first order; QS_ERR_STATE = the batch was uploaded without node ranges; QS_ERR_UNSUPPORTED = a table-shard context, or more
+ * taxa than qs_tree_taxa_plan's limit (1277: the difference arrays share 64 KB of LDS with the bitmaps).
+ * Asynchronous on the context's stream, behind the batch's upload. The reference has no output per tree and none per taxon: this
+ * replaces nothing there. */
+int qs_tree_taxon_agreement(qs_ctx *ctx, const qs_ref_tree *ref, const qs_device_batch *b, int64_t *dst_device);
+
+/* Host-only: the LDS plan of qs_tree_taxon_agreement for n_taxa. out = { words per bitmap, link bitmaps of one round, inner nodes of one
+ * workgroup, links of a node whose difference arrays are in LDS at once, bytes of those arrays, dynamic LDS bytes of the launch, the
+ * largest n_taxa the call supports }. QS_ERR_UNSUPPORTED (out is still written; entries 1 and 5 are 0) above that limit. */
+int qs_tree_taxa_plan(uint32_t n_taxa, uint32_t out[7]);
 
 /* Weighted sums of such rows over the trees, for a bootstrap over the evaluation trees: QP-IC of an internode is log_score of three
  * sums over trees, so a replicate is a reweighting of the per-tree words, not a recount.

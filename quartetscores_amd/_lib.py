@@ -44,6 +44,7 @@ EXPORTS = [
     "qs_table_remap", "qs_tree_agreement", "qs_taxon_support", "qs_table_restrict", "qs_taxon_placement", "qs_placement_scores", "qs_clade_placement",
     "qs_last_count_split", "qs_fix_overlap_plan", "qs_group_check", "qs_group_support", "qs_tree_pair_agreement", "qs_taxon_pair_support",
     "qs_branch_taxon_support", "qs_tree_branch_support", "qs_branch_resample", "qs_branch_frequencies",
+    "qs_tree_taxon_agreement", "qs_tree_taxa_plan",
 ]
 
 
@@ -127,6 +128,10 @@ def load():
     L.qs_branch_taxon_support.argtypes = [vp, vp, vp, u32, vp, vp]
     L.qs_tree_branch_support.restype = i32
     L.qs_tree_branch_support.argtypes = [vp, vp, vp, vp]
+    L.qs_tree_taxon_agreement.restype = i32
+    L.qs_tree_taxon_agreement.argtypes = [vp, vp, vp, vp]
+    L.qs_tree_taxa_plan.restype = i32
+    L.qs_tree_taxa_plan.argtypes = [u32, vp]
     L.qs_branch_resample.restype = i32
     L.qs_branch_resample.argtypes = [vp, vp, u32, u32, vp, u32, vp]
     L.qs_branch_frequencies.restype = i32

@@ -154,6 +154,8 @@ EdgeScores run(const Tree &referenceTree, const Args &a, size_t m) {
     if (!a.per_tree.empty()) per_tree.reset(new PerTree(a, m, referenceTree, dev));
     std::unique_ptr<TreeBranches> tree_branches;
     if (TreeBranches::wanted(a)) tree_branches.reset(new TreeBranches(a, m, referenceTree, dev));
+    std::unique_ptr<TreeTaxa> tree_taxa;
+    if (!a.tree_taxa.empty()) tree_taxa.reset(new TreeTaxa(a, referenceTree, dev));
     TreeDistances tree_distances;
     if (!a.tree_distances.empty()) {
         dev.tree_distances = a.tree_distances;
@@ -174,6 +176,7 @@ EdgeScores run(const Tree &referenceTree, const Args &a, size_t m) {
     if (per_tree) per_tree->write();
     if (!a.tree_distances.empty()) tree_distances.write(qsc.context(), a.dev.device, a.tree_distances);
     if (tree_branches) tree_branches->write();
+    if (tree_taxa) tree_taxa->write();
     if (!a.per_taxon.empty()) write_per_taxon(qsc.context(), qsc.reference(), a);
     if (!a.place_taxa.empty()) write_place_taxa(qsc.context(), qsc.reference(), a);
     if (!a.place_clades.empty()) write_place_clades(qsc.context(), qsc.reference(), a);
@@ -216,6 +219,7 @@ int main(int argc, char *argv[]) {
         check_test_groups(a);
         a.pair_ids = check_taxon_list_output(a, "--taxon-pairs");
         a.drop_ids = check_taxon_list_output(a, "--drop-one");
+        check_tree_taxa(a);
     } catch (const std::exception &e) {
         std::cerr << "ERROR: " << e.what() << std::endl;
         return 1;

@@ -69,6 +69,11 @@ struct Args {
     uint32_t bootstrap_reps = 100;   // --bootstrap-reps B
     uint64_t bootstrap_seed = 1;     // --bootstrap-seed S
     bool bootstrap_reps_given = false, bootstrap_seed_given = false;
+    std::string tree_taxa;        // --tree-taxa FILE: per evaluation tree the quartet agreement of every taxon it holds with -r (TSV)
+    std::string tree_taxa_only;   // --tree-taxa-only NAMES: a file of the taxon labels whose lines are written (default: all)
+    std::vector<uint16_t> tree_taxa_ids;   // the lookup ids whose lines are written, ascending (check_taxon_list_output)
+    double tree_taxa_min_gain = 0.0;       // --tree-taxa-min-gain G: only the lines with gain >= G
+    bool tree_taxa_min_gain_given = false;
     std::string local_pp;         // --local-pp FILE: local posterior, coalescent length and polytomy test of every internode of -r (TSV)
     double local_pp_lambda = 0.5; // --local-pp-lambda L
     bool local_pp_lambda_given = false;
@@ -244,7 +249,23 @@ inline void usage(std::ostream &os) {
           "                  the sums over all pairs of its groups. One GPU that counts (not with --gpus / --table-shards /\n"
           "                  --load-table), fewer than 2^23 evaluation trees; works with --branch-trees / --bootstrap and beside every\n"
           "                  other output\n"
-          "   --local-pp-lambda L  with --local-pp: the rate of the prior on branch lengths, L > 0 (default 0.5)\n";
+          "   --local-pp-lambda L  with --local-pp: the rate of the prior on branch lengths, L > 0 (default 0.5)\n"
+          "   --tree-taxa F  write, per evaluation tree and taxon the tree holds, how the 4-sets of the tree that hold the taxon agree with\n"
+          "                  the -r tree to F (TSV, after a header one line per tree in -e order and taxon in lookup-id order: tree taxon name\n"
+          "                  quartets concordant discordant eval_only ref_only unresolved concordance tree_concordance concordance_without\n"
+          "                  gain). quartets = C(L-1,3) for a tree of L taxa; the counts as in --per-tree, over the 4-sets that hold the\n"
+          "                  taxon; concordance = concordant / (concordant + discordant); tree_concordance = the tree's own (--per-tree's\n"
+          "                  figure); concordance_without = the tree's concordance over the 4-sets that do NOT hold the taxon; gain =\n"
+          "                  concordance_without - tree_concordance: how much the tree's agreement with the -r tree rises when this one\n"
+          "                  leaf is taken out of this one tree (one contaminated, paralogous or misaligned sequence). nan where a\n"
+          "                  denominator is 0; trees with fewer than four taxa write no line. The full file has (trees x taxa) lines.\n"
+          "                  Computed on the device behind the counting from the trees themselves, written batch by batch; one GPU that\n"
+          "                  counts (not with --gpus / --table-shards / --load-table), at most 1277 taxa; works with --per-tree,\n"
+          "                  --branch-trees, --bootstrap, --local-pp and beside every other output\n"
+          "   --tree-taxa-only NAMES  with --tree-taxa: write only the lines of the taxa listed in NAMES (one label per line, as for\n"
+          "                  --place-only)\n"
+          "   --tree-taxa-min-gain G  with --tree-taxa: write only the lines with gain >= G (lines whose gain is nan are dropped): the\n"
+          "                  list of rogue leaves\n";
 }
 
 // One option of the command line. `text` is how messages name it (its name unless a row says otherwise); the target is the member that
@@ -283,7 +304,15 @@ inline std::vector<Option> options(Args &a) {
         str("--tree-distances", &a.tree_distances), str("--per-taxon", &a.per_taxon), str("--place-taxa", &a.place_taxa), str("--place-only", &a.place_only),
         str("--taxon-pairs", &a.taxon_pairs), str("--taxon-pairs-only", &a.taxon_pairs_only), str("--drop-one", &a.drop_one), str("--drop-one-only", &a.drop_one_only),
         str("--branch-trees", &a.branch_trees), str("--bootstrap", &a.bootstrap), str("--local-pp", &a.local_pp), str("--place-clades", &a.place_clades),
-        str("--place-clades-only", &a.place_clades_only),
+        str("--place-clades-only", &a.place_clades_only), str("--tree-taxa", &a.tree_taxa), str("--tree-taxa-only", &a.tree_taxa_only),
+        checked("--tree-taxa-min-gain", nullptr, [&a](const char *v) -> std::string {
+            char *end = nullptr;
+            a.tree_taxa_min_gain = std::strtod(v, &end);
+            if (end == v || *end != '\0' || !std::isfinite(a.tree_taxa_min_gain))
+                return std::string("Couldn't read argument value from string '") + v + "' for arg --tree-taxa-min-gain (a number)";
+            a.tree_taxa_min_gain_given = true;
+            return "";
+        }),
         checked("--spill", nullptr, [&a](const char *v) -> std::string {
             const std::string sv = v;
             a.spill = sv == "host" ? ShardedTableQuartetScoreComputer::SPILL_HOST : sv == "recount" ? ShardedTableQuartetScoreComputer::SPILL_RECOUNT : ShardedTableQuartetScoreComputer::SPILL_AUTO;
@@ -378,7 +407,8 @@ inline std::vector<Output> output_registry(const Args &a) {
             {"--drop-one", a.drop_one, Needs::WHOLE_TABLE, "--drop-one-only", &a.drop_one_only},
             {"--branch-trees", a.branch_trees, Needs::COUNTED_TREES, nullptr, nullptr},
             {"--bootstrap", a.bootstrap, Needs::COUNTED_TREES, nullptr, nullptr},
-            {"--local-pp", a.local_pp, Needs::COUNTED_TREES, nullptr, nullptr}};
+            {"--local-pp", a.local_pp, Needs::COUNTED_TREES, nullptr, nullptr},
+            {"--tree-taxa", a.tree_taxa, Needs::COUNTED_TREES, "--tree-taxa-only", &a.tree_taxa_only}};
 }
 
 // Every output file of the command line with the option that names it; an option that was not given has an empty path
@@ -524,6 +554,18 @@ inline void check_tree_branches(const Args &a) {
     if (a.local_pp.empty() && a.local_pp_lambda_given) throw std::runtime_error("--local-pp-lambda needs --local-pp FILE");
     for (const char *flag : {"--branch-trees", "--bootstrap", "--local-pp"}) check_output(a, flag);
     if (!a.bootstrap.empty() && a.bootstrap_reps == 0) throw std::runtime_error("--bootstrap-reps must be at least 1");
+}
+
+// --tree-taxa: beyond check_taxon_list_output, its second companion needs it and the -r tree must be within the limit of the device's
+// plan (qs_tree_taxa_plan, host-only); leaves the lookup ids to write in a.tree_taxa_ids
+inline void check_tree_taxa(Args &a) {
+    if (a.tree_taxa.empty() && a.tree_taxa_min_gain_given) throw std::runtime_error("--tree-taxa-min-gain needs --tree-taxa FILE");
+    a.tree_taxa_ids = check_taxon_list_output(a, "--tree-taxa");
+    if (a.tree_taxa.empty()) return;
+    const size_t n = flatten_reference(read_reference(a)).names.size();
+    uint32_t plan[7];
+    if (qs_tree_taxa_plan((uint32_t)n, plan) != QS_OK)
+        throw std::runtime_error("--tree-taxa: the reference tree " + a.ref + " has " + std::to_string(n) + " taxa, the device plan supports at most " + std::to_string(plan[6]));
 }
 
 // --place-clades: beyond check_output, refused where a line of --place-clades-only names a label the -r tree lacks, the whole tree, a

@@ -1,6 +1,6 @@
 // cli_queries.hpp -- the device side of the CLI's outputs beyond the annotated tree: the one helper through which every output gets
-// its words from the count table (table_query), the writers above it, the two hook structs that work behind every batch's count
-// (PerTree, TreeBranches) and the rescoring of further trees from the same table (--also-ref, --without-taxa). The lines themselves
+// its words from the count table (table_query), the writers above it, the three hook structs that work behind every batch's count
+// (PerTree, TreeBranches, TreeTaxa) and the rescoring of further trees from the same table (--also-ref, --without-taxa). The lines themselves
 // come from cli_reports.hpp.
 #pragma once
 
@@ -215,6 +215,34 @@ struct TreeBranches {
         bootstrap_lines(f.f, shape, a.bootstrap_reps, totals.data());
         f.close();
     }
+};
+
+// --tree-taxa: qs_tree_taxon_agreement behind every batch's count into one device buffer of (trees of the batch) x n x 4 words; every
+// batch is waited for and downloaded and its lines are written as it comes, which this output pays for and no other: no buffer grows
+// with m, on the device or on the host
+struct TreeTaxa {
+    const Args &a;
+    RefFlat ref;
+    qs::DevBuf<int64_t> rows;
+    std::vector<int64_t> host;
+    std::vector<uint8_t> keep;
+    TsvFile lines;
+    TreeTaxa(const Args &args, const Tree &referenceTree, DeviceOptions &opt) : a(args), ref(flatten_reference(referenceTree)), keep(ref.names.size(), 0) {
+        opt.tree_branches = true;   // (the batches carry their node ranges)
+        for (uint16_t x : a.tree_taxa_ids) keep[x] = 1;
+        lines.open(a.tree_taxa, kTreeTaxaHeader);
+        add_after_count(opt, [this](qs_ctx *ctx, const qs_device_batch *db, size_t i0, const BatchFlat &b) {
+            const size_t k = b.n_trees, words = k * ref.names.size() * 4;
+            reserve_words("--tree-taxa", a.dev.device, rows, std::max<size_t>(1, words));
+            const qs_ref_tree rt = ref_view(ref);
+            if (qs_tree_taxon_agreement(ctx, &rt, db, rows.get()) != QS_OK || qs_sync(ctx) != QS_OK) throw std::runtime_error(std::string("--tree-taxa: ") + qs_last_error(ctx));
+            host.resize(words);
+            download_words("--tree-taxa", host.data(), rows.get(), words);
+            tree_taxa_lines(lines.f, ref, i0, k, b.leaf_off.data(), b.leaf_ids.data(), host.data(), keep, a.tree_taxa_min_gain_given ? &a.tree_taxa_min_gain : nullptr);
+            lines.check();
+        });
+    }
+    void write() { lines.close(); }
 };
 
 // --also-ref / --without-taxa, after the primary tree's output is written: one further tree scored from the same count table. The

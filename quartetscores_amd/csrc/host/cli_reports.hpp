@@ -259,6 +259,37 @@ inline void branch_trees_lines(std::ostream &os, const RefShape &S, size_t i0, s
         }
 }
 
+constexpr const char *kTreeTaxaHeader = "tree\ttaxon\tname\tquartets\tconcordant\tdiscordant\teval_only\tref_only\tunresolved\tconcordance\ttree_concordance\tconcordance_without\tgain\n";
+// --tree-taxa: the lines of the k trees of a batch, the first of which is tree i0, from their leaf lists and their k x n x 4 words
+// (concordant, discordant, resolved in the tree, resolved in -r, over the 4-sets of the tree that hold the taxon): per tree of at least
+// four taxa one line per taxon it holds, in id order; keep[x] = 0 leaves taxon x out, min_gain (where given) the lines below it and
+// those whose gain is nan
+inline void tree_taxa_lines(std::ostream &os, const RefFlat &ref, size_t i0, size_t k, const uint32_t *leaf_off, const uint16_t *leaf_ids, const int64_t *words,
+                            const std::vector<uint8_t> &keep, const double *min_gain) {
+    const size_t n = ref.names.size();
+    const auto ratio = [](int64_t num, int64_t den) { return den ? (double)num / (double)den : std::nan(""); };
+    std::vector<uint16_t> ids;
+    for (size_t t = 0; t < k; ++t) {
+        ids.assign(leaf_ids + leaf_off[t], leaf_ids + leaf_off[t + 1]);
+        const uint64_t L = ids.size();
+        if (L < 4) continue;
+        std::sort(ids.begin(), ids.end());
+        const int64_t *w = &words[t * n * 4];
+        int64_t conc = 0, disc = 0;   // of the whole tree: every 4-set is in four taxa's words
+        for (uint16_t x : ids) { conc += w[4 * x]; disc += w[4 * x + 1]; }
+        conc /= 4; disc /= 4;
+        const double tree_conc = ratio(conc, conc + disc);
+        const uint64_t quartets = (L - 1) * (L - 2) * (L - 3) / 6;
+        for (uint16_t x : ids) {
+            const int64_t c = w[4 * x], d = w[4 * x + 1], eo = w[4 * x + 2] - c - d, ro = w[4 * x + 3] - c - d;
+            const double without = ratio(conc - c, conc - c + disc - d), gain = without - tree_conc;
+            if (!keep[x] || (min_gain && !(gain >= *min_gain))) continue;
+            os << (i0 + t) << '\t' << x << '\t' << ref.names[x] << '\t' << quartets << '\t' << c << '\t' << d << '\t' << eo << '\t' << ro << '\t'
+               << ((int64_t)quartets - c - d - eo - ro) << '\t' << Fixed6(c, c + d) << '\t' << Fixed6(tree_conc) << '\t' << Fixed6(without) << '\t' << Fixed6(gain) << '\n';
+        }
+    }
+}
+
 constexpr const char *kBootstrapHeader = "node\tlo\thi\tqpic\tmean\tsd\tlo95\thi95\treps\n";
 // --bootstrap: one line per internode from the sums [1 + B][n_nodes][4]: row 0 unweighted, rows 1 .. B the replicates (B >= 1)
 inline void bootstrap_lines(std::ostream &os, const RefShape &S, size_t B, const int64_t *totals) {

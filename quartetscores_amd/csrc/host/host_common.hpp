@@ -37,7 +37,7 @@ struct DeviceOptions {
     bool trace = false;          // --trace: time stamps of the counting pipeline on stderr
     std::string per_tree;        // --per-tree FILE: batches carry their node ranges (qs_tree_agreement reads them)
     std::string tree_distances;  // --tree-distances FILE: likewise (qs_tree_pair_agreement reads them)
-    bool tree_branches = false;  // --branch-trees / --bootstrap: likewise (qs_tree_branch_support reads them)
+    bool tree_branches = false;  // --branch-trees / --bootstrap / --local-pp / --tree-taxa: likewise (qs_tree_branch_support, qs_tree_taxon_agreement read them)
     // called behind every batch's qs_count_batch (first tree of the batch, the flattened batch) and behind the final qs_sync;
     // several features share them through add_after_count / add_after_sync
     std::function<void(qs_ctx *, const qs_device_batch *, size_t, const BatchFlat &)> after_count;

@@ -1,8 +1,9 @@
 // qs_abi_query.hip -- what reads a finished table and is not the score: per-taxon, per-pair and per-branch-and-taxon support, taxon and clade placement, per-tree
-// agreement and per-tree support of every branch with its resampling (against a reference tree; these two read the trees, not a table),
+// agreement, per-tree-and-taxon agreement and per-tree support of every branch with its resampling (against a reference tree; these
+// read the trees, not a table),
 // the agreement of the evaluation trees with each other and the support of taxon groups (against none). Host code only; the kernels are
-// in qs_taxon.hip, qs_taxon_pairs.hip, qs_branch_taxa.hip, qs_place.hip, qs_place_clade.hip, qs_agree.hip, qs_tree_branch.hip,
-// qs_agree_pairs.hip and qs_groups.hip.
+// in qs_taxon.hip, qs_taxon_pairs.hip, qs_branch_taxa.hip, qs_place.hip, qs_place_clade.hip, qs_agree.hip, qs_tree_taxa.hip,
+// qs_tree_branch.hip, qs_agree_pairs.hip and qs_groups.hip.
 #include "qs_ctx.hpp"
 #include "qs_plan.hpp"
 
@@ -492,9 +493,9 @@ extern "C" int qs_placement_scores(const qs_ref_tree *ref, const int64_t *links_
 // Per-tree quartet agreement of a batch with the reference tree (qs_agree.hip). The reference's links come from its depth-first id
 // order: the children of an inner node split its id interval, ordered by their first id, and its parent link holds the other ids.
 // The reference has no per-tree output: this replaces nothing there.
-static int agree_ref_upload(qs_ctx *c, const qs_ref_tree *ref) {
-    if (!ref || !ref->parent || !ref->leaf_node) return fail(c, QS_ERR_ARG, "qs_tree_agreement: NULL reference arrays");
-    if (ref->n_taxa != c->n) return fail(c, QS_ERR_ARG, "qs_tree_agreement: the reference tree's n_taxa differs from the context");
+static int agree_ref_upload(qs_ctx *c, const qs_ref_tree *ref, const char *who = "qs_tree_agreement") {
+    if (!ref || !ref->parent || !ref->leaf_node) return fail(c, QS_ERR_ARG, std::string(who) + ": NULL reference arrays");
+    if (ref->n_taxa != c->n) return fail(c, QS_ERR_ARG, std::string(who) + ": the reference tree's n_taxa differs from the context");
     const uint32_t N = ref->n_nodes, n = ref->n_taxa;
     if (c->agree_off && c->agree_parent.size() == N && c->agree_leaf_node.size() == n &&
         memcmp(c->agree_parent.data(), ref->parent, (size_t)N * 4) == 0 && memcmp(c->agree_leaf_node.data(), ref->leaf_node, (size_t)n * 4) == 0)
@@ -548,6 +549,40 @@ extern "C" int qs_tree_agreement(qs_ctx *c, const qs_ref_tree *ref, const qs_dev
     if (d.ready) QS_HIP(c, hipStreamWaitEvent(c->stream, d.ready, 0));
     QS_HIP(c, launch_tree_agree(c->stream, d, c->n, d.max_tree_nodes, c->agree_off.get(), c->agree_bnd.get(), c->agree_par.get(), c->agree_n_u,
                                 reinterpret_cast<unsigned long long *>(dst_device)));
+    return QS_OK;   // asynchronous on the context's stream
+}
+
+// Host-only: the LDS plan of qs_tree_taxon_agreement for n_taxa (qs_tree_taxa.hip tree_taxa_plan) and the largest n_taxa it supports.
+extern "C" int qs_tree_taxa_plan(uint32_t n_taxa, uint32_t out[7]) {
+    if (!out) return fail(nullptr, QS_ERR_ARG, "qs_tree_taxa_plan: NULL argument");
+    TreeTaxaPlan p;
+    const bool ok = tree_taxa_plan(n_taxa, p);
+    const uint32_t words[7] = {p.W, p.cap, p.nb, p.flight, p.diff_bytes, p.lds_bytes, tree_taxa_max_taxa()};
+    std::copy(words, words + 7, out);
+    return ok ? QS_OK : fail(nullptr, QS_ERR_UNSUPPORTED, "qs_tree_taxa_plan: more than " + std::to_string(tree_taxa_max_taxa()) + " taxa");
+}
+
+// Per tree of a batch and per taxon the tree holds the quartet agreement with the reference tree over the 4-sets that hold the taxon
+// (qs_tree_taxa.hip). The reference's nodes are qs_tree_agreement's upload, cached per context. The reference has no output per tree
+// and none per taxon: this replaces nothing there.
+extern "C" int qs_tree_taxon_agreement(qs_ctx *c, const qs_ref_tree *ref, const qs_device_batch *b, int64_t *dst_device) {
+    if (!c) return QS_ERR_ARG;
+    const char *who = "qs_tree_taxon_agreement";
+    if (int rc = need_args(c, who, b && dst_device)) return rc;
+    if (c->d_lo != 0 || c->d_hi != c->n)
+        return fail(c, QS_ERR_UNSUPPORTED, "qs_tree_taxon_agreement: whole-table contexts only (no table shards)");
+    if (int rc = need_aligned(c, who, dst_device)) return rc;
+    TreeTaxaPlan plan;
+    if (!tree_taxa_plan(c->n, plan))
+        return fail(c, QS_ERR_UNSUPPORTED, "qs_tree_taxon_agreement: more than " + std::to_string(tree_taxa_max_taxa()) +
+                                               " taxa (the difference arrays of a workgroup live in LDS beside its bitmaps)");
+    if (int rc = agree_ref_upload(c, ref, who)) return rc;
+    const DeviceBatch &d = b->d;
+    if (d.n_trees && !d.node_off) return fail(c, QS_ERR_STATE, "qs_tree_taxon_agreement: the batch was uploaded without node ranges");
+    QS_HIP(c, hipSetDevice(c->device));
+    if (d.ready) QS_HIP(c, hipStreamWaitEvent(c->stream, d.ready, 0));
+    QS_HIP(c, launch_tree_taxa(c->stream, d, c->n, d.max_tree_nodes, c->agree_off.get(), c->agree_bnd.get(), c->agree_par.get(), c->agree_n_u,
+                               reinterpret_cast<unsigned long long *>(dst_device)));
     return QS_OK;   // asynchronous on the context's stream
 }
 

@@ -238,6 +238,17 @@ hipError_t launch_branch_resample(hipStream_t s, const long long *rows, uint32_t
                                   unsigned long long *dst);
 // ... and dst[node] += (trees with q1 + q2 + q3 > 0, sum over them of floor(q_i x 2^40 / (q1 + q2 + q3)), i = 1..3) (qs_branch_frequencies)
 hipError_t launch_branch_frequencies(hipStream_t s, const long long *rows, uint32_t n_trees, uint32_t n_nodes, unsigned long long *dst);
+// qs_tree_taxa.hip: per tree of the batch and taxon id the four words (concordant, discordant, resolved in the tree, resolved in the
+// reference) over the 4-sets of the tree's taxa that hold the taxon (qs_tree_taxon_agreement); the reference's nodes as for
+// launch_tree_agree. dst = n_trees rows of n x 4 words, overwritten
+constexpr int kTreeTaxaWords = 4;
+// LDS plan of such a launch for n taxa: W words per bitmap, `flight` links of a node with their two difference arrays (diff_bytes in
+// all) in LDS at once, the link bitmaps of one round (cap), the inner nodes of one workgroup (nb), the dynamic LDS of the launch
+struct TreeTaxaPlan { uint32_t W, cap, nb, flight, diff_bytes, lds_bytes; };
+bool tree_taxa_plan(uint32_t n, TreeTaxaPlan &p);   // false: more taxa than the plan supports (cap and lds_bytes are 0)
+uint32_t tree_taxa_max_taxa();                      // the largest n that tree_taxa_plan accepts
+hipError_t launch_tree_taxa(hipStream_t s, const DeviceBatch &b, uint32_t n, uint32_t max_tree_nodes, const uint32_t *ref_off,
+                            const uint16_t *ref_bnd, const uint8_t *ref_par, uint32_t n_u, unsigned long long *dst);
 // qs_place_clade.hip: link sums of the quartet placement of listed clades (qs_clade_placement); whole tables only. ref_lca, inner_node,
 // child, next as in PlaceDevice. tasks = d | group of 64 largest ids << 16 by d ascending, in the numbering of the ids OUTSIDE a clade:
 // the walk of the middle id n_outside - 1 - d (d = 1 ..: the longest walks first), so that the first clades[4 i + 3] entries are the walks

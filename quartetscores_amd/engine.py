@@ -61,6 +61,48 @@ def agreement_columns(counts, taxa) -> dict:
             "unresolved": quartets - both - eval_only - ref_only, "concordance": concordance}
 
 
+TREE_TAXA_COLUMNS = ("tree", "taxon", "name", "quartets", "concordant", "discordant", "eval_only", "ref_only", "unresolved", "concordance",
+                     "tree_concordance", "concordance_without", "gain")
+TREE_TAXA_FLOATS = ("concordance", "tree_concordance", "concordance_without", "gain")
+
+
+def tree_taxon_columns(names, words, batch: flatten.TreeBatch, first_tree=0, only=None, min_gain=None) -> dict:
+    """The columns of QuartetScores --tree-taxa from Context.tree_taxon_agreement: words (m, n, 4) int64 in AGREEMENT_FIELDS order,
+    batch = the flattened trees the words came from (it says which taxa a tree holds), first_tree = the index of words[0] among all
+    evaluation trees -> dict in TREE_TAXA_COLUMNS order with one entry per tree of at least four taxa and taxon it holds, by tree and
+    lookup id: quartets = C(L-1,3) for a tree of L taxa, eval_only / ref_only / unresolved as agreement_columns has them, concordance
+    = concordant / (concordant + discordant), tree_concordance = the same ratio over all 4-sets of the tree (the sums over its taxa
+    / 4), concordance_without = the ratio over the 4-sets of the tree that do not hold the taxon, gain = concordance_without -
+    tree_concordance; nan where a denominator is 0. only = lookup ids to keep (--tree-taxa-only); min_gain = keep the entries with
+    gain >= min_gain, which drops those whose gain is nan (--tree-taxa-min-gain). `name` is a list of str."""
+    n = len(names)
+    w = np.asarray(words, dtype=np.int64).reshape(-1, n, 4)
+    keep = None if only is None else set(int(x) for x in only)
+    out = {name: [] for name in TREE_TAXA_COLUMNS}
+    ratio = lambda num, den: num / den if den else math.nan
+    for t in range(len(w)):
+        ids = sorted(int(x) for x in batch.leaf_ids[int(batch.leaf_off[t]):int(batch.leaf_off[t + 1])])
+        L = len(ids)
+        if L < 4:
+            continue
+        quartets = (L - 1) * (L - 2) * (L - 3) // 6
+        conc_t, disc_t = int(w[t, :, 0].sum()) // 4, int(w[t, :, 1].sum()) // 4
+        tree_conc = ratio(conc_t, conc_t + disc_t)
+        for x in ids:
+            c, d, re, rr = (int(z) for z in w[t, x])
+            without = ratio(conc_t - c, conc_t - c + disc_t - d)
+            gain = without - tree_conc
+            if keep is not None and x not in keep:
+                continue
+            if min_gain is not None and not gain >= min_gain:
+                continue
+            eo, ro = re - c - d, rr - c - d
+            for name, val in zip(TREE_TAXA_COLUMNS, (first_tree + t, x, names[x], quartets, c, d, eo, ro, quartets - c - d - eo - ro, ratio(c, c + d),
+                                                     tree_conc, without, gain)):
+                out[name].append(val)
+    return {name: col if name == "name" else np.asarray(col, dtype=np.float64 if name in TREE_TAXA_FLOATS else np.int64) for name, col in out.items()}
+
+
 PAIR_FIELDS = ("concordant", "discordant", "resolved_row", "resolved_col", "shared")
 
 
@@ -364,6 +406,20 @@ def _group_labels(n_taxa, labels) -> np.ndarray:
     if a.size and (a.min() < 0 or a.max() > 255):
         raise QSError(_lib.QS_ERR_ARG, "group labels are 0..4")
     return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+TREE_TAXA_PLAN_FIELDS = ("W", "cap", "nb", "flight", "diff_bytes", "lds_bytes", "max_taxa")
+
+
+def tree_taxa_plan(n_taxa: int) -> dict:
+    """qs_tree_taxa_plan (host-only, no device): the LDS plan of qs_tree_taxon_agreement for n_taxa as a dict of TREE_TAXA_PLAN_FIELDS
+    and "supported" (False above max_taxa, where cap and lds_bytes are 0)."""
+    L = _lib.load()
+    out = np.zeros(7, dtype=np.uint32)
+    rc = L.qs_tree_taxa_plan(n_taxa, out.ctypes.data_as(C.c_void_p))
+    if rc not in (0, _lib.QS_ERR_UNSUPPORTED):
+        raise QSError(rc, L.qs_last_error(None).decode())
+    return {**{k: int(v) for k, v in zip(TREE_TAXA_PLAN_FIELDS, out)}, "supported": rc == 0}
 
 
 def group_check(n_taxa: int, labels) -> Tuple[np.ndarray, np.ndarray]:
@@ -718,6 +774,15 @@ class Context:
         n_trees = self._batch_trees[hb.value]
         words = n_trees * ref.n_nodes * 4
         return self._query(ref, words, lambda s, p: self.L.qs_tree_branch_support(self.h, s, hb, C.c_void_p(p))).reshape(n_trees, ref.n_nodes, 4)
+
+    def tree_taxon_agreement(self, ref: flatten.RefTree, hb) -> np.ndarray:
+        """qs_tree_taxon_agreement: per tree of the uploaded batch `hb` (uploaded with its node ranges) and taxon (lookup id) the four
+        words of AGREEMENT_FIELDS over the 4-sets of the tree's taxa that hold the taxon -> int64 (n_trees, n_taxa, 4); taxa the tree
+        lacks give zeros; tree_taxon_columns turns them into the CLI's columns. Allocates the device buffer, waits for the result
+        and downloads it."""
+        n_trees = self._batch_trees[hb.value]
+        words = n_trees * self.n * 4
+        return self._query(ref, words, lambda s, p: self.L.qs_tree_taxon_agreement(self.h, s, hb, C.c_void_p(p))).reshape(n_trees, self.n, 4)
 
     def branch_resample(self, rows, weights, out=None) -> np.ndarray:
         """qs_branch_resample: rows int64 (m, n_nodes, 4) as tree_branch_support returns them, weights (B, m) unsigned 32-bit ->

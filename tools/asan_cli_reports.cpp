@@ -142,6 +142,31 @@ static void drive(const std::string &newick, Expect want) {
     per_tree_lines(tree, 4, taxa, counts);
     per_tree_lines(tree, 0, nullptr, nullptr);
     CHECK(columns_match(kPerTreeHeader, tree.str()) == 4);
+
+    // --tree-taxa: a batch of four trees -- all taxa, three taxa (no line), every second taxon in any order, none -- with every taxon
+    // kept, one kept and under a threshold no gain reaches
+    std::vector<uint32_t> leaf_off{0};
+    std::vector<uint16_t> leaf_ids;
+    for (size_t x = 0; x < n; ++x) leaf_ids.push_back((uint16_t)x);
+    leaf_off.push_back((uint32_t)leaf_ids.size());
+    for (size_t x = 0; x < 3; ++x) leaf_ids.push_back((uint16_t)(n - 1 - x));
+    leaf_off.push_back((uint32_t)leaf_ids.size());
+    for (size_t x = n; x-- > 0;) if (x % 2 == 0) leaf_ids.push_back((uint16_t)x);
+    const size_t half = leaf_ids.size() - leaf_off.back();
+    leaf_off.push_back((uint32_t)leaf_ids.size());
+    leaf_off.push_back((uint32_t)leaf_ids.size());
+    std::vector<int64_t> tw(4 * n * 4);
+    for (size_t i = 0; i < tw.size(); i += 4) { tw[i] = (int64_t)(mix(i) % 3) * 4; tw[i + 1] = (int64_t)(mix(i + 1) % 2) * 4; tw[i + 2] = tw[i] + tw[i + 1] + 1; tw[i + 3] = tw[i] + tw[i + 1]; }
+    std::vector<uint8_t> keep_all(n, 1), keep_one(n, 0);
+    keep_one[0] = 1;
+    const double never = 2.0;
+    std::ostringstream tt, one, nothing;
+    tree_taxa_lines(tt, ref, 7, 4, leaf_off.data(), leaf_ids.data(), tw.data(), keep_all, nullptr);
+    tree_taxa_lines(one, ref, 7, 4, leaf_off.data(), leaf_ids.data(), tw.data(), keep_one, nullptr);
+    tree_taxa_lines(nothing, ref, 7, 4, leaf_off.data(), leaf_ids.data(), tw.data(), keep_all, &never);
+    tree_taxa_lines(nothing, ref, 0, 0, leaf_off.data(), nullptr, nullptr, keep_all, nullptr);
+    CHECK(columns_match(kTreeTaxaHeader, tt.str()) == n + (half >= 4 ? half : 0) && columns_match(kTreeTaxaHeader, one.str()) == 1 + (half >= 4) && nothing.str().empty());
+    CHECK(tt.str().rfind("7\t0\t", 0) == 0 && (half < 4 || tt.str().find("\n9\t0\t") != std::string::npos) && tt.str().find("\n8\t") == std::string::npos);
 }
 
 // Lines worked out by hand on (((t0,t1),t2),t3,t4,(t5,t6,t7)): nodes in preorder 0 = root, 1 = ((t0,t1),t2), 2 = (t0,t1), 3 4 5 = t0 t1
@@ -180,6 +205,19 @@ static void fixed_lines() {
     CHECK(drop.str() == "2\tt2\t1\t0\t3\t1\t5\t5\t0\t0\t1.000000\tnan\tnan\n"
                         "2\tt2\t2\t0\t2\t1\t2\t2\t0\t0\t0.369070\t-0.488140\t-0.857211\n"
                         "2\tt2\t8\t5\t8\t3\t0\t0\t0\t0\t1.000000\t1.000000\t0.000000\n");
+    // --tree-taxa of the tree ((((B,C),D),E),(A,F)) against (((((A,B),C),D),E),F): A holds the 10 discordant 4-sets, every other taxon 4
+    // concordant and 6 discordant ones; the tree has 5 and 10, without A 5 of 5, without another taxon 1 of 5
+    const RefFlat six = flat("(((((A,B),C),D),E),F);");
+    const uint32_t leaf_off[2] = {0, 6};
+    const uint16_t leaf_ids[6] = {1, 2, 3, 4, 0, 5};
+    std::vector<int64_t> w{0, 10, 10, 10};
+    for (int x = 1; x < 6; ++x) w.insert(w.end(), {4, 6, 10, 10});
+    std::ostringstream all, rogue;
+    const double G = 0.5;
+    tree_taxa_lines(all, six, 3, 1, leaf_off, leaf_ids, w.data(), std::vector<uint8_t>(6, 1), nullptr);
+    tree_taxa_lines(rogue, six, 3, 1, leaf_off, leaf_ids, w.data(), std::vector<uint8_t>(6, 1), &G);
+    CHECK(rogue.str() == "3\t0\tA\t10\t0\t10\t0\t0\t0\t0.000000\t0.333333\t1.000000\t0.666667\n");
+    CHECK(all.str().rfind(rogue.str(), 0) == 0 && all.str().find("3\t1\tB\t10\t4\t6\t0\t0\t0\t0.400000\t0.333333\t0.200000\t-0.133333\n") == rogue.str().size());
 }
 
 static void formats_and_sink() {
