@@ -16,7 +16,8 @@
  *                                 (QuartetCounterLookup.hpp:299-318)
  *   qs_table_*                    QuartetLookupTable<T> storage (quartet_lookup_table.hpp:19-228);
  *                                 qs_table_remap replaces nothing (the reference recounts per reference tree), nor does
- *                                 qs_table_restrict (the reference recounts per taxon set)
+ *                                 qs_table_restrict (the reference recounts per taxon set), nor qs_table_collapse (the
+ *                                 reference maps no individuals to species: its TaxonMapper.hpp is dead code)
  *   qs_tree_agreement             replaces nothing in the reference (it reports no per-tree agreement)
  *   qs_tree_taxon_agreement /     replace nothing in the reference (it has no output per tree and none per taxon)
  *   qs_tree_taxa_plan
@@ -311,6 +312,23 @@ int qs_table_remap(qs_ctx *dst, const qs_ctx *src, const uint16_t *src_id_of);
  * taxa still counts towards it; scores never depend on it). The reference rejects an evaluation leaf it does not know and recounts per
  * run: this replaces nothing there. */
 int qs_table_restrict(qs_ctx *dst, const qs_ctx *src, const uint16_t *src_id_of);
+
+/* The table of `src`, counted over INDIVIDUALS (several leaves per species in the evaluation trees), summed into `dst`'s table over the
+ * SPECIES that own them: dst has n_dst = its n_taxa species, src n_src >= n_dst individuals, and species i owns the consecutive source
+ * ids [first_id[i], first_id[i + 1]) -- first_id (host) has n_dst + 1 entries, strictly increasing from first_id[0] = 0 to
+ * first_id[n_dst] = n_src (not increasing, an empty group, wrong ends or n_dst > n_src: QS_ERR_ARG). For species S0 < S1 < S2 < S3 and
+ * slot k, dst[rank4(S0,S1,S2,S3)][k] = the sum of src[rank4(a,b,c,d)][k] over a in S0, b in S1, c in S2, d in S3: the topology a tree
+ * displays for four individuals does not depend on its other leaves, so this is the multi-individual quartet count (Rabiee, Sayyari &
+ * Mirarab 2019); the groups are consecutive and in order, so the slots carry over unchanged. Source tuples with two individuals of one
+ * species are never read. With all groups of size 1 the result is a copy. Sums are exact in 64 bits; a cell beyond dst's cell width
+ * raises QS_ERR_OVERFLOW at the next qs_sync (dst's contents are unspecified then). Everything else as qs_table_restrict: whole-table
+ * contexts on the same device (a table shard: QS_ERR_UNSUPPORTED); both need a table (QS_ERR_STATE); cells 32 -> 32, 16 -> 16 or
+ * 16 -> 32 (narrowing: QS_ERR_ARG); a refused call leaves dst untouched. Waits for src's stream, then runs asynchronously on dst's
+ * stream; dst's previous contents are overwritten and its trees-counted becomes src's. A cell of dst can exceed trees-counted
+ * afterwards; scores and the whole-table queries do not depend on that number (the call itself sizes the log table of the device QIC
+ * and the partial sums of the queries for (largest source count) x (the four largest groups), also for a table re-indexed out of dst).
+ * The reference maps no individuals to species: this replaces nothing there. */
+int qs_table_collapse(qs_ctx *dst, const qs_ctx *src, const uint16_t *first_id);
 
 /* Writes the u32 table as a u16 table (same [rank][3] layout, 2 bytes per cell, padded to a whole 32-bit word)
  * into caller-owned device memory: the wire format for the multi-GPU all-reduce while all totals stay below 2^16

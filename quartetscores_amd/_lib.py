@@ -44,7 +44,7 @@ EXPORTS = [
     "qs_table_remap", "qs_tree_agreement", "qs_taxon_support", "qs_table_restrict", "qs_taxon_placement", "qs_placement_scores", "qs_clade_placement",
     "qs_last_count_split", "qs_fix_overlap_plan", "qs_group_check", "qs_group_support", "qs_tree_pair_agreement", "qs_taxon_pair_support",
     "qs_branch_taxon_support", "qs_tree_branch_support", "qs_branch_resample", "qs_branch_frequencies",
-    "qs_tree_taxon_agreement", "qs_tree_taxa_plan",
+    "qs_tree_taxon_agreement", "qs_tree_taxa_plan", "qs_table_collapse",
 ]
 
 
@@ -116,6 +116,8 @@ def load():
     L.qs_table_remap.argtypes = [vp, vp, vp]
     L.qs_table_restrict.restype = i32
     L.qs_table_restrict.argtypes = [vp, vp, vp]
+    L.qs_table_collapse.restype = i32
+    L.qs_table_collapse.argtypes = [vp, vp, vp]
     L.qs_tree_agreement.restype = i32
     L.qs_tree_agreement.argtypes = [vp, vp, vp, vp]
     L.qs_tree_pair_agreement.restype = i32

@@ -58,6 +58,16 @@ inline std::shared_ptr<const EvalFile> loadEvalFile(const std::string &evalTrees
 // Count the number of evaluation trees: one scan for top-level ';' (ingest.hpp).
 inline size_t countEvalTrees(const std::string &evalTreesPath) { return loadEvalFile(evalTreesPath)->spans.size(); }
 
+// --species-map: the species' table keeps the individuals' cell width `bits` while m x (the four largest groups) fits 16 bits
+inline uint32_t species_table_bits(uint32_t bits, size_t m, const SpeciesLayout &sp) { return bits == 16 && (uint64_t)m * sp.top4 < 65536 ? 16u : 32u; }
+// --load-table: the cell width the size of the file implies for n taxa (a --species-map run saves 32-bit cells for few trees); 0 = neither
+inline uint32_t saved_table_bits(const std::string &path, size_t n) {
+    std::ifstream f(path, std::ios::binary | std::ios::ate);
+    if (!f) throw std::runtime_error("cannot open " + path);
+    const uint64_t size = (uint64_t)f.tellg(), cells = c4(n) * 3;
+    return size == cells * 2 ? 16u : size == cells * 4 ? 32u : 0u;
+}
+
 template <typename CINT> class QuartetCounterLookup {
 public:
     QuartetCounterLookup(Tree const &refTree, const std::string &evalTreesPath, size_t m, bool savemem,
@@ -68,14 +78,16 @@ public:
         // passes over the table, hidden under the parsing; 512 taxa x 10000 trees at -t 1: 0.66 s with 8192-tree batches, 0.55 s
         // with small ones). From 4 threads on the device is the bottleneck and every batch is one full panel slice.
         if (threads_of(opt) < 4) opt.batch_trees = std::min<size_t>(opt.batch_trees, 2048);
-        const uint32_t bits = sizeof(CINT) <= 2 ? 16 : 32;
+        // (a --load-table file says its own width; with --species-map the individuals are counted at m's width, collapse_species widens)
+        const uint32_t bits = !opt.load_table.empty() && opt.table_bits ? opt.table_bits : sizeof(CINT) <= 2 ? 16 : 32;
         // HIP initialisation + table allocation (~0.1 s) run on a helper thread while this one reads the evaluation
         // file and flattens the first batch
         int rc_create = QS_OK, rc_alloc = QS_OK;
         std::string create_err;
         trace_mark(opt, "counter: start (GPU set-up thread + first batch on the host threads)");
         std::thread gpu_init([&] {
-            rc_create = qs_create(&ctx_, (uint32_t)ref_.names.size(), bits, QS_FLAG_NONE, opt.device, nullptr, 0, 0);
+            // (--species-map: the table of the individuals first; collapse_species puts the species' table in its place)
+            rc_create = qs_create(&ctx_, (uint32_t)(opt.species ? opt.species->names.size() : ref_.names.size()), bits, QS_FLAG_NONE, opt.device, nullptr, 0, 0);
             if (rc_create != QS_OK) { create_err = qs_last_error(nullptr); return; }
             trace_mark(opt, "gpu thread: context created (HIP initialised)");
             rc_alloc = qs_table_alloc(ctx_);
@@ -151,7 +163,30 @@ private:
     }
     BatchFlat flatten_batch(const EvalFile &ef, size_t i0, const DeviceOptions &opt) const {
         const size_t i1 = batch_end(i0, ef.spans.size(), opt);
-        return flatten_parallel(ef.text, ef.spans, i0, i1, ref_.name_to_id, threads_of(opt), wants_ranges(opt));
+        return flatten_parallel(ef.text, ef.spans, i0, i1, opt.species ? opt.species->name_to_id : ref_.name_to_id, threads_of(opt), wants_ranges(opt));
+    }
+    // --species-map: the counted table of the individuals summed into a context of the species (qs_table_collapse), which takes this
+    // one's place; the individuals' table is freed. 16-bit cells while m x (the four largest groups) stays below 65536, else 32.
+    void collapse_species(size_t m, const DeviceOptions &opt) {
+        const SpeciesLayout &sp = *opt.species;
+        const uint32_t bits = opt.table_bits ? opt.table_bits : species_table_bits(sizeof(CINT) <= 2 ? 16 : 32, m, sp);
+        qs_ctx *species = nullptr;
+        if (qs_create(&species, (uint32_t)ref_.names.size(), bits, QS_FLAG_NONE, opt.device, nullptr, 0, 0) != QS_OK) throw std::runtime_error(qs_last_error(nullptr));
+        try {
+            if (qs_table_alloc(species) != QS_OK) throw std::runtime_error(std::string("--species-map: ") + qs_last_error(species));
+            const auto begin = std::chrono::steady_clock::now();
+            if (qs_table_collapse(species, ctx_, sp.first_id.data()) != QS_OK || qs_sync(species) != QS_OK)
+                throw std::runtime_error(std::string("--species-map: ") + qs_last_error(species));
+            const auto us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - begin).count();
+            std::cout << "Collapsed the count table in " << us << " microseconds.\n";
+            if (opt.trace)
+                std::fprintf(stderr, "[trace] qs_table_collapse: %zu individuals -> %zu species, %d-bit cells, %.3f ms\n", sp.names.size(), ref_.names.size(), (int)bits, us / 1000.0);
+        } catch (...) {
+            qs_destroy(species);
+            throw;
+        }
+        qs_destroy(ctx_);   // (the individuals' table goes)
+        ctx_ = species;
     }
     void countQuartets(const std::shared_ptr<const EvalFile> &ef, BatchFlat first, size_t m, const DeviceOptions &opt) {
         if (!opt.load_table.empty()) { // resume from a saved table instead of counting
@@ -184,8 +219,9 @@ private:
                     progress++;
                 }
             }
-            {   // the scoring set-up (reference tree on the device, round tables, accumulators, candidate log) while the device
-                // still counts: this thread would only wait. Optional -- a failure here shows up again in qs_score.
+            if (!opt.species) {   // the scoring set-up (reference tree on the device, round tables, accumulators, candidate log) while the
+                // device still counts: this thread would only wait. Optional -- a failure here shows up again in qs_score.
+                // (--species-map: this context holds the individuals; the species' context is scored)
                 const qs_ref_tree rt = ref_view(ref_);
                 (void)qs_score_prepare(ctx_, &rt, (uint64_t)m);
                 trace_mark(opt, "host: scoring set-up done behind the enqueued counts");
@@ -198,6 +234,7 @@ private:
             throw;
         }
         queue.release();
+        if (opt.species) collapse_species(m, opt);
         if (!opt.save_table.empty()) {
             std::string bytes(qs_table_bytes(ctx_), '\0');
             if (qs_table_download(ctx_, &bytes[0], bytes.size()) != QS_OK) fail();

@@ -23,6 +23,8 @@
 // table (qs_group_check, qs_group_support).
 // --taxon-pairs FILE [--taxon-pairs-only NAMES] writes, per pair of taxa of the -r tree, how often the evaluation trees put the two
 // together against the other two taxa of a 4-set, beside what the -r tree shows for the same 4-sets (qs_taxon_pair_support).
+// --species-map FILE takes evaluation trees with several individuals per species of the -r tree: they are counted under the individuals'
+// ids and the table is summed into the species' table on the device (qs_table_collapse); everything after works on the species.
 // --drop-one FILE [--drop-one-only NAMES] writes, per taxon and internode of the -r tree, the internode's QP-IC without that taxon, from
 // the same count table (qs_branch_taxon_support).
 //
@@ -88,9 +90,18 @@ EdgeScores run_sharded(const Tree &referenceTree, const Args &a, size_t m, uint3
 
 template <typename CINT>
 EdgeScores run(const Tree &referenceTree, const Args &a, size_t m) {
-    const uint32_t bits = sizeof(CINT) <= 2 ? 16u : 32u;
+    uint32_t bits = sizeof(CINT) <= 2 ? 16u : 32u;
     size_t n = 0;
     for (size_t v = 0; v < referenceTree.node_count(); ++v) n += referenceTree.is_leaf(v);
+    // The width of the table that is scored, and with it of the --also-ref / --without-taxa tables cut from it, is not always m's: the
+    // species' table of --species-map is widened where m x (the four largest groups) leaves 16 bits, and a table saved by such a run
+    // is loaded at the width its size implies (single-GPU route only; the others refuse both options)
+    uint32_t scored_bits = 0;
+    if (a.dev.species) scored_bits = species_table_bits(bits, m, *a.dev.species);
+    else if (!a.dev.load_table.empty() && a.gpus == 0 && a.table_shards < 0) {
+        scored_bits = saved_table_bits(a.dev.load_table, n);
+        if (!scored_bits) throw std::runtime_error("--load-table: size does not match this reference tree (neither its 16-bit nor its 32-bit table)");
+    }
     const uint64_t bytes = c4(n) * 3 * (bits / 8);
     const int gpus = std::max(1, a.gpus);
     if (a.table_shards >= 0 || a.gpus > 0) {
@@ -123,11 +134,13 @@ EdgeScores run(const Tree &referenceTree, const Args &a, size_t m) {
     if (a.gpus > 0) return run_multi(referenceTree, a, m, bits);
     // --also-ref: the second table is allocated before anything is counted, so that a table that fits once but not twice is
     // reported now and not after the counting
+    if (scored_bits) bits = scored_bits;   // (from here on: the tables re-indexed out of the scored one)
+    const uint64_t scored_bytes = c4(n) * 3 * (bits / 8);
     qs_ctx *also_table = nullptr;
     struct AlsoTable { qs_ctx *&c; bool keep; ~AlsoTable() { if (!keep) qs_destroy(c); } } also_guard{also_table, !a.clean_exit};
     if (!a.also.empty()) {
-        if (ShardedTableQuartetScoreComputer::shards_needed(bytes, a.dev.device) > 1)
-            throw std::runtime_error("--also-ref needs the whole count table (" + std::to_string(bytes) + " bytes) on one GPU");
+        if (ShardedTableQuartetScoreComputer::shards_needed(scored_bytes, a.dev.device) > 1)
+            throw std::runtime_error("--also-ref needs the whole count table (" + std::to_string(scored_bytes) + " bytes) on one GPU");
         if (qs_create(&also_table, (uint32_t)n, bits, QS_FLAG_NONE, a.dev.device, nullptr, 0, 0) != QS_OK) throw std::runtime_error(qs_last_error(nullptr));
         if (qs_table_alloc(also_table) != QS_OK) throw std::runtime_error(std::string("--also-ref: ") + qs_last_error(also_table));
         trace_mark(a.dev, "main: --also-ref table allocated");
@@ -144,12 +157,13 @@ EdgeScores run(const Tree &referenceTree, const Args &a, size_t m) {
         size_t freeb = 0, total = 0;
         hip_ok(hipSetDevice(a.dev.device), "--without-taxa: hipSetDevice");
         hip_ok(hipMemGetInfo(&freeb, &total), "--without-taxa: hipMemGetInfo");
-        if (need + bytes + (64u << 20) > freeb || without_table.reserve(need, nullptr) != hipSuccess)   // (the -r tree's table comes on top)
+        if (need + scored_bytes + (64u << 20) > freeb || without_table.reserve(need, nullptr) != hipSuccess)   // (the -r tree's table comes on top)
             throw std::runtime_error("--without-taxa: Insufficient memory!");
         trace_mark(a.dev, "main: --without-taxa table allocated");
     }
     // the outputs that work behind every batch's count hook themselves into the options, in this order
     DeviceOptions dev = a.dev;
+    dev.table_bits = scored_bits;
     std::unique_ptr<PerTree> per_tree;
     if (!a.per_tree.empty()) per_tree.reset(new PerTree(a, m, referenceTree, dev));
     std::unique_ptr<TreeBranches> tree_branches;
@@ -208,6 +222,7 @@ int main(int argc, char *argv[]) {
         return 1;
     }
     try {   // (the order decides which message a command line sees that trips two checks)
+        check_species_map(a);
         check_also_refs(a);
         check_without_taxa(a);
         check_output(a, "--per-tree");

@@ -85,6 +85,7 @@ struct Args {
     std::vector<uint8_t> group_labels, group_kind;
     std::vector<AlsoRef> also;
     std::vector<WithoutTaxa> without;
+    std::string species_map;   // --species-map FILE: the evaluation trees' leaves are individuals of the species of -r (check_species_map -> dev.species)
     size_t threads = 0;
     bool verbose = false, savemem = false, raw_rank_order = false, fail_fast = false, clean_exit = false, fast_exit = false;
     int table_shards = -1;   // -1 = off (the whole table on the device); 0 = as many as the device's free memory asks for; K = K shards, one after the other (table_shards.hpp)
@@ -141,6 +142,17 @@ inline void usage(std::ostream &os) {
           "                  down to the kept taxa instead of pruning every tree and counting again. At least four taxa must remain; one\n"
           "                  GPU with the whole table (not with --gpus / --table-shards); works with --load-table, --per-tree, --per-taxon\n"
           "                  (both still the full -r tree) and beside --also-ref (whose trees are not pruned)\n"
+          "   --species-map FILE  the evaluation trees hold several individuals (alleles, samples) per species and the -r tree one leaf\n"
+          "                  per species: FILE maps them in ASTRAL's format, one line per species, species:ind1,ind2,... (blank lines and\n"
+          "                  lines that start with # are skipped, surrounding blanks trimmed; a leaf of -r without a line is a species\n"
+          "                  with one individual of the same name). The trees are counted under the individuals' ids and the count table\n"
+          "                  is summed into the species' table on the device: a 4-set of species counts every choice of one individual\n"
+          "                  per species (the multi-individual quartet score). Scores, -q and every output that reads the count table\n"
+          "                  (--per-taxon, --place-taxa, --place-clades, --test-groups, --taxon-pairs, --drop-one, --without-taxa,\n"
+          "                  --also-ref) then work on the species; --save-table writes the species' table, which a later --load-table\n"
+          "                  run WITHOUT the map resumes on. At most 4096 individuals, at least 4 species; one GPU that counts (not\n"
+          "                  with --gpus / --table-shards / --load-table) and not with the outputs computed from the trees themselves\n"
+          "                  (--per-tree, --tree-distances, --branch-trees, --bootstrap, --local-pp, --tree-taxa)\n"
           "   --per-tree F   write the quartet agreement of every evaluation tree with the -r tree to F (TSV, one line per tree in\n"
           "                  -e order after a header: tree taxa quartets concordant discordant eval_only ref_only unresolved\n"
           "                  concordance); computed on the device behind the counting; one GPU that counts (not with --gpus /\n"
@@ -305,6 +317,7 @@ inline std::vector<Option> options(Args &a) {
         str("--taxon-pairs", &a.taxon_pairs), str("--taxon-pairs-only", &a.taxon_pairs_only), str("--drop-one", &a.drop_one), str("--drop-one-only", &a.drop_one_only),
         str("--branch-trees", &a.branch_trees), str("--bootstrap", &a.bootstrap), str("--local-pp", &a.local_pp), str("--place-clades", &a.place_clades),
         str("--place-clades-only", &a.place_clades_only), str("--tree-taxa", &a.tree_taxa), str("--tree-taxa-only", &a.tree_taxa_only),
+        str("--species-map", &a.species_map),
         checked("--tree-taxa-min-gain", nullptr, [&a](const char *v) -> std::string {
             char *end = nullptr;
             a.tree_taxa_min_gain = std::strtod(v, &end);
@@ -439,6 +452,8 @@ inline bool check_output(const Args &a, const std::string &flag) {
     if (o.needs == Needs::WHOLE_TABLE && split) throw std::runtime_error(flag + " needs the whole count table on one GPU: omit --gpus / --table-shards");
     if (o.needs == Needs::COUNTED_TREES && (split || !a.dev.load_table.empty()))
         throw std::runtime_error(flag + " needs the evaluation trees counted on one GPU: omit --gpus / --table-shards / --load-table");
+    if (o.needs == Needs::COUNTED_TREES && !a.species_map.empty())
+        throw std::runtime_error(flag + " compares every evaluation tree with the -r tree leaf by leaf, and with --species-map the trees hold individuals, the -r tree species: omit one of the two");
     for (const auto &e : output_files(a))
         if (e.first != flag && e.second == o.path) throw std::runtime_error(flag + ": " + o.path + " is also another output file");
     if (std::ifstream(o.path).good()) throw std::runtime_error(flag + ": the output file " + o.path + " already exists");
@@ -452,6 +467,71 @@ inline Tree read_reference(const Args &a) {
     NewickReader rr(text);
     if (!rr.next(primary)) throw std::runtime_error("empty reference tree file");
     return primary;
+}
+
+// --species-map FILE: everything before the device is touched -- the routes that cannot take it are refused, the file parses against
+// the leaves of -r (each message names the offending label), and the layout of the individuals is left in a.dev.species
+inline void check_species_map(Args &a) {
+    if (a.species_map.empty()) return;
+    const std::string what = "--species-map " + a.species_map + ": ";
+    if (!a.dev.load_table.empty())
+        throw std::runtime_error("--species-map does not work with --load-table: a saved table holds no names, and the table a --species-map run saves is the species' table already (load it without the map)");
+    if (a.gpus > 0 || a.table_shards >= 0)
+        throw std::runtime_error("--species-map needs the individuals' whole count table on one GPU: omit --gpus / --table-shards");
+    const RefFlat rf = flatten_reference(read_reference(a));
+    auto trimmed = [](const std::string &t) {
+        const size_t b = t.find_first_not_of(" \t\r"), e = t.find_last_not_of(" \t\r");
+        return b == std::string::npos ? std::string() : t.substr(b, e - b + 1);
+    };
+    std::map<std::string, std::vector<std::string>> listed;   // species -> its individuals in file order
+    std::map<std::string, std::string> owner;                 // individual -> species
+    std::istringstream lines(slurp(a.species_map));
+    size_t line_no = 0;
+    for (std::string line; std::getline(lines, line);) {
+        ++line_no;
+        const std::string at = what + "line " + std::to_string(line_no) + ": ";
+        line = trimmed(line);
+        if (line.empty() || line[0] == '#') continue;
+        const size_t colon = line.find(':');
+        if (colon == std::string::npos) throw std::runtime_error(at + "no ':' in '" + line + "'");
+        const std::string species = trimmed(line.substr(0, colon));
+        if (species.empty()) throw std::runtime_error(at + "no species name in front of ':'");
+        if (!rf.name_to_id.count(species)) throw std::runtime_error(at + "the species '" + species + "' is not a leaf of the reference tree " + a.ref);
+        if (listed.count(species)) throw std::runtime_error(at + "the species '" + species + "' has two lines");
+        std::vector<std::string> &inds = listed[species];
+        const std::string rest = line.substr(colon + 1);
+        if (trimmed(rest).empty()) throw std::runtime_error(at + "the species '" + species + "' has an empty individual list");
+        for (size_t from = 0;;) {
+            const size_t comma = rest.find(',', from);
+            const std::string ind = trimmed(rest.substr(from, comma == std::string::npos ? std::string::npos : comma - from));
+            if (ind.empty()) throw std::runtime_error(at + "the species '" + species + "' lists an empty individual name");
+            const auto ins = owner.emplace(ind, species);
+            if (!ins.second) throw std::runtime_error(at + "the individual '" + ind + "' is listed twice (species '" + ins.first->second + "' and '" + species + "')");
+            inds.push_back(ind);
+            if (comma == std::string::npos) break;
+            from = comma + 1;
+        }
+    }
+    for (const auto &kv : owner)
+        if (rf.name_to_id.count(kv.first) && !listed.count(kv.first))
+            throw std::runtime_error(what + "the individual '" + kv.first + "' of species '" + kv.second + "' has the name of the unlisted species '" + kv.first + "'");
+    if (rf.names.size() < 4) throw std::runtime_error(what + "fewer than 4 species (" + std::to_string(rf.names.size()) + ") in the reference tree " + a.ref);
+    auto sp = std::make_shared<SpeciesLayout>();
+    std::vector<uint64_t> sizes;
+    sp->first_id.push_back(0);
+    for (const std::string &species : rf.names) {
+        const auto it = listed.find(species);
+        if (it == listed.end()) sp->names.push_back(species);
+        else sp->names.insert(sp->names.end(), it->second.begin(), it->second.end());
+        if (sp->names.size() > 4096)
+            throw std::runtime_error(what + "more than 4096 individuals in all (reached at the species '" + species + "')");
+        sizes.push_back(sp->names.size() - sp->first_id.back());
+        sp->first_id.push_back((uint16_t)sp->names.size());
+    }
+    for (size_t i = 0; i < sp->names.size(); ++i) sp->name_to_id[sp->names[i]] = (uint32_t)i;
+    std::sort(sizes.begin(), sizes.end());
+    for (size_t k = sizes.size() - 4; k < sizes.size(); ++k) sp->top4 *= sizes[k];
+    a.dev.species = sp;
 }
 
 // A NAMES file (--without-taxa, --place-only): one label per line, as parsed and unquoted; surrounding blanks go, blank lines are skipped,

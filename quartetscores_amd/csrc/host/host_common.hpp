@@ -11,11 +11,21 @@
 #include <cstdint>
 #include <cstdio>
 #include <functional>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 namespace qsh {
+
+// --species-map: the individuals behind the species of the -r tree in counting order -- species in lookup-id order, individuals in
+// map order within a species; species i owns the counting ids [first_id[i], first_id[i + 1]) (qs_table_collapse)
+struct SpeciesLayout {
+    std::vector<std::string> names;
+    std::unordered_map<std::string, uint32_t> name_to_id;
+    std::vector<uint16_t> first_id;
+    uint64_t top4 = 1;   // the product of the four largest groups: a collapsed cell is at most m times this
+};
 
 struct DeviceOptions {
     int device = 0;
@@ -35,6 +45,9 @@ struct DeviceOptions {
     bool comm_overlap = false;   // --gpus N, rccl: count while ncclCommInitAll runs (false: the first launch waits for the communicators)
     std::string load_table, save_table; // count-table persistence
     bool trace = false;          // --trace: time stamps of the counting pipeline on stderr
+    std::shared_ptr<const SpeciesLayout> species;   // --species-map FILE: count under the individuals' ids, then collapse into the species' table
+    uint32_t table_bits = 0;     // cell width of the table the run scores where the number of trees does not decide it (0 = it does): the species'
+                                 // table of --species-map (m x the four largest groups), a --load-table file (its size)
     std::string per_tree;        // --per-tree FILE: batches carry their node ranges (qs_tree_agreement reads them)
     std::string tree_distances;  // --tree-distances FILE: likewise (qs_tree_pair_agreement reads them)
     bool tree_branches = false;  // --branch-trees / --bootstrap / --local-pp / --tree-taxa: likewise (qs_tree_branch_support, qs_tree_taxon_agreement read them)

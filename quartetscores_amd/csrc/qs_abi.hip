@@ -271,7 +271,7 @@ extern "C" uint64_t qs_trees_counted(const qs_ctx *c) { return c ? c->trees_coun
 // the largest count a cell of the context's table may hold: the trees behind the table if known, else what a cell can hold
 uint64_t qs::table_max_count(const qs_ctx *c) {
     const uint64_t cell_max = c->count_bits == 16 ? 0xFFFFull : 0xFFFFFFFFull;
-    const uint64_t trees = std::max(c->trees_counted, c->table_trees_hint);
+    const uint64_t trees = std::max(std::max(c->trees_counted, c->table_trees_hint), c->collapse_max_count);   // (a collapsed table's cells exceed its trees)
     return trees ? std::min(trees, cell_max) : cell_max;
 }
 
@@ -287,6 +287,7 @@ extern "C" int qs_table_alloc(qs_ctx *c) {
     if (c->table_mem.reserve(bytes + 16, nullptr) != hipSuccess) { c->table = nullptr; return fail(c, QS_ERR_OOM, "Insufficient memory!"); }
     c->table = c->table_mem.get();
     c->trees_counted = 0;
+    c->collapse_max_count = 0;   // (describes contents that are gone)
     QS_HIP(c, hipMemsetAsync(c->table, 0, bytes + 16, c->stream));
     return QS_OK;
 }
@@ -319,6 +320,7 @@ extern "C" int qs_table_clear(qs_ctx *c) {
     QS_HIP(c, hipSetDevice(c->device));
     QS_HIP(c, hipMemsetAsync(c->table, 0, (size_t)qs_table_bytes(c), c->stream));
     c->trees_counted = 0;
+    c->collapse_max_count = 0;   // (describes contents that are gone)
     return QS_OK;
 }
 
@@ -460,6 +462,7 @@ static int table_reindex(qs_ctx *dst, const qs_ctx *src, const uint16_t *src_id_
     else
         QS_HIP(dst, launch_table_remap(dst->stream, src->table, (int)src->count_bits, dst->table, (int)dst->count_bits, dst->remap_ids.get(), dst->n, dst->n_tuples));
     dst->trees_counted = src->trees_counted;   // sizes the log table and the 16-bit overflow guard of later counts
+    dst->collapse_max_count = src->collapse_max_count;   // (the cells of a collapsed source stay as large as they were)
     return QS_OK;   // asynchronous on dst's stream
 }
 
@@ -472,6 +475,59 @@ extern "C" int qs_table_remap(qs_ctx *dst, const qs_ctx *src, const uint16_t *sr
 // trees-counted; scores never depend on it). The reference rejects a leaf it does not know and recounts per run: this replaces
 // nothing there.
 extern "C" int qs_table_restrict(qs_ctx *dst, const qs_ctx *src, const uint16_t *src_id_of) { return table_reindex(dst, src, src_id_of, true); }
+
+// The table of `src` (individuals) summed into the table of the species that own them (qs_collapse.hip): species i owns the source ids
+// [first_id[i], first_id[i + 1]), and a destination tuple is the sum of the source tuples over one individual per species. A cell of
+// dst can exceed trees-counted afterwards: collapse_max_count tells the score's log table and the whole-table queries so. The
+// reference has no species map (its TaxonMapper is dead code): this replaces nothing there.
+extern "C" int qs_table_collapse(qs_ctx *dst, const qs_ctx *src, const uint16_t *first_id) {
+    const std::string fn = "qs_table_collapse: ";
+    if (dst) dst->log_valid = false;   // (the table changes: a logged pass 1 no longer describes it)
+    if (!dst) return QS_ERR_ARG;
+    if (!src || !first_id) return fail(dst, QS_ERR_ARG, fn + "NULL argument");
+    if (dst == src) return fail(dst, QS_ERR_ARG, fn + "source and destination are the same context");
+    if (dst->d_lo != 0 || dst->d_hi != dst->n || src->d_lo != 0 || src->d_hi != src->n)
+        return fail(dst, QS_ERR_UNSUPPORTED, fn + "whole-table contexts only (no table shards)");
+    if (dst->n > src->n) return fail(dst, QS_ERR_ARG, fn + "the destination has more taxa than the source");
+    if (dst->device != src->device) return fail(dst, QS_ERR_ARG, fn + "the contexts are on different devices");
+    if (!dst->table || !src->table) return fail(dst, QS_ERR_STATE, fn + "the " + (src->table ? "destination" : "source") + " has no table");
+    if (dst->table == src->table) return fail(dst, QS_ERR_ARG, fn + "source and destination share their table");
+    if (dst->count_bits < src->count_bits) return fail(dst, QS_ERR_ARG, fn + "32-bit cells cannot be narrowed to 16 bits");
+    if (src->n > 4096) return fail(dst, QS_ERR_UNSUPPORTED, fn + "more than 4096 source taxa");
+    if (first_id[0] != 0 || first_id[dst->n] != src->n) return fail(dst, QS_ERR_ARG, fn + "first_id does not run from 0 to the source's n_taxa");
+    for (uint32_t i = 0; i < dst->n; ++i)
+        if (first_id[i + 1] <= first_id[i]) return fail(dst, QS_ERR_ARG, fn + "first_id is not strictly increasing (group " + std::to_string(i) + " is empty)");
+    // the largest sum: (largest source count) x the four largest groups
+    uint64_t top[4] = {1, 1, 1, 1};
+    for (uint32_t i = 0; i < dst->n; ++i) {
+        uint64_t g = first_id[i + 1] - first_id[i];
+        for (uint64_t &t : top) if (g > t) std::swap(g, t);
+    }
+    const uint64_t src_max = table_max_count(src), prod = top[0] * top[1] * top[2] * top[3];   // (groups sum to <= 4096: below 2^40)
+    const uint64_t bound = src_max > UINT64_MAX / prod ? UINT64_MAX : src_max * prod;
+    const size_t id_words = 4097 + (size_t)src->n;   // first_id | the species of every source id
+    QS_HIP(dst, hipSetDevice(dst->device));
+    QS_HIP(dst, dst->collapse_ids_dev.reserve((4097 + 4096) * sizeof(uint16_t), &dst->stream));
+    QS_HIP(dst, hipStreamSynchronize(dst->stream));   // (an earlier call's upload may still read the host copy)
+    dst->collapse_ids.assign(id_words, 0);
+    for (uint32_t i = 0; i <= dst->n; ++i) dst->collapse_ids[i] = first_id[i];
+    for (uint32_t i = 0; i < dst->n; ++i)
+        for (uint32_t a = first_id[i]; a < first_id[i + 1]; ++a) dst->collapse_ids[4097 + a] = (uint16_t)i;
+    if (src->stream != dst->stream) {   // the source's counting (or upload) first
+        hipEvent_t ev = nullptr;
+        QS_HIP(dst, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        hipError_t e = hipEventRecord(ev, src->stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(dst->stream, ev, 0);
+        (void)hipEventDestroy(ev);
+        QS_HIP(dst, e);
+    }
+    QS_HIP(dst, hipMemcpyAsync(dst->collapse_ids_dev.get(), dst->collapse_ids.data(), id_words * sizeof(uint16_t), hipMemcpyHostToDevice, dst->stream));
+    QS_HIP(dst, launch_table_collapse(dst->stream, src->table, (int)src->count_bits, dst->table, (int)dst->count_bits, dst->collapse_ids_dev.get(),
+                                      dst->n, src->n, dst->dev_flags.get()));
+    dst->trees_counted = src->trees_counted;
+    dst->collapse_max_count = bound;   // (sizes the log table of the device QIC: ensure_score_tables)
+    return QS_OK;   // asynchronous on dst's stream
+}
 
 extern "C" int qs_sync(qs_ctx *c) {
     if (!c) return QS_ERR_ARG;

@@ -653,7 +653,7 @@ static int run_launch(qs_ctx *c, const qs_device_batch *b, const Launch &L, uint
         bool has_fix = false;   // (never the byte-SWAR kernel: its panel holds the trees' own depths)
         for (int mo = 0; mo < 4 && bitsliced && d.n_fix; ++mo) has_fix = has_fix || (seg_groups[mo] && clamp_fix_work(b, seg_slot[mo], seg_slot[mo] + seg_trees[mo]) > 0);
         // (with the first overwriting launch enqueued the old contents are gone: a later refusal must not leave their count behind)
-        auto overwritten = [&] { if (ow) { if (wire) c->wire_trees = 0; else c->trees_counted = 0; } };
+        auto overwritten = [&] { if (ow) { if (wire) c->wire_trees = 0; else { c->trees_counted = 0; c->collapse_max_count = 0; } } };
         first = false;
         if (has_fix && d_mid) {
             // THE ORDERING RULE of a split slice. A correction must land after the store of the cell it corrects, and a cell belongs to
@@ -751,6 +751,7 @@ extern "C" int qs_count_batch(qs_ctx *c, const qs_device_batch *b, uint32_t algo
         if (algo & QS_COUNT_OVERWRITE) { // "discard the previous contents" holds for an empty batch too
             QS_HIP(c, hipMemsetAsync(c->table, 0, c->n_tuples * 3 * (c->count_bits / 8), c->stream));
             c->trees_counted = 0;
+            c->collapse_max_count = 0;
         }
         c->last_timed = false;
         return QS_OK;
@@ -851,6 +852,8 @@ extern "C" int qs_count_batch(qs_ctx *c, const qs_device_batch *b, uint32_t algo
     }
     c->last_timed = timed;
     c->trees_counted = (overwrite ? 0 : c->trees_counted) + d.n_trees;
+    // (a collapsed table's bound: gone with the contents, else every cell may grow by the trees counted on top)
+    c->collapse_max_count = overwrite || !c->collapse_max_count ? 0 : (c->collapse_max_count > UINT64_MAX - d.n_trees ? UINT64_MAX : c->collapse_max_count + d.n_trees);
     return QS_OK;
 }
 

@@ -199,7 +199,7 @@ int qs::get_ref(qs_ctx *c, const qs_ref_tree *ref, bool want_dev, const RefHost 
 int qs::ensure_score_tables(qs_ctx *c) {
     // every count and every tuple sum is at most the number of trees behind the table: what this context counted, or what
     // the caller says stands behind a reduced / uploaded / viewed table (QS_TUNE_TABLE_TREES)
-    const uint64_t want64 = std::min<uint64_t>(std::max<uint64_t>(std::max(c->trees_counted, c->table_trees_hint) + 1, 65536), 1ull << 20);
+    const uint64_t want64 = std::min<uint64_t>(std::max<uint64_t>(std::min<uint64_t>(std::max(std::max(c->trees_counted, c->table_trees_hint), c->collapse_max_count), 1ull << 20) + 1, 65536), 1ull << 20);
     const uint32_t want = (uint32_t)want64;
     if (c->tbl_n >= want) return QS_OK;
     c->tbl_n = 0;   // (entries that are valid, not the capacity: set again once the new table is on the device)

@@ -161,6 +161,12 @@ struct qs_ctx {
     uint32_t tune_score_sample = 64u | 65536u;             // QS_TUNE_SCORE_SAMPLE: pre-pass of the single-read scoring (0 = none; S | by-round bit 16)
     uint64_t tune_score_log_cap = 0;             // QS_TUNE_SCORE_LOG_CAP: records the log may hold (0 = 8 M); tests force overflows
     DevBuf<uint16_t> remap_ids;                  // qs_table_remap / qs_table_restrict: src_id_of on the device (n entries)
+    // qs_table_collapse: first_id and the species of every source id (host copy kept until the upload on `stream` has read it), and
+    // the largest sum a cell of the collapsed table may hold (trees x the four largest groups; 0 = never collapsed into): cells
+    // can exceed trees-counted then, which sizes the log table and the partial sums of the whole-table queries
+    std::vector<uint16_t> collapse_ids;
+    DevBuf<uint16_t> collapse_ids_dev;
+    uint64_t collapse_max_count = 0;
     // qs_tree_agreement: the reference tree's inner nodes (>= 3 links) as id boundaries on the device, and the tree they came from
     std::vector<int32_t> agree_parent;
     std::vector<uint32_t> agree_leaf_node;

@@ -151,6 +151,10 @@ hipError_t launch_table_remap(hipStream_t s, const void *src, int src_bits, void
 // the map is strictly increasing (no sort, slots are the identity); cell widths as above
 hipError_t launch_table_restrict(hipStream_t s, const void *src, int src_bits, void *dst, int dst_bits, const uint16_t *src_id_of_dev,
                                  uint32_t n_dst, uint64_t n_tuples, bool monotone);
+// qs_collapse.hip: dst (n_dst species) <- the sums of src (n_src individuals) over one individual per species; ids_dev = first_id
+// (n_dst + 1 entries) and, from entry 4097 on, the species of every source id; a sum beyond dst's cell width raises *overflow_flag
+hipError_t launch_table_collapse(hipStream_t s, const void *src, int src_bits, void *dst, int dst_bits, const uint16_t *ids_dev,
+                                 uint32_t n_dst, uint32_t n_src, uint32_t *overflow_flag);
 // qs_agree.hip: per-tree quartet agreement with the reference (qs_tree_agreement); the reference's inner nodes with >= 3
 // links as id boundaries (ref_off / ref_bnd, ref_par = has a parent link); dst = 4 words per tree of the batch
 hipError_t launch_tree_agree(hipStream_t s, const DeviceBatch &b, uint32_t n, uint32_t max_tree_nodes, const uint32_t *ref_off,

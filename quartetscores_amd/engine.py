@@ -753,6 +753,16 @@ class Context:
             raise ValueError(f"table_restrict: src_id_of needs {self.n} entries, got {ids.shape}")
         self._chk(self.L.qs_table_restrict(self.h, src.h, ids.ctypes.data_as(C.c_void_p)))
 
+    def table_collapse(self, src: "Context", first_id):
+        """qs_table_collapse: this context's table (species) := the sums of `src`'s table (individuals) over one individual per
+        species. Species i owns src's ids [first_id[i], first_id[i + 1]) (flatten.species_layout); n_taxa + 1 entries from 0 to
+        src's n_taxa, strictly increasing. A sum beyond this context's cell width raises QS_ERR_OVERFLOW at the next sync().
+        Asynchronous on this context's stream."""
+        ids = np.ascontiguousarray(first_id, dtype=np.uint16)
+        if ids.shape != (self.n + 1,) or (np.asarray(first_id).astype(np.int64) != ids).any():
+            raise ValueError(f"table_collapse: first_id needs {self.n + 1} entries in [0, 65535], got {np.shape(first_id)}")
+        self._chk(self.L.qs_table_collapse(self.h, src.h, ids.ctypes.data_as(C.c_void_p)))
+
     def tree_agreement(self, ref: flatten.RefTree, hb) -> np.ndarray:
         """qs_tree_agreement: per tree of the uploaded batch `hb` (uploaded with its node ranges) its quartet agreement with `ref`
         -> uint64 (n_trees, 4) in AGREEMENT_FIELDS order (agreement_columns derives the rest). Allocates the device buffer,
@@ -1170,14 +1180,23 @@ class QuartetCounterLookup:
 
     def __init__(self, refTree: Union[str, flatten.RefTree], evalTreesPath, m: Optional[int] = None, savemem: bool = False,
                  *, count_bits: Optional[int] = None, device: int = 0, stream: int = 0, algo: int = QS_ALGO_AUTO,
-                 batch_trees: int = 4096, table_tensor=None):
+                 batch_trees: int = 4096, table_tensor=None, species_map=None):
         self.ref = refTree if isinstance(refTree, flatten.RefTree) else flatten.flatten_reference(refTree)
         texts = _read_eval(evalTreesPath)
-        batch = flatten.flatten_eval_trees(texts, self.ref.name_to_id)  # raises UnknownTaxonError like QCL:218
+        # species_map ({species: [individuals]} or the text of a map file): the evaluation trees' leaves are individuals; count
+        # under their ids, then collapse into the species' table (qs_table_collapse) and let the individuals' table go
+        layout = None
+        if species_map is not None and table_tensor is not None:
+            raise ValueError("table_tensor and species_map do not go together: the tensor would hold the individuals' table, and the species' "
+                             "table that takes its place is the context's own")
+        if species_map is not None:
+            layout = flatten.species_layout(self.ref, flatten.parse_species_map(species_map) if isinstance(species_map, str) else species_map)
+        name_to_id = layout.name_to_id if layout else self.ref.name_to_id
+        batch = flatten.flatten_eval_trees(texts, name_to_id)  # raises UnknownTaxonError like QCL:218
         self.m = batch.n_trees if m is None else m
         self.savemem = savemem
         bits = count_bits or count_bits_for(self.m)
-        self.ctx = Context(self.ref.n_taxa, bits, device, stream)
+        self.ctx = Context(len(name_to_id), bits, device, stream)
         if table_tensor is not None:
             self.ctx.table_attach(table_tensor)
             self.ctx.table_clear()
@@ -1186,6 +1205,14 @@ class QuartetCounterLookup:
         for lo in range(0, batch.n_trees, batch_trees):
             hi = min(batch.n_trees, lo + batch_trees)
             self.ctx.count_trees(batch.slice(lo, hi) if (lo, hi) != (0, batch.n_trees) else batch, algo)
+        if layout:
+            sizes = np.sort(np.diff(layout.first_id.astype(np.int64)))[-4:]
+            species = Context(self.ref.n_taxa, 16 if bits == 16 and self.m * int(np.prod(sizes)) < 65536 else 32, device, stream)
+            species.table_alloc()
+            species.table_collapse(self.ctx, layout.first_id)
+            species.sync()   # (a sum beyond 32 bits raises here)
+            self.ctx.close()
+            self.ctx = species
         # "lookup table size in bytes: ..." (QuartetCounterLookup.hpp:268-272)
         self.lookup_table_bytes = self.ctx.table_bytes
         self._node_to_lookup = {int(v): i for i, v in enumerate(self.ref.leaf_node)}

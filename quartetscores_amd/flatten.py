@@ -82,6 +82,72 @@ def taxon_restriction(ref_dst: RefTree, ref_src: RefTree) -> np.ndarray:
     return np.array([ref_src.name_to_id[nm] for nm in ref_dst.names], dtype=np.uint16)
 
 
+def parse_species_map(text: str) -> Dict[str, List[str]]:
+    """The text of a species map in ASTRAL's format -> {species: [individuals]} in file order. One line per species,
+    `species:ind1,ind2,...`; blank lines and lines that start with `#` are ignored, surrounding blanks are trimmed. Raises
+    ValueError naming the offending label for a line without a colon, an empty name, an empty individual list and a species
+    that has two lines (what the map means beside a reference tree is species_layout's business)."""
+    mapping: Dict[str, List[str]] = {}
+    for no, line in enumerate(text.splitlines(), 1):
+        line = line.strip()
+        if not line or line.startswith("#"):
+            continue
+        if ":" not in line:
+            raise ValueError(f"species map line {no}: no ':' in '{line}'")
+        species, rest = (x.strip() for x in line.split(":", 1))
+        if not species:
+            raise ValueError(f"species map line {no}: no species name in front of ':'")
+        inds = [x.strip() for x in rest.split(",")] if rest.strip() else []
+        if not inds:
+            raise ValueError(f"species map line {no}: species '{species}' has an empty individual list")
+        if any(not x for x in inds):
+            raise ValueError(f"species map line {no}: species '{species}' lists an empty individual name")
+        if species in mapping:
+            raise ValueError(f"species map line {no}: species '{species}' has two lines")
+        mapping[species] = inds
+    return mapping
+
+
+@dataclass
+class SpeciesLayout:
+    names: List[str]                # counting id -> individual's name
+    name_to_id: Dict[str, int]
+    first_id: np.ndarray            # uint16[n_species + 1]: species i (the reference's lookup id) owns ids [first_id[i], first_id[i + 1])
+
+
+MAX_INDIVIDUALS = 4096              # qs_create's cap on n_taxa
+
+
+def species_layout(ref: RefTree, mapping: Dict[str, Sequence[str]]) -> SpeciesLayout:
+    """The counting order of the individuals behind the species tree `ref`: species in ref's lookup-id order, individuals in
+    map order within a species; a leaf of ref without an entry is a species with one individual of the same name. Raises
+    ValueError naming the label for a species that is no leaf of ref, an individual listed twice (under one species or two),
+    an individual named like an unlisted species, an empty individual list, more than 4096 individuals and fewer than 4
+    species."""
+    owner: Dict[str, str] = {}
+    for species, inds in mapping.items():
+        if species not in ref.name_to_id:
+            raise ValueError(f"species map: species '{species}' is not a leaf of the reference tree")
+        if len(inds) == 0:
+            raise ValueError(f"species map: species '{species}' has an empty individual list")
+        for ind in inds:
+            if ind in owner:
+                raise ValueError(f"species map: individual '{ind}' is listed twice (species '{owner[ind]}' and '{species}')")
+            if ind in ref.name_to_id and ind not in mapping:
+                raise ValueError(f"species map: individual '{ind}' of species '{species}' has the name of the unlisted species '{ind}'")
+            owner[ind] = species
+    if ref.n_taxa < 4:
+        raise ValueError(f"species map: fewer than 4 species ({ref.n_taxa}) in the reference tree")
+    names: List[str] = []
+    first = [0]
+    for species in ref.names:
+        names.extend(mapping.get(species, [species]))
+        first.append(len(names))
+    if len(names) > MAX_INDIVIDUALS:
+        raise ValueError(f"species map: {len(names)} individuals in all, more than {MAX_INDIVIDUALS}")
+    return SpeciesLayout(names, {nm: i for i, nm in enumerate(names)}, np.asarray(first, dtype=np.uint16))
+
+
 @dataclass
 class TreeBatch:
     n_trees: int
